@@ -3,12 +3,16 @@
 graph construction + transitive reduction (BASELINE.json metric), synthetic input of the
 named shape resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c5|c2s|c3s|c5s]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c5|c2s|c3s|c5s] [--full] [--dump-outputs DIR]
 
 One step = one pass of the whole hot path over the data set: rala_hip_initialize
 (duplicate removal, bound bucketing, pile build + annotation), rala_hip_construct
 (second overlap pass, containment fixed point, preprocess tail, graph build) and
-rala_hip_remove_transitive_edges.  Prints ONE JSON line on rank 0.  The workloads c3s / c5s add
+rala_hip_remove_transitive_edges.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times
+the K steps and prints the line; `--full` adds what takes work of its own: the step's result against the
+committed digests, the host-fed and end-to-end-from-PAF figures, the traffic passes under rocprofv3 and the
+CPU baseline (each can still be left out with its --no-* option).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs).  The workloads c3s / c5s add
 the sensitive second pass (`rala -s`, reference graph.cpp:882-1054) to every step: the sensitive
 overlaps - derived from the piles of an untimed first pass, as the two-run workflow of the
 reference derives them from its `-p` output - lie in HBM like the primary ones.
@@ -425,6 +429,46 @@ def result_check(data_name, with_sens, first, last, valid, row_fnv, row_sum, ran
     return out, out["ok"] is not False
 
 
+DUMP_BUDGET = 60 << 20      # bytes of .npy data at most (--dump-outputs promises 64 MB)
+
+
+def step_outputs(ctx, n_tr, whole):
+    """what a caller of the timed path receives after its last step, from `ctx`: the graph with its transitive marks and the
+    read state; `whole` (one context holds every read): also the piles' medians, the overlaps' validity and the sum of every
+    pile row over its valid region.  A rank of a sharded run holds the graph and begin / end / alive as copies."""
+    g = ctx.graph()
+    p = ctx.piles()
+    out = {"transitive_pairs": np.array([n_tr], dtype=np.uint64)}
+    for k in ("node_read", "src", "dst", "len", "marked"):
+        out["graph_" + k] = g[k]
+    for k in ("begin", "end", "alive") + (("median", "p10") if whole else ()):
+        out["pile_" + k] = p[k]
+    if whole:
+        out["valid"] = ctx.valid()
+        out["pile_row_sum"] = ctx.pile_row_digests()[1]
+    return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 where every value is exact in it, float64 otherwise.  An array
+    longer than its share of DUMP_BUDGET keeps a seeded sample of its entries (the same positions for the same length, so two
+    builds compare entry for entry); lengths.npy holds the full lengths, in the order of the names sorted."""
+    import zlib
+
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET // (len(arrays) + 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).ravel()
+        exact32 = a.size == 0 or (int(a.max()) < (1 << 24) and int(a.min()) > -(1 << 24))
+        dt = np.dtype(np.float32 if exact32 else np.float64)
+        cap = share // dt.itemsize
+        if a.size > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.unique(rng.integers(0, a.size, size=cap))]
+        np.save(os.path.join(d, name + ".npy"), a.astype(dt))
+    np.save(os.path.join(d, "lengths.npy"), np.array([np.asarray(arrays[k]).size for k in sorted(arrays)], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -441,7 +485,14 @@ def main():
                     help="ranks as threads only: RCCL (default) or the in-process transport (peer copies)")
     ap.add_argument("--devices", default=os.environ.get("RALA_GPU_DEVICES", ""),
                     help="ranks as threads only: device ordinal per rank, comma separated (default 0,1,...)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the result check, the host-fed and end-to-end figures, the traffic passes and the CPU baseline "
+                         "(a plain run prints the timed steps' line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_e2e = args.no_traffic = args.no_result_check = True
 
     import torch
 
@@ -621,6 +672,15 @@ def main():
         from rala_amd import multi as _m
         dt = _m.max_over_ranks(dt)
 
+    if args.dump_outputs and rank == 0:
+        if use_dist:
+            outputs = step_outputs(runner.mg.context(), n_tr, False)
+        elif use_threads:
+            outputs = step_outputs(runner.ranks[0].context(), n_tr, False)
+        else:
+            outputs = step_outputs(ctx, n_tr, True)
+        dump_outputs(args.dump_outputs, outputs)
+
     # ---- the result of the timed path against the committed digests (outside the timed region) ----
     check, check_ok = None, True
     if not args.no_result_check:
@@ -722,8 +782,8 @@ def main():
             out["result_check"] = check
         if not sharded:
             ctx.close()                 # the end-to-end run creates a context of its own: give the memory back first
-        # (the full run only - what the driver launches; the quick runs of tests and measurement scripts pass --no-cpu-baseline -
-        # and not inside a profiler)
+        # (--full only, and there not beside --no-cpu-baseline - the quick runs of tests and measurement scripts pass it - nor
+        # inside a profiler)
         under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
         if (not args.no_traffic and not args.no_cpu_baseline and not sharded and world == 1 and not under_profiler and
                 not os.environ.get("RALA_BENCH_CHILD")):

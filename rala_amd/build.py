@@ -15,6 +15,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "rala_amd")
 REFERENCE = "/root/reference"
+REFCLI = os.path.join(ROOT, "oracle", "_ref", "rala_ref")      # the reference's command line (build_reference_cli)
 
 
 def _stale(out, srcs):
@@ -146,20 +147,15 @@ def build_host(force=False):
 
 def build_reference_cli(librala, force=False):
     """Drop-in check of SURVEY 8(b): the reference's own command line, compiled from where it
-    lies (never copied), against this package's headers and librala.so.  Only possible where
-    /root/reference exists; the binary (rala_amd/host/_refcli/rala_ref, git-ignored) travels to
-    the GPU box like the other built files."""
+    lies (never copied), against this package's headers and librala.so, by oracle/Makefile's
+    `refcli` target into REFCLI (git-ignored, beside the oracle's other reference builds; it
+    finds librala.so relative to itself).  Only possible where the reference exists."""
     src = os.path.join(REFERENCE, "src", "main.cpp")
     if not os.path.exists(src):
         return None
-    d = os.path.join(PKG, "host")
-    out_dir = os.path.join(d, "_refcli")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "rala_ref")
-    if force or _stale(exe, [src, librala]):
-        _link(["g++", "-O2", "-std=c++11", "-pthread", "-I" + d], exe,
-              [src, librala, "-Wl,-rpath," + d, "-Wl,-rpath," + os.path.join(PKG, "csrc")])
-    return exe
+    _run(["make", "refcli", "REF=" + REFERENCE, "HOST=" + os.path.dirname(librala)] + (["-B"] if force else []),
+         cwd=os.path.join(ROOT, "oracle"))
+    return REFCLI
 
 
 def build_oracle(force=False):
@@ -175,5 +171,5 @@ def build_oracle(force=False):
 
 
 def build_all(force=False):
-    return {"hip": build_hip(force), "synth": build_synth(force), "host": build_host(force),
-            "oracle": build_oracle(force)}
+    oracle = build_oracle(force)        # (first: a forced one empties oracle/_ref, where build_host puts the reference CLI)
+    return {"hip": build_hip(force), "synth": build_synth(force), "host": build_host(force), "oracle": oracle}

@@ -69,7 +69,7 @@ def test_reference_cli_compiles_unchanged():
     if not os.path.exists(os.path.join(build.REFERENCE, "src", "main.cpp")):
         pytest.skip("no /root/reference here")
     build.build_host()
-    exe = os.path.join(build.PKG, "host", "_refcli", "rala_ref")
+    exe = build.REFCLI
     assert os.path.exists(exe)
     r = subprocess.run([exe, "--version"], stdout=subprocess.PIPE)
     assert r.returncode == 0 and r.stdout.strip() == b"v1.0.0"

@@ -55,3 +55,25 @@ def test_result_check_passes_on_the_committed_digests(monkeypatch):
     monkeypatch.setattr(bench, "_dg", lambda *a: next(answers))
     out, ok = bench.result_check("c3", False, first, dict(first), np.zeros(8, np.uint8), np.zeros(1, np.uint64), np.zeros(1, np.uint64), [0, 7])
     assert ok and out["ok"] is True and not out["stages_differ"] and len(out["stages_equal"]) == len(bench.RESULT_STAGES)
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.dump_outputs: float32 where exact, float64 otherwise; an array beyond its share of the budget keeps a seeded sample
+    of its entries, the same in every run; the files together stay under 64 MB"""
+    import bench
+
+    arrays = {"valid": (np.arange(40_000_000) % 3 == 0).astype(np.uint8), "small": np.arange(1000, dtype=np.uint32),
+              "wide": np.arange(3_000_000, dtype=np.uint64) << np.uint64(30), "one": np.array([7], dtype=np.uint64)}
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), arrays)
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == ["lengths.npy", "one.npy", "small.npy", "valid.npy", "wide.npy"]
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in names) <= 64 << 20
+    got = {f: np.load(tmp_path / "0" / f) for f in names}
+    for f in names:
+        assert np.array_equal(got[f], np.load(tmp_path / "1" / f)), f
+    assert got["small.npy"].dtype == np.float32 and np.array_equal(got["small.npy"], np.arange(1000))
+    assert got["wide.npy"].dtype == np.float64 and 0 < len(got["wide.npy"]) < 3_000_000
+    assert np.all(np.fmod(got["wide.npy"], float(1 << 30)) == 0)          # sampled entries, exact
+    assert got["valid.npy"].dtype == np.float32 and 0 < len(got["valid.npy"]) < 40_000_000
+    assert list(got["lengths.npy"]) == [1, 1000, 40_000_000, 3_000_000]

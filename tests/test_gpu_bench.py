@@ -24,12 +24,12 @@ def bench(*args, env=None):
 
 
 def test_bare_bench_runs_one_and_several_ranks():
-    one = bench("--workload", "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e")
+    one = bench("--workload", "c2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e")
     assert one.returncode == 0, one.stderr[-2000:]
     a = json.loads(one.stdout.strip().splitlines()[-1])
     assert a["n_gpus"] == 1 and a["roofline"]["frac"] > 0 and a["roofline"]["stage_frac"] > 0
     many = bench("--gpus", "4", "--transport", "local", "--devices", "0,0,0,0", "--workload", "c2", "--steps", "2",
-                 "--warmup", "1", "--no-cpu-baseline", "--no-e2e")
+                 "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e")
     assert many.returncode == 0, many.stderr[-2000:]
     b = json.loads(many.stdout.strip().splitlines()[-1])
     assert b["n_gpus"] == 4 and b["scaling"] == "strong"
@@ -51,7 +51,7 @@ def test_a_wrong_result_prints_no_figure():
     """a step whose result differs from the committed digests ends with exit code 4 and no line (RALA_BENCH_FAKE_WRONG_RESULT
     turns one digest over before the comparison)"""
     for extra in ((), ("--gpus", "2", "--transport", "local", "--devices", "0,0")):
-        res = bench("--workload", "c2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-e2e", *extra,
+        res = bench("--workload", "c2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-e2e", *extra,
                     env={"RALA_BENCH_FAKE_WRONG_RESULT": "1"})
         assert res.returncode == 4, (res.returncode, res.stderr[-2000:])
         assert not [x for x in res.stdout.splitlines() if x.startswith("{")]
@@ -68,7 +68,7 @@ def test_bench_refuses_more_rccl_ranks_than_devices():
 
 
 def test_bench_end_to_end_figure_is_measured():
-    res = bench("--workload", "c1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
+    res = bench("--workload", "c1", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline")
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
     e2e = line["end_to_end_from_paf"]
@@ -113,7 +113,7 @@ def test_a_rank_without_a_device_fails_the_set_up_at_once():
 def test_sensitive_workload():
     """c2s: the sensitive second pass inside the timed step, its overlaps resident in HBM; the line carries the pass' own
     bytes and time; the same over two ranks that share the device"""
-    one = bench("--workload", "c2s", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e")
+    one = bench("--workload", "c2s", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e")
     assert one.returncode == 0, one.stderr[-2000:]
     a = json.loads(one.stdout.strip().splitlines()[-1])
     sp = a["sensitive_pass"]
@@ -122,7 +122,7 @@ def test_sensitive_workload():
     p = json.loads(plain.stdout.strip().splitlines()[-1])
     assert a["config"]["transitive_pairs"] != p["config"]["transitive_pairs"]          # the pass drops overlaps
     two = bench("--gpus", "2", "--transport", "local", "--devices", "0,0", "--workload", "c2s", "--steps", "2", "--warmup", "1",
-                "--no-cpu-baseline", "--no-e2e")
+                "--full", "--no-cpu-baseline", "--no-e2e")
     assert two.returncode == 0, two.stderr[-2000:]
     b = json.loads(two.stdout.strip().splitlines()[-1])
     assert b["config"]["transitive_pairs"] == a["config"]["transitive_pairs"]
@@ -144,7 +144,7 @@ def test_one_process_per_gpu_launch():
     for wl in ("c2", "c2s"):
         res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                               "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", wl,
-                              "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"],
+                              "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e"],
                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=e, timeout=600)
         assert res.returncode == 0, res.stderr[-3000:]
         lines[wl] = json.loads([x for x in res.stdout.splitlines() if x.startswith("{")][-1])
@@ -169,3 +169,37 @@ def test_traffic_is_measured_in_the_run():
     t = bench.measure_traffic("c2")
     assert t is not None, "the PMC passes failed"
     assert 1.9e9 < t < 2.8e9, t
+
+
+def test_plain_run_is_lean_and_dumps_the_step_outputs(tmp_path):
+    """a plain run prints the timed steps' line alone - no result check, no host-fed or end-to-end figure, no CPU baseline - and
+    --dump-outputs writes what the last step computed (at most 64 MB, float32 / float64): the same arrays from two runs with the
+    same arguments, and a graph whose digests are the committed ones of the reference objects' result"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench as bench_mod
+
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        res = bench("--workload", "c2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        assert line["metric"] and line["unit"] == "overlaps/s" and line["dtype"]
+        assert not set(line) & {"result_check", "cpu_baseline", "end_to_end_from_paf", "from_pinned_host"}
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert int(arrays["transitive_pairs"][0]) == line["config"]["transitive_pairs"]
+        runs.append(arrays)
+    a, b = runs
+    assert a.keys() == b.keys() and {"graph_src", "graph_dst", "pile_begin", "valid", "pile_row_sum"} <= set(a)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_c2.json")))
+    u32 = lambda x: a[x].astype(np.uint32)
+    assert bench_mod._dg(u32("graph_node_read")) == want["nodes"]
+    assert bench_mod._dg(u32("graph_src"), u32("graph_dst"), u32("graph_len"), a["graph_marked"].astype(np.uint8)) == want["edges"]

@@ -281,7 +281,7 @@ def test_reference_cli_drop_in(tmp_path):
     against rala_amd/host's headers (rala_amd/build.py: build_reference_cli; the binary travels to
     the GPU box), gives the same contigs, debug CSV and -p reads as this package's own driver."""
     build.build_host()
-    ref = os.path.join(build.PKG, "host", "_refcli", "rala_ref")
+    ref = build.REFCLI
     if not os.path.exists(ref):
         pytest.skip("reference CLI was not built (no /root/reference where the build ran)")
     exe = os.path.join(build.PKG, "host", "rala")

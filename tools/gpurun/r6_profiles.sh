@@ -3,13 +3,13 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/r06
 mkdir -p $OUT
 cd $ROOT
-python bench.py --steps 20 --warmup 3 > $OUT/r06_c3_bench.json 2> $OUT/bench.log
-python bench.py --workload c3s --steps 10 --warmup 2 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c3s_bench.json
-python bench.py --workload c5 --steps 5 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5_bench_1gpu.json
-python bench.py --workload c5s --steps 4 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5s_bench_1gpu.json
-RALA_FORCE_SHARDED=1 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c3_bench_sharded_world1.json
-RALA_FORCE_SHARDED=1 python bench.py --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5_bench_sharded_world1.json
-python bench.py --gpus 8 --transport local --devices 0,0,0,0,0,0,0,0 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep "^{" > $OUT/r06_c3_bench_8ranks_one_gpu.json
+python bench.py --full --steps 20 --warmup 3 > $OUT/r06_c3_bench.json 2> $OUT/bench.log
+python bench.py --full --workload c3s --steps 10 --warmup 2 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c3s_bench.json
+python bench.py --full --workload c5 --steps 5 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5_bench_1gpu.json
+python bench.py --full --workload c5s --steps 4 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5s_bench_1gpu.json
+RALA_FORCE_SHARDED=1 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c3_bench_sharded_world1.json
+RALA_FORCE_SHARDED=1 python bench.py --full --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-e2e 2>/dev/null | grep "^{" > $OUT/r06_c5_bench_sharded_world1.json
+python bench.py --full --gpus 8 --transport local --devices 0,0,0,0,0,0,0,0 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | grep "^{" > $OUT/r06_c3_bench_8ranks_one_gpu.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e > $OUT/r06_c3_bench_under_rocprof.json 2> $OUT/stats.log
 cp $(ls $OUT/stats/*/*kernel_stats.csv | head -1) $OUT/r06_c3_kernel_stats.csv
