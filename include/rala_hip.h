@@ -135,7 +135,13 @@ int rala_hip_set_overlaps(rala_hip_ctx* ctx, const rala_hip_overlaps* ovl, uint6
  * *irregular != 0: the file is not a plain list of 12-column records (a line with fewer columns, a name of more than a
  * kilobyte ...) - nothing was set, take the host reader (rala_amd/host/io.cpp), which knows what to do with such files.
  * The name table: rala::io::NameTable as built on the host (rala_amd/csrc/name_table.h: 32-byte buckets {hash32, id + 1,
- * length, arena offset, first 16 bytes}, n_buckets a power of two, the names' bytes in `arena`). */
+ * length, arena offset, first 16 bytes}, n_buckets a power of two, the names' bytes in `arena`).
+ * A BGZF file (what bgzip writes: gzip members of at most 64 KB with a "BC" extra field) is taken as well: the compressed
+ * bytes go to the device, a kernel inflates the members into the text the plain file would have given, and the same
+ * kernels tokenise it (ship_ms then counts the compressed bytes; rala_hip_get_inflate_timings: the inflater).  The members
+ * accepted are those the host reader's BgzfSource accepts (rala_amd/host/io.cpp); anything else - a plain single-member
+ * gzip stream (known from its first 18 bytes, before anything is shipped), a cut file, a bad CRC32 or ISIZE, bytes behind
+ * the last member that are no member - gives *irregular & 8 and sets nothing. */
 typedef struct rala_hip_ingest_timings {
     float ship_ms;          /* file -> device memory (reads and copies overlapped) */
     float tokenize_ms;      /* count + scan + parse on the device */
@@ -152,6 +158,21 @@ int rala_hip_set_overlaps_from_paf(rala_hip_ctx* ctx, const char* path, int chec
 int rala_hip_set_overlaps_from_mhap(rala_hip_ctx* ctx, const char* path, int check_lengths, uint32_t threads,
                                     int64_t* length_error_read, int* irregular);
 int rala_hip_get_ingest_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out);
+/* The inflater of the last rala_hip_set_overlaps_from_paf / _mhap call (zeros when the file was not BGZF). */
+typedef struct rala_hip_inflate_timings {
+    float inflate_ms;           /* the members inflated on the device (all windows) */
+    uint64_t compressed_bytes;  /* the file's bytes shipped to the device */
+    uint64_t members;           /* gzip members with text */
+} rala_hip_inflate_timings;
+int rala_hip_get_inflate_timings(rala_hip_ctx* ctx, rala_hip_inflate_timings* out);
+/* The member index of a BGZF file held in memory (no context, no device): the chain of gzip members from byte 0, as the
+ * device ingest builds it - the bytes scanned for member headers in blocks of block_bytes (0: the ingest's 32 MB), then
+ * walked from offset 0.  *valid = 0: not a BGZF file the host reader would take (first 18 bytes not a BGZF header, a cut
+ * member, bytes behind the last member that are no member, ISIZE > 65536).  *n_members: the members (empty ones included);
+ * when cap >= *n_members, each one's file offset, compressed size (BSIZE + 1), text size (ISIZE) and text offset (the
+ * exclusive scan of the text sizes) are written to the arrays given (any may be null). */
+int rala_hip_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, uint64_t cap, uint64_t* n_members, uint64_t* file_off,
+                        uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* text_off, int* valid);
 /* The sensitive overlaps (rala -s; Graph::preprocess, src/graph.cpp:901-939) of an uncompressed PAF file the same way, without
  * the length check (Overlap::transmute_ has none, src/overlap.cpp:84-114): the lines that start in bytes [lo, hi) of the file
  * (hi = ~0: to its end; a rank of a sharded run takes a share - any split of the sensitive set will do).  *out receives DEVICE

@@ -240,6 +240,10 @@ struct rala_hip_ctx {
     int64_t ingest_window_bytes = 0;    // option: the tokeniser's window over the file's text (0: a quarter of the free device memory)
     rala_hip::DevBuf<unsigned long long> d_paf_bad;
     rala_hip_ingest_timings ingest_tm = {};
+    // BGZF overlap files (ingest.hip, inflate_kernels.hip): the compressed bytes, the members' jobs, the inflater's flag
+    rala_hip::DevBuf<uint8_t> d_bgzf_comp, d_bgzf_jobs;
+    rala_hip::DevBuf<uint32_t> d_bgzf_flag;
+    rala_hip_inflate_timings inflate_tm = {};
 
     // overlaps
     uint64_t n_ovl = 0;

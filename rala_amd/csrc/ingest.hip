@@ -7,9 +7,13 @@
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <memory>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -64,61 +68,27 @@ int ingest_fail(rala_hip_ctx* ctx, int code, const std::string& msg) {
         }                                                                                                   \
     } while (0)
 
+struct Fd {                                         // (closed on every way out - ADVICE round 4)
+    int fd = -1;
+    ~Fd() { if (fd >= 0) close(fd); }
+};
+
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-}  // namespace
-
-// The lines that START in bytes [lo, hi) of the file (hi = ~0: to its end), tokenised on the device into `T`'s columns (room for
-// extra_rows more rows than the range holds: a rank of a sharded run receives the heads of its neighbours' first runs).  The
-// text is shipped by reader threads - two pinned staging blocks each, a block's copy queued behind its read - with what the last
-// lines' first eleven columns may need behind hi.
-int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads,
-                                 size_t extra_rows, const PafTarget& T, PafRange* out) {
-    if (!ctx || !path || !out) return RALA_HIP_EINVAL;
-    *out = PafRange();
-    if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_name_buckets == 0 && !T.mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
-    INGEST_CHECK(hipSetDevice(ctx->device));
-    struct Fd {                                     // (closed on every way out - ADVICE round 4)
-        int fd = -1;
-        ~Fd() { if (fd >= 0) close(fd); }
-    } file;
-    file.fd = open(path, O_RDONLY);
-    const int fd = file.fd;
-    if (fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
-    struct stat st;
-    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
-    const uint64_t file_n = (uint64_t)st.st_size;
-    hi = std::min(hi, file_n);
-    lo = std::min(lo, hi);
-    const uint64_t n = hi - lo;                                             // bytes whose line starts are ours
-    const uint64_t n_avail = std::min<uint64_t>(file_n - lo, n + paf_halo_bytes());
-    bool first_is_start = lo == 0;
-    if (lo) {
-        char before = 0;
-        if (pread(fd, &before, 1, (off_t)(lo - 1)) != 1) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
-        first_is_start = before == '\n';
-    }
-    const uint32_t chunk = paf_chunk_bytes();
-    const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
-    const uint64_t cap = n_chunks * chunk + 4096 + 64;
-    hipStream_t s = ctx->stream;
-    const double t0 = now_ms();
-    if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
-    // what lies behind the text reads as newlines
-    INGEST_CHECK(hipMemsetAsync(ctx->d_paf_text.p + n_avail, '\n', cap - n_avail, s));
-
-    // ---- ship: reader threads, two pinned blocks each, a block's copy queued behind its read ----
-    const uint64_t n_blocks = (n_avail + kBlockBytes - 1) / kBlockBytes;
+// The ship stage: bytes [off, off + len) of the file to dev (null: read only) by reader threads - two pinned staging blocks
+// each, a block's copy queued behind its read; scan (optional) sees every block in host memory as it was read.  meanwhile
+// runs on the calling thread while the readers work (false: out of device memory).  0 ok, 1 a read / copy failed, 2 meanwhile failed.
+using BlockScan = std::function<void(uint64_t block, const uint8_t* bytes, size_t n)>;
+int ship_file(int fd, uint64_t off, uint64_t len, uint8_t* dev, int device, uint32_t threads, const BlockScan* scan,
+              const std::function<bool()>& meanwhile, uint32_t* n_readers_out) {
+    const uint64_t n_blocks = (len + kBlockBytes - 1) / kBlockBytes;
     const uint32_t n_readers = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(threads ? threads : 1, kMaxReaders), n_blocks));
+    if (n_readers_out) *n_readers_out = n_readers;
     std::atomic<uint64_t> next(0);
     std::atomic<int> failed(0);
     std::vector<std::thread> readers;
-    uint8_t* const text = ctx->d_paf_text.p;
-    const int device = ctx->device;
     for (uint32_t t = 0; t < n_readers && n_blocks; ++t) {
         readers.emplace_back([&]() {
             if (hipSetDevice(device) != hipSuccess) { failed = 1; return; }
@@ -133,17 +103,19 @@ int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t l
                 const uint64_t b = next.fetch_add(1);
                 if (b >= n_blocks) break;
                 if (busy[k]) ok = hipEventSynchronize(ev[k]) == hipSuccess;       // the block's last copy has left it
-                const uint64_t off = b * kBlockBytes;
-                const size_t len = (size_t)std::min<uint64_t>(kBlockBytes, n_avail - off);
+                const uint64_t o = b * kBlockBytes;
+                const size_t n = (size_t)std::min<uint64_t>(kBlockBytes, len - o);
                 size_t got = 0;
-                while (ok && got < len) {
-                    const ssize_t r = pread(fd, (char*)blk[k] + got, len - got, (off_t)(lo + off + got));
+                while (ok && got < n) {
+                    const ssize_t r = pread(fd, (char*)blk[k] + got, n - got, (off_t)(off + o + got));
                     if (r <= 0) { ok = false; break; }
                     got += (size_t)r;
                 }
-                ok = ok && hipMemcpyAsync(text + off, blk[k], len, hipMemcpyHostToDevice, cs) == hipSuccess &&
-                     hipEventRecord(ev[k], cs) == hipSuccess;
-                busy[k] = ok;
+                if (ok && dev) {
+                    ok = hipMemcpyAsync(dev + o, blk[k], n, hipMemcpyHostToDevice, cs) == hipSuccess && hipEventRecord(ev[k], cs) == hipSuccess;
+                    busy[k] = ok;
+                }
+                if (ok && scan) (*scan)(b, (const uint8_t*)blk[k], n);     // (reads the block while it is copied)
             }
             if (cs) ok = (hipStreamSynchronize(cs) == hipSuccess) && ok;
             if (!ok) failed = 1;
@@ -154,28 +126,35 @@ int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t l
             if (cs) (void)hipStreamDestroy(cs);
         });
     }
-    // While the readers work: the device memory the tokeniser will want.  hipMalloc of a few hundred megabytes takes a
-    // millisecond and more, eight columns of them 4 - 9 ms - behind the copies that is free.  The number of records is not
-    // known yet: a record has at least 23 bytes, files in the wild 60 - 150 per line; room for one per 32 bytes is made now
-    // (twice what a synthetic file needs) and the exact count decides later whether that was enough.
-    {
-        const size_t guess = (size_t)(n / 32) + 1024 + extra_rows;
-        bool ok = true;
-        for (int k = 0; k < 7 && ok; ++k) ok = T.col[k]->ensure(guess) == hipSuccess;
-        ok = ok && T.strand->ensure(guess) == hipSuccess && ctx->d_paf_bad.ensure(2) == hipSuccess;
-        if (n_chunks) {
-            ok = ok && ctx->d_paf_chunk[0].ensure(n_chunks + 2) == hipSuccess && ctx->d_paf_chunk[1].ensure(n_chunks + 2) == hipSuccess &&
-                 ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(std::max<uint64_t>(n_chunks, ctx->n_reads), ctx->n_ovl) + 2)) == hipSuccess;
-        }
-        if (!ok) failed = 2;
-    }
+    const bool room = meanwhile();
     for (auto& th : readers) th.join();
-    if (failed == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
-    if (failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
-    INGEST_CHECK(hipStreamSynchronize(s));
-    const double t1 = now_ms();
+    return !room ? 2 : failed ? 1 : 0;
+}
 
-    // ---- count, scan, parse ----
+// The device memory the tokeniser will want for n bytes of text (made while the readers work: hipMalloc of a few hundred
+// megabytes takes a millisecond and more, eight columns of them 4 - 9 ms - behind the copies that is free).  The number of
+// records is not known yet: a record has at least 23 bytes, files in the wild 60 - 150 per line; room for one per 32 bytes
+// is made now (twice what a synthetic file needs) and the exact count decides later whether that was enough.
+bool tokeniser_memory(rala_hip_ctx* ctx, uint64_t n, uint64_t n_chunks, size_t extra_rows, const PafTarget& T) {
+    const size_t guess = (size_t)(n / 32) + 1024 + extra_rows;
+    bool ok = true;
+    for (int k = 0; k < 7 && ok; ++k) ok = T.col[k]->ensure(guess) == hipSuccess;
+    ok = ok && T.strand->ensure(guess) == hipSuccess && ctx->d_paf_bad.ensure(2) == hipSuccess;
+    if (n_chunks) {
+        ok = ok && ctx->d_paf_chunk[0].ensure(n_chunks + 2) == hipSuccess && ctx->d_paf_chunk[1].ensure(n_chunks + 2) == hipSuccess &&
+             ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(std::max<uint64_t>(n_chunks, ctx->n_reads), ctx->n_ovl) + 2)) == hipSuccess;
+    }
+    return ok;
+}
+
+// What follows once the text is in device memory, for the plain file and the BGZF one alike: count, scan, parse into T's
+// columns (n, n_avail, first_is_start: launch_paf_count / launch_paf_parse), then the text's memory back.  t1: when the
+// text was there; ship_ms = t1 - t0.
+int tokenise_text(rala_hip_ctx* ctx, const uint8_t* text, uint64_t n, uint64_t n_avail, bool first_is_start, bool check_lengths,
+                  size_t extra_rows, const PafTarget& T, PafRange* out, double t0, double t1, uint32_t n_readers) {
+    hipStream_t s = ctx->stream;
+    const uint32_t chunk = paf_chunk_bytes();
+    const uint64_t n_chunks = (n + chunk - 1) / chunk;
     const bool trace = getenv("RALA_HIP_TRACE") != nullptr;
     double tc = t1, tp0 = t1, tp1 = t1;
     uint32_t n_lines = 0;
@@ -223,9 +202,310 @@ int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t l
     out->n_lines = n_lines;
     out->first_bad = bad;
     out->flags = flags;
-    out->file_bytes = file_n;
     return RALA_HIP_OK;
 }
+
+}  // namespace
+
+// The lines that START in bytes [lo, hi) of the file (hi = ~0: to its end), tokenised on the device into `T`'s columns (room for
+// extra_rows more rows than the range holds: a rank of a sharded run receives the heads of its neighbours' first runs).  The
+// text is shipped by reader threads - two pinned staging blocks each, a block's copy queued behind its read - with what the last
+// lines' first eleven columns may need behind hi.
+int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads,
+                                 size_t extra_rows, const PafTarget& T, PafRange* out) {
+    if (!ctx || !path || !out) return RALA_HIP_EINVAL;
+    *out = PafRange();
+    if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
+    if (ctx->n_name_buckets == 0 && !T.mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    Fd file;
+    file.fd = open(path, O_RDONLY);
+    const int fd = file.fd;
+    if (fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    const uint64_t file_n = (uint64_t)st.st_size;
+    hi = std::min(hi, file_n);
+    lo = std::min(lo, hi);
+    const uint64_t n = hi - lo;                                             // bytes whose line starts are ours
+    const uint64_t n_avail = std::min<uint64_t>(file_n - lo, n + paf_halo_bytes());
+    bool first_is_start = lo == 0;
+    if (lo) {
+        char before = 0;
+        if (pread(fd, &before, 1, (off_t)(lo - 1)) != 1) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
+        first_is_start = before == '\n';
+    }
+    const uint32_t chunk = paf_chunk_bytes();
+    const uint64_t n_chunks = (n + chunk - 1) / chunk;
+    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    const uint64_t cap = n_chunks * chunk + 4096 + 64;
+    hipStream_t s = ctx->stream;
+    const double t0 = now_ms();
+    if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+    // what lies behind the text reads as newlines
+    INGEST_CHECK(hipMemsetAsync(ctx->d_paf_text.p + n_avail, '\n', cap - n_avail, s));
+    uint32_t n_readers = 0;
+    const int shipped = ship_file(fd, lo, n_avail, ctx->d_paf_text.p, ctx->device, threads, nullptr,
+                                  [&]() { return tokeniser_memory(ctx, n, n_chunks, extra_rows, T); }, &n_readers);
+    if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+    if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    out->file_bytes = file_n;
+    return tokenise_text(ctx, ctx->d_paf_text.p, n, n_avail, first_is_start, check_lengths, extra_rows, T, out, t0, t1, n_readers);
+}
+
+// ---- BGZF: the member index -------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kHeaderReach = 12 + 65535;      // the bytes a member header may occupy (XLEN < 2^16)
+
+struct BgzfCand {
+    uint64_t pos;
+    uint32_t bsize;         // the member's bytes (BSIZE + 1); 0: no member header the host reader would take
+    uint32_t hdr;           // 12 + XLEN
+    uint32_t prev_isize;    // the 4 bytes in front of pos (the ISIZE of a member that ends here)
+};
+struct BgzfMember {
+    uint64_t off, text_off;
+    uint32_t bsize, hdr, isize;
+};
+
+// is_bgzf of the host reader (io.cpp, BgzfSource): the first 18 bytes
+bool bgzf_head(const uint8_t* h, uint64_t n) {
+    return n >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) != 0 && h[10] == 6 && h[11] == 0 && h[12] == 'B' &&
+           h[13] == 'C' && h[14] == 2 && h[15] == 0;
+}
+
+// The member-header candidates among the bytes [off, off + n) of a file of file_n bytes: at(q) gives byte q for q in
+// [off - min(off, 8), min(file_n, off + n + kHeaderReach)).  A candidate is every 0x1f 0x8b 0x08 with FEXTRA; its BSIZE
+// is read as read_block reads it (BgzfSource: any XLEN, the last "BC" subfield of length 2, bsize >= 12 + XLEN + 8).
+template <class At>
+void bgzf_scan(const uint8_t* bytes, uint64_t n, uint64_t off, uint64_t file_n, const At& at, std::vector<BgzfCand>& out) {
+    const uint8_t* const end = bytes + n;
+    for (const uint8_t* h = (const uint8_t*)memchr(bytes, 0x1f, n); h; h = (const uint8_t*)memchr(h + 1, 0x1f, (size_t)(end - h - 1))) {
+        const uint64_t q = off + (uint64_t)(h - bytes);
+        if (q + 12 > file_n) break;
+        if (at(q + 1) != 0x8b || at(q + 2) != 8 || !(at(q + 3) & 4)) {
+            if (h + 1 >= end) break;
+            continue;
+        }
+        BgzfCand c;
+        c.pos = q;
+        c.bsize = 0;
+        c.prev_isize = 0;
+        if (q >= 4) for (int k = 3; k >= 0; --k) c.prev_isize = (c.prev_isize << 8) | at(q - 4 + (uint64_t)k);
+        const uint32_t xlen = at(q + 10) | (uint32_t)at(q + 11) << 8;
+        c.hdr = 12 + xlen;
+        if (q + 12 + xlen <= file_n) {
+            uint32_t bsize = 0;
+            for (uint32_t k = 0; k + 4 <= xlen;) {
+                const uint64_t e = q + 12 + k;
+                const uint32_t slen = at(e + 2) | (uint32_t)at(e + 3) << 8;
+                if (at(e) == 'B' && at(e + 1) == 'C' && slen == 2 && k + 6 <= xlen) bsize = (at(e + 4) | (uint32_t)at(e + 5) << 8) + 1;
+                k += 4 + slen;
+            }
+            if (bsize >= 12 + xlen + 8) c.bsize = bsize;
+        }
+        out.push_back(c);
+        if (h + 1 >= end) break;
+    }
+}
+
+// The chain of members from offset 0 through the candidates (in file order); tail: the file's last 4 bytes (the last member's
+// ISIZE).  false: the chain breaks - a position with no member header, a member beyond the end, ISIZE > 65536.
+bool bgzf_walk(const std::vector<std::vector<BgzfCand>>& blocks, uint64_t file_n, uint32_t tail, std::vector<BgzfMember>& members) {
+    members.clear();
+    uint64_t o = 0;
+    size_t b = 0, i = 0;
+    while (o < file_n) {
+        while (b < blocks.size() && (i >= blocks[b].size() || blocks[b][i].pos < o)) {
+            if (i >= blocks[b].size()) { ++b; i = 0; } else { ++i; }
+        }
+        if (b >= blocks.size()) return false;
+        const BgzfCand& c = blocks[b][i];
+        if (c.pos != o || c.bsize == 0 || o + c.bsize > file_n) return false;
+        if (!members.empty()) members.back().isize = c.prev_isize;
+        BgzfMember m;
+        m.off = o; m.bsize = c.bsize; m.hdr = c.hdr; m.isize = 0; m.text_off = 0;
+        members.push_back(m);
+        o += c.bsize;
+    }
+    if (!members.empty()) members.back().isize = tail;
+    uint64_t t = 0;
+    for (BgzfMember& m : members) {
+        if (m.isize > 65536) return false;
+        m.text_off = t;
+        t += m.isize;
+    }
+    return true;
+}
+
+uint32_t le32(const uint8_t* p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// the index of a file in memory, scanned in blocks of block_bytes (what the readers do with their staging blocks)
+bool bgzf_index_bytes(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, std::vector<BgzfMember>& members) {
+    if (!bgzf_head(bytes, n)) return false;
+    const uint64_t n_blocks = (n + block_bytes - 1) / block_bytes;
+    std::vector<std::vector<BgzfCand>> cand(n_blocks);
+    auto at = [&](uint64_t q) { return bytes[q]; };
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        const uint64_t off = b * block_bytes;
+        bgzf_scan(bytes + off, std::min(block_bytes, n - off), off, n, at, cand[b]);
+    }
+    return bgzf_walk(cand, n, le32(bytes + n - 4), members);
+}
+
+// A BGZF file on the device: the members indexed while the file is read once (every reader thread scans its staging blocks
+// for member headers; the chain is walked from offset 0 after the join), the compressed bytes kept in device memory when
+// they fit the window (else shipped window by window: the members that cover it), the members inflated into the text
+// buffer, and from there on the plain file's way (tokenise_text).
+struct BgzfFile {
+    Fd file;
+    uint64_t file_n = 0, text_n = 0;
+    std::vector<BgzfMember> jobs;       // the members with text, in file order
+    uint64_t n_members = 0;
+    bool resident = false;              // all compressed bytes in ctx->d_bgzf_comp
+    float ship_ms = 0, inflate_ms = 0;
+    uint64_t shipped = 0;
+    uint32_t n_readers = 0;
+};
+
+// index the file (and ship it when it fits); *valid = false: not a chain of members the host reader takes
+int bgzf_open(rala_hip_ctx* ctx, const char* path, uint32_t threads, uint64_t window, BgzfFile& f, bool* valid) {
+    *valid = false;
+    f.file.fd = open(path, O_RDONLY);
+    if (f.file.fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+    struct stat st;
+    if (fstat(f.file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    f.file_n = (uint64_t)st.st_size;
+    if (f.file_n < 18) return RALA_HIP_OK;
+    const double t0 = now_ms();
+    f.resident = f.file_n <= window;
+    if (f.resident && ctx->d_bgzf_comp.ensure(f.file_n + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    const int fd = f.file.fd;
+    const uint64_t file_n = f.file_n;
+    const uint64_t n_blocks = (file_n + kBlockBytes - 1) / kBlockBytes;
+    std::vector<std::vector<BgzfCand>> cand(n_blocks);
+    std::atomic<int> edge_failed(0);
+    const BlockScan scan = [&](uint64_t b, const uint8_t* bytes, size_t n) {
+        // the block, the 8 bytes in front of it and what a header that starts in it may reach behind it
+        const uint64_t off = b * kBlockBytes;
+        uint8_t pre[8];
+        const uint64_t n_pre = std::min<uint64_t>(8, off);
+        std::vector<uint8_t> ext((size_t)std::min<uint64_t>(kHeaderReach, file_n - off - n));
+        if ((n_pre && pread(fd, pre, n_pre, (off_t)(off - n_pre)) != (ssize_t)n_pre) ||
+            (!ext.empty() && pread(fd, ext.data(), ext.size(), (off_t)(off + n)) != (ssize_t)ext.size())) {
+            edge_failed = 1;
+            return;
+        }
+        auto at = [&](uint64_t q) -> uint8_t {
+            if (q < off) return pre[n_pre - (off - q)];
+            if (q < off + n) return bytes[q - off];
+            return ext[q - off - n];
+        };
+        bgzf_scan(bytes, n, off, file_n, at, cand[b]);
+    };
+    const int shipped = ship_file(fd, 0, file_n, f.resident ? ctx->d_bgzf_comp.p : nullptr, ctx->device, threads, &scan,
+                                  []() { return true; }, &f.n_readers);
+    if (shipped || edge_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    uint8_t tail[4];
+    if (pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
+    std::vector<BgzfMember> members;
+    if (!bgzf_walk(cand, file_n, le32(tail), members)) return RALA_HIP_OK;
+    f.n_members = members.size();
+    for (const BgzfMember& m : members) {
+        if (m.isize) f.jobs.push_back(m);
+        f.text_n += m.isize;
+    }
+    f.shipped = f.resident ? file_n : 0;
+    f.ship_ms = (float)(now_ms() - t0);
+    *valid = true;
+    return RALA_HIP_OK;
+}
+
+// bgzf's paf_tokenise_range: the lines that start in bytes [lo, hi) of the file's TEXT
+int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads, const PafTarget& T,
+                        PafRange* out) {
+    *out = PafRange();
+    hi = std::min(hi, f.text_n);
+    lo = std::min(lo, hi);
+    const uint64_t n = hi - lo;
+    const uint64_t n_avail = std::min<uint64_t>(f.text_n - lo, n + paf_halo_bytes());
+    const uint32_t chunk = paf_chunk_bytes();
+    const uint64_t n_chunks = (n + chunk - 1) / chunk;
+    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    const uint64_t cap = n_chunks * chunk + 4096 + 64;
+    hipStream_t s = ctx->stream;
+    // the members that hold the text [lo - 1, lo + n_avail) (the byte in front of lo says whether lo starts a line)
+    const uint64_t need_lo = lo ? lo - 1 : 0, need_hi = lo + n_avail;
+    size_t j0 = 0, j1 = 0;
+    if (need_hi > need_lo) {
+        auto by_text = [](const BgzfMember& m, uint64_t t) { return m.text_off < t; };
+        j1 = std::lower_bound(f.jobs.begin(), f.jobs.end(), need_hi, by_text) - f.jobs.begin();
+        j0 = std::lower_bound(f.jobs.begin(), f.jobs.end(), need_lo + 1, by_text) - f.jobs.begin() - 1;
+    }
+    const uint64_t base = j1 > j0 ? f.jobs[j0].text_off : lo;
+    const uint64_t shift = lo - base;
+    const uint64_t extent = j1 > j0 ? f.jobs[j1 - 1].text_off + f.jobs[j1 - 1].isize - base : 0;
+    const uint64_t size = std::max(shift + cap, extent) + 64;
+    const double t0 = now_ms();
+    if (ctx->d_paf_text.ensure(size) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+    uint64_t comp_base = 0;
+    auto columns = [&]() { return tokeniser_memory(ctx, n, n_chunks, 0, T); };
+    if (!f.resident && j1 > j0) {
+        comp_base = f.jobs[j0].off;
+        const uint64_t c_len = f.jobs[j1 - 1].off + f.jobs[j1 - 1].bsize - comp_base;
+        if (ctx->d_bgzf_comp.ensure(c_len + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        const int shipped = ship_file(f.file.fd, comp_base, c_len, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, columns, &f.n_readers);
+        if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+        if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying the compressed file failed");
+        f.shipped += c_len;
+    } else if (!columns()) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+    }
+    const double t_ship = now_ms();
+    std::vector<BgzfJob> jobs(j1 - j0);
+    for (size_t j = j0; j < j1; ++j) {
+        const BgzfMember& m = f.jobs[j];
+        BgzfJob& J = jobs[j - j0];
+        J.comp_off = m.off + m.hdr - comp_base;
+        J.text_off = m.text_off - base;
+        J.deflate_len = m.bsize - m.hdr - 8;
+        J.isize = m.isize;
+    }
+    uint32_t flag = 0;
+    if (!jobs.empty()) {
+        INGEST_CHECK(ctx->d_bgzf_jobs.ensure(jobs.size() * sizeof(BgzfJob)));
+        INGEST_CHECK(ctx->d_bgzf_flag.ensure(1));
+        INGEST_CHECK(hipMemcpyAsync(ctx->d_bgzf_jobs.p, jobs.data(), jobs.size() * sizeof(BgzfJob), hipMemcpyHostToDevice, s));
+        INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+        launch_bgzf_inflate(ctx->d_bgzf_comp.p, (const BgzfJob*)ctx->d_bgzf_jobs.p, (uint32_t)jobs.size(), ctx->d_paf_text.p, size, ctx->d_bgzf_flag.p, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    uint8_t* const text = ctx->d_paf_text.p + shift;
+    // what lies behind the text reads as newlines (as for the plain file)
+    INGEST_CHECK(hipMemsetAsync(text + n_avail, '\n', cap - n_avail, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    f.inflate_ms += (float)(t1 - t_ship);
+    if (flag) {
+        ctx->d_paf_text.release();
+        out->flags = flag;
+        return RALA_HIP_OK;
+    }
+    bool first_is_start = lo == 0;
+    if (lo) {
+        uint8_t before = 0;
+        INGEST_CHECK(hipMemcpy(&before, text - 1, 1, hipMemcpyDeviceToHost));
+        first_is_start = before == '\n';
+    }
+    out->file_bytes = f.file_n;
+    return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, t1 - (t_ship - t0), t1, f.n_readers);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -282,9 +562,42 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         window = std::max<uint64_t>(256ull << 20, free_b / 4);
     }
     struct stat st_;
-    const uint64_t file_n = stat(path, &st_) == 0 && S_ISREG(st_.st_mode) ? (uint64_t)st_.st_size : 0;
+    uint64_t file_n = stat(path, &st_) == 0 && S_ISREG(st_.st_mode) ? (uint64_t)st_.st_size : 0;
+    // A gzip file: BGZF is inflated on the device (the windows then lie over its text), anything else is the host reader's -
+    // known from the first 18 bytes, before anything is shipped
+    ctx->inflate_tm = rala_hip_inflate_timings();
+    std::unique_ptr<BgzfFile> bg;
+    if (file_n >= 2) {
+        uint8_t head[18] = {0};
+        ssize_t got = -1;
+        {
+            Fd probe;
+            probe.fd = open(path, O_RDONLY);
+            if (probe.fd >= 0) got = pread(probe.fd, head, sizeof(head), 0);
+        }
+        if (got >= 2 && head[0] == 0x1f && head[1] == 0x8b) {
+            bool valid = bgzf_head(head, (uint64_t)got);
+            if (valid) {
+                if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
+                if (ctx->n_name_buckets == 0 && !mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
+                INGEST_CHECK(hipSetDevice(ctx->device));
+                bg.reset(new BgzfFile);
+                const int rc = bgzf_open(ctx, path, threads, window, *bg, &valid);
+                if (rc != RALA_HIP_OK) return rc;
+            }
+            if (!valid) {
+                *irregular = 8;
+                return RALA_HIP_OK;
+            }
+            file_n = bg->text_n;
+        }
+    }
+    auto tokenise_range = [&](uint64_t lo, uint64_t hi, const PafTarget& to, PafRange* part) {
+        return bg ? bgzf_tokenise_range(ctx, *bg, lo, hi, check_lengths != 0, threads, to, part)
+                  : paf_tokenise_range(ctx, path, lo, hi, check_lengths != 0, threads, 0, to, part);
+    };
     if (file_n <= window) {
-        const int rc = paf_tokenise_range(ctx, path, 0, ~0ull, check_lengths != 0, threads, 0, T, &R);
+        const int rc = tokenise_range(0, ~0ull, T, &R);
         if (rc != RALA_HIP_OK) return rc;
     } else {
         PafTarget W;
@@ -295,7 +608,7 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         float ship = 0, tok = 0;
         for (uint64_t lo = 0; lo < file_n; lo += window) {
             PafRange part;
-            const int rc = paf_tokenise_range(ctx, path, lo, lo + window, check_lengths != 0, threads, 0, W, &part);
+            const int rc = tokenise_range(lo, lo + window, W, &part);
             if (rc != RALA_HIP_OK) return rc;
             ship += ctx->ingest_tm.ship_ms; tok += ctx->ingest_tm.tokenize_ms;
             R.flags |= part.flags;
@@ -318,6 +631,17 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         R.n_lines = rows;
         ctx->ingest_tm.ship_ms = ship; ctx->ingest_tm.tokenize_ms = tok;
         ctx->ingest_tm.bytes = file_n; ctx->ingest_tm.lines = rows;
+    }
+    if (bg) {
+        ctx->d_bgzf_comp.release();
+        ctx->ingest_tm.ship_ms += bg->ship_ms;
+        ctx->inflate_tm.inflate_ms = bg->inflate_ms;
+        ctx->inflate_tm.compressed_bytes = bg->shipped;
+        ctx->inflate_tm.members = bg->jobs.size();
+        if (getenv("RALA_HIP_TRACE")) {
+            fprintf(stderr, "[trace] device inflate: %lu BGZF members, %.3f GB compressed shipped (index and ship %.1f ms), %.3f GB of text "
+                    "inflated in %.2f ms\n", (unsigned long)bg->jobs.size(), bg->shipped / 1e9, bg->ship_ms, bg->text_n / 1e9, bg->inflate_ms);
+        }
     }
     if (R.flags) {
         *irregular = (int)R.flags;
@@ -374,6 +698,28 @@ int rala_hip_get_overlap_columns(rala_hip_ctx* ctx, uint64_t* n, uint32_t* const
 int rala_hip_get_ingest_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out) {
     if (!ctx || !out) return RALA_HIP_EINVAL;
     *out = ctx->ingest_tm;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_inflate_timings(rala_hip_ctx* ctx, rala_hip_inflate_timings* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->inflate_tm;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, uint64_t cap, uint64_t* n_members, uint64_t* file_off,
+                        uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* text_off, int* valid) {
+    if ((!bytes && n) || !n_members || !valid) return RALA_HIP_EINVAL;
+    std::vector<BgzfMember> m;
+    *valid = bgzf_index_bytes(bytes, n, block_bytes ? block_bytes : kBlockBytes, m) ? 1 : 0;
+    *n_members = *valid ? m.size() : 0;
+    if (!*valid || cap < m.size()) return RALA_HIP_OK;
+    for (size_t i = 0; i < m.size(); ++i) {
+        if (file_off) file_off[i] = m[i].off;
+        if (comp_bytes) comp_bytes[i] = m[i].bsize;
+        if (text_bytes) text_bytes[i] = m[i].isize;
+        if (text_off) text_off[i] = m[i].text_off;
+    }
     return RALA_HIP_OK;
 }
 

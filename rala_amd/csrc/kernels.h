@@ -494,6 +494,18 @@ void launch_paf_parse(const uint8_t* text, uint64_t n, uint64_t n_avail, bool fi
                       uint64_t n_buckets, const char* arena, const uint32_t* read_len, uint32_t n_reads, bool check_lengths,
                       const PafColumns& out, uint32_t* flags, unsigned long long* first_bad, hipStream_t s, bool mhap = false);
 
+// ---- BGZF members -> text (inflate_kernels.hip) ---------------------------------------------
+// one gzip member of a BGZF file: its raw-deflate bytes at comp + comp_off (deflate_len of them, then CRC32 and ISIZE), its
+// text (isize bytes, 1 .. 65536) to text + text_off
+struct BgzfJob {
+    uint64_t comp_off, text_off;
+    uint32_t deflate_len, isize;
+};
+// every job inflated by one wavefront (RFC 1951) and checked against its CRC32 and ISIZE; what zlib's inflate refuses - and any
+// text that would lie beyond text_cap - sets flag 8 in *flags, and that member's text is not written
+void launch_bgzf_inflate(const uint8_t* comp, const BgzfJob* jobs, uint32_t n_jobs, uint8_t* text, uint64_t text_cap, uint32_t* flags,
+                         hipStream_t s);
+
 // ---- scans (scan_kernels.hip) --------------------------------------------------
 // exclusive prefix sum of n uint32 values; out may alias in; out[n] receives the total
 size_t scan_workspace_bytes(uint64_t n);

@@ -2,9 +2,10 @@
 // reduced graph (ingest -> rala_hip_initialize / _construct / _remove_transitive_edges), sequence
 // loading excluded like in the metric's definition.  Read names are "r<i>" (what rala_amd.synth
 // writes).  Ingest: an uncompressed file's text goes to the device and is tokenised there
-// (rala_hip_set_overlaps_from_paf; ms_parse = ship + tokenise, ms_upload = the name table); a
-// compressed file, a file the device tokeniser calls irregular, or device_ingest = 0: the host
-// readers (multi-threaded parse, then the columns' upload).
+// (rala_hip_set_overlaps_from_paf; ms_parse = ship + tokenise, ms_upload = the name table), a
+// BGZF file's members are inflated there first; a plain gzip file, a file the device tokeniser
+// calls irregular, or device_ingest = 0: the host readers (multi-threaded parse, then the columns'
+// upload).
 #include <stdint.h>
 #include <stdio.h>
 
@@ -39,7 +40,7 @@ extern "C" int rala_e2e_from_paf_with(const char* paf_path, const uint32_t* read
     uint64_t n_ovl = 0;
     bool on_device = false;
     clock::time_point t1, t2;
-    if (device_ingest && !rala::io::has_suffix(path, ".gz")) {
+    if (device_ingest) {
         int irregular = 0;
         rc = rala_hip_set_name_table(ctx, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
         t1 = clock::now();

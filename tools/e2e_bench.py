@@ -1,7 +1,9 @@
 """End-to-end overlaps/s from PAF text (second figure): multi-threaded
 ingest + upload + the whole device path.  python tools/e2e_bench.py [c2|c3] [threads]
 RALA_E2E_GZIP=1: the same from a gzip-compressed file (gzip -1; one thread inflates, the others parse);
-RALA_E2E_GZIP=bgzf: from a BGZF file (what bgzip writes: blocks inflated by several threads)."""
+RALA_E2E_GZIP=bgzf: from a BGZF file (what bgzip writes: members of at most 64 KB), two legs on the same file alternating
+three times each - the device leg (the compressed bytes shipped, the members inflated and the text tokenised on the GPU;
+ship / inflate / tokenise from the ingest's trace) and the host leg (device_ingest = 0: the host's BGZF reader)."""
 import ctypes
 import json
 import os
@@ -58,6 +60,58 @@ with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as d:
         os.remove(paf)
         paf += ".gz"
         print("[e2e] bgzf: %.2f GB in %.1f s" % (os.path.getsize(paf) / 1e9, time.time() - t0), file=sys.stderr)
+    if os.environ.get("RALA_E2E_GZIP") == "bgzf":
+        L.rala_e2e_from_paf_with.argtypes = ([ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int] +
+                                             [ctypes.c_void_p] * 6)
+        read_len = np.ascontiguousarray(ds.read_len, dtype=np.uint32)
+        trace_path = os.path.join(d, "trace.txt")
+
+        def leg(device):
+            ms = [ctypes.c_double() for _ in range(3)]
+            n_ovl, n_tr, used = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_int(-1)
+            # (the ingest's trace lines go to stderr: caught in a file for the ship / inflate / tokenise times)
+            os.environ["RALA_HIP_TRACE"] = "1"
+            sys.stderr.flush()
+            saved = os.dup(2)
+            with open(trace_path, "w") as tf:
+                os.dup2(tf.fileno(), 2)
+                try:
+                    rc = L.rala_e2e_from_paf_with(paf.encode(), read_len.ctypes.data, ds.n_reads, threads, device,
+                                                  *[ctypes.byref(x) for x in ms], ctypes.byref(n_ovl), ctypes.byref(n_tr), ctypes.byref(used))
+                finally:
+                    os.dup2(saved, 2)
+                    os.close(saved)
+                    os.environ.pop("RALA_HIP_TRACE", None)
+            trace = [x for x in open(trace_path).read().splitlines() if "device ingest" in x or "device inflate" in x]
+            assert rc == 0, rc
+            assert used.value == device, (device, used.value)
+            tot = sum(x.value for x in ms)
+            out = {"device_ingest": device, "ms_parse": ms[0].value, "ms_upload": ms[1].value, "ms_device_first_call": ms[2].value,
+                   "ms_total": tot, "overlaps_per_s": n_ovl.value / (tot * 1e-3), "n_overlaps": n_ovl.value, "transitive_pairs": n_tr.value}
+            if device:
+                ing = [x for x in trace if "device ingest" in x][-1]
+                inf = [x for x in trace if "device inflate" in x][-1]
+                out["ms_ship_compressed"] = float(ing.split(" shipped in ")[1].split(" ms")[0]) + float(inf.split("(index and ship ")[1].split(" ms")[0])
+                out["ms_tokenise"] = float(ing.split(" tokenised in ")[1].split(" ms")[0])
+                out["ms_inflate"] = float(inf.split(" inflated in ")[1].split(" ms")[0])
+                out["trace"] = trace
+            print("[e2e] %s leg: parse %.1f ms, upload %.1f ms, device %.1f ms, total %.1f ms = %.1f M overlaps/s" % (
+                "device" if device else "host", ms[0].value, ms[1].value, ms[2].value, tot, out["overlaps_per_s"] / 1e6), file=sys.stderr)
+            return out
+
+        runs = []
+        for rep in range(3):
+            runs.append((leg(1), leg(0)))
+        dev = min((r[0] for r in runs), key=lambda x: x["ms_total"])
+        host = min((r[1] for r in runs), key=lambda x: x["ms_total"])
+        assert all(r[0]["transitive_pairs"] == r[1]["transitive_pairs"] == dev["transitive_pairs"] for r in runs)
+        assert all(r[0]["n_overlaps"] == r[1]["n_overlaps"] for r in runs)
+        print(json.dumps({"workload": wl, "paf_bytes": size, "bgzf_bytes": os.path.getsize(paf), "threads": threads,
+                          "n_overlaps": dev["n_overlaps"], "transitive_pairs": dev["transitive_pairs"], "device": dev, "host": host,
+                          "alternations": [{"device_ms_total": a["ms_total"], "host_ms_total": b["ms_total"],
+                                            "host_over_device": b["ms_total"] / a["ms_total"]} for a, b in runs],
+                          "min_host_over_device": min(b["ms_total"] / a["ms_total"] for a, b in runs)}))
+        sys.exit(0)
     best = None
     # RALA_E2E_AB=VAR: alternate runs without and with the environment variable VAR=1 (reader variants), report both
     ab = os.environ.get("RALA_E2E_AB")
