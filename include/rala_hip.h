@@ -96,15 +96,17 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * "use_round_batches" (default 1: the containment fixed point of the second pass is finished on the device after two
  * rounds; 0 makes the host look at the killer list after every round), "use_partitioned_buckets" (default 1; 0 buckets the
  * target side through fixed slots), "debug_fp_lds_limit" (tests: containment fixed points with more killers than this
- * take the kernel for lists that do not fit the LDS), "use_fused_emit" (default 1; sharded runs: the senders scatter the
+ * take the kernel for lists that do not fit the LDS), "debug_fp_give_up" (tests: 1 or 2 - the workgroups of that kernel do not
+ * meet at their first barrier / at the later ones, and the last one to leave does the rounds alone), "use_fused_emit" (default 1; sharded runs: the senders scatter the
  * bounds once, by (owner, partition of the owner's reads), and the owners start at the second level of the partitioned
  * bucketing; 0: bounds grouped by owner only, bucketed by the owner from the start), "use_bound_records" (default 1; sharded
  * runs without the former: 0 ships two bound tuples per overlap side instead of one bound record),
- * "debug_part_shift" (tests / measurements, process-wide: the partitioned bucketing's first-level partitions hold 1 << value reads,
+ * "debug_part_shift" (tests / measurements: the partitioned bucketing's first-level partitions hold 1 << value reads,
  * 12 .. 14; 0 = by the rule - 4096 reads, more where that would make more than 256 partitions),
  * "pile_chunk_mb" (default 1024: the rows of all piles lie in physical chunks of this many MB mapped side by side into one range -
  * hipMemCreate / hipMemMap - which the first pile kernel's stores like better than where one hipMalloc puts them; 0 = one hipMalloc),
- * "debug_count_window" (tests, process-wide: the partitioned bucketing counts this many groups of 128 reads per pass over the ids;
+ * "debug_chunk_fail" (tests: the mapping of those chunks fails at chunk k, and the rows come from one hipMalloc; -1, the default: never),
+ * "debug_count_window" (tests: the partitioned bucketing counts this many groups of 128 reads per pass over the ids;
  * 0 = what a workgroup's LDS holds, 38 400 - one pass up to 4.9 M reads),
  * "debug_ev_events" (tests / measurements: 1 = the partitioned bucketing's row offsets count bound events where 4 n fits 32 bits, as
  * before round 6; 0, the default: bound pairs - up to 2^31 overlaps per context),

@@ -66,20 +66,18 @@ static_assert(kKeyBits + 2 * kCoordBits == 64, "a record is 8 bytes");
 struct PartGeom {
     uint32_t shift, gpp, n_part;                // reads per partition = 1 << shift; groups per partition; partitions
 };
-}  // namespace
-uint32_t g_part_shift = 0;                      // (option "debug_part_shift", tests and measurements: 12 .. 14; 0 = by the rule)
-uint32_t g_count_window = 0;                    // (option "debug_count_window", tests: groups per counting pass; 0 = what the LDS holds)
-namespace {
-inline PartGeom part_geom(uint32_t n_reads) {
+// (bt.part_shift - option "debug_part_shift", tests and measurements: 12 .. 14; 0 = by the rule)
+inline PartGeom part_geom(uint32_t n_reads, const BucketTuning& bt) {
     uint32_t shift = kL1Shift;
     while (shift < kKeyBits && ((uint64_t)n_reads + (1u << shift) - 1) >> shift > 256) ++shift;
-    if (g_part_shift >= kL1Shift && g_part_shift <= kKeyBits) shift = g_part_shift;
+    if (bt.part_shift >= kL1Shift && bt.part_shift <= kKeyBits) shift = bt.part_shift;
     return PartGeom{shift, 1u << (shift - kGroupShift), (uint32_t)(((uint64_t)n_reads + (1u << shift) - 1) >> shift)};
 }
 
 // groups of 128 reads whose counts one counting pass keeps in a workgroup's LDS (4 bytes each in 150 KB: 4.9 M reads)
 constexpr uint32_t kCountWindow = 150u * 1024u / 4u;
-inline uint32_t count_window() { return g_count_window ? g_count_window : kCountWindow; }
+// (bt.count_window - option "debug_count_window", tests: groups per counting pass; 0 = what the LDS holds)
+inline uint32_t count_window(const BucketTuning& bt) { return bt.count_window ? bt.count_window : kCountWindow; }
 
 __device__ __forceinline__ uint64_t pack_record(uint32_t b, uint32_t begin, uint32_t end) {
     // coordinates beyond 2^25 lie outside every read this path takes (partition_path_fits) and stay outside
@@ -752,15 +750,15 @@ __global__ __launch_bounds__(1024) void shard_owner_layout_kernel(const uint64_t
 
 }  // namespace
 
-uint32_t partition_count(uint32_t n_reads) { return part_geom(n_reads).n_part; }
-uint32_t partition_group_slots(uint32_t n_reads) { const PartGeom G = part_geom(n_reads); return G.n_part * G.gpp + 2; }
+uint32_t partition_count(uint32_t n_reads, const BucketTuning& bt) { return part_geom(n_reads, bt).n_part; }
+uint32_t partition_group_slots(uint32_t n_reads, const BucketTuning& bt) { const PartGeom G = part_geom(n_reads, bt); return G.n_part * G.gpp + 2; }
 size_t partition_records_needed(uint32_t, uint64_t n_overlaps) { return (size_t)n_overlaps + 64; }
-size_t partition_tile_slots(uint32_t n_reads, uint64_t n_overlaps) { return (size_t)(n_overlaps / kTile) + partition_count(n_reads) + 4; }
-bool partition_path_fits(uint32_t n_reads, uint32_t max_read_len, uint64_t n_overlaps) {
+size_t partition_tile_slots(uint32_t n_reads, uint64_t n_overlaps, const BucketTuning& bt) { return (size_t)(n_overlaps / kTile) + partition_count(n_reads, bt) + 4; }
+bool partition_path_fits(uint32_t n_reads, uint32_t max_read_len, uint64_t n_overlaps, const BucketTuning& bt) {
     // coordinates in 25 bits; the histogram of all groups in the LDS of one workgroup; level-1 histograms next to
     // the staging area; the bound PAIRS' positions (two per overlap) in 32 bits; enough overlaps per partition for whole-line copies
     if (n_reads == 0 || n_overlaps == 0) return false;
-    const PartGeom G = part_geom(n_reads);
+    const PartGeom G = part_geom(n_reads, bt);
     const uint64_t n_part = G.n_part;
     // (round 6: a histogram of all groups that outgrows the LDS is counted in windows - up to eight passes over the ids)
     return max_read_len < kCoordMax - 32u && n_part * G.gpp <= 8ull * kCountWindow &&
@@ -773,15 +771,16 @@ bool partition_path_fits(uint32_t n_reads, uint32_t max_read_len, uint64_t n_ove
 // what the caller has put in.  workgroups: compute units of the device (the counting kernel's persistent workgroups).
 namespace {
 struct PartitionBuffers {
-    uint32_t n_part, n_groups, group_slots, shift, gpp;
+    uint32_t n_part, n_groups, group_slots, shift, gpp, window;      // (window: groups per counting pass)
     size_t tile_slots;
     uint32_t *group_count, *group_base, *group_cursor, *tile_part, *tile_lo, *tile_hi, *n_tiles;
-    PartitionBuffers(uint32_t n_reads, uint64_t n_records, uint32_t* group, uint32_t* tiles) {
-        const PartGeom G = part_geom(n_reads);
+    PartitionBuffers(uint32_t n_reads, uint64_t n_records, const BucketTuning& bt, uint32_t* group, uint32_t* tiles) {
+        const PartGeom G = part_geom(n_reads, bt);
         n_part = G.n_part; shift = G.shift; gpp = G.gpp;
+        window = std::min(n_part * gpp, count_window(bt));
         n_groups = (n_reads + kGroupReads - 1) / kGroupReads;
-        group_slots = partition_group_slots(n_reads);
-        tile_slots = partition_tile_slots(n_reads, n_records);
+        group_slots = partition_group_slots(n_reads, bt);
+        tile_slots = partition_tile_slots(n_reads, n_records, bt);
         group_count = group; group_base = group + group_slots; group_cursor = group + 2 * (size_t)group_slots;
         tile_part = tiles; tile_lo = tiles + tile_slots; tile_hi = tiles + 2 * tile_slots; n_tiles = tiles + 3 * tile_slots;
     }
@@ -821,11 +820,11 @@ bool bucket_count_can_dedupe(const OvlSoA& o, const uint8_t* valid) {
 // dedupe (may be null): the counting pass does duplicate removal's first pass on the way (group_count_dedupe_kernel) -
 // suspect: n_reads bytes, cleared here; valid: the validity bytes; list_*: room for list_cap marks and a zeroed counter; the
 // caller runs launch_dedupe_fix behind this call's counting pass (the event `counted`, recorded here when given)
-hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, uint32_t* acount, uint32_t* written,
+hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, const BucketTuning& bt, uint32_t* acount, uint32_t* written,
                                      uint32_t* part_cursor, uint32_t* group, uint32_t* tiles, uint64_t* rec1, uint64_t* rec2,
                                      uint32_t* ev_off, uint32_t* ev, uint32_t workgroups, FillList& fills, hipStream_t s,
                                      const BucketDedupe* dedupe, uint32_t ev_shift) {
-    const PartitionBuffers B(n_reads, o.n, group, tiles);
+    const PartitionBuffers B(n_reads, o.n, bt, group, tiles);
     // (with whatever the caller wants cleared at this point)
     fills.add(acount, 0, (size_t)n_reads * 4);
     fills.add(written, 0, (size_t)n_reads * 4);
@@ -833,7 +832,7 @@ hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, uint32_t
     if (dedupe) fills.add(dedupe->suspect, 0, n_reads);
     hipError_t e = fills.launch(s);
     if (e != hipSuccess) return e;
-    const uint32_t all_groups = B.n_part * B.gpp, window = std::min(all_groups, count_window());
+    const uint32_t all_groups = B.n_part * B.gpp, window = B.window;
     const size_t lds_count = (size_t)window * 4;
     e = count_attribute(lds_count);
     if (e != hipSuccess) return e;
@@ -880,16 +879,16 @@ hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, uint32_t
 
 // An owner rank's bound records (both sides of every overlap that touches one of its reads) into the same CSR.  zero_counts:
 // n_reads + 2 zeroed words (cleared here, through `fills`): no query side apart from the records.
-hipError_t launch_bucket_partitioned_records(const uint64_t* records, uint64_t n, uint32_t n_reads, uint32_t* zero_counts,
+hipError_t launch_bucket_partitioned_records(const uint64_t* records, uint64_t n, uint32_t n_reads, const BucketTuning& bt, uint32_t* zero_counts,
                                              uint32_t* part_cursor, uint32_t* group, uint32_t* tiles, uint64_t* rec1, uint64_t* rec2,
                                              uint32_t* ev_off, uint32_t* ev, uint32_t workgroups, FillList& fills, hipStream_t s,
                                              uint32_t shrink, uint32_t ev_shift) {
-    const PartitionBuffers B(n_reads, n, group, tiles);
+    const PartitionBuffers B(n_reads, n, bt, group, tiles);
     fills.add(zero_counts, 0, (size_t)n_reads * 4);
     fills.add(B.group_count, 0, (size_t)B.group_slots * 4);
     hipError_t e = fills.launch(s);
     if (e != hipSuccess) return e;
-    const uint32_t all_groups = B.n_part * B.gpp, window = std::min(all_groups, count_window());
+    const uint32_t all_groups = B.n_part * B.gpp, window = B.window;
     const size_t lds_count = (size_t)window * 4;
     e = count_attribute(lds_count);
     if (e != hipSuccess) return e;
@@ -911,8 +910,8 @@ hipError_t launch_bucket_partitioned_records(const uint64_t* records, uint64_t n
 }
 
 // (n_records: an owner's records - two per overlap that stays on the rank)
-bool partition_path_fits_records(uint32_t n_reads, uint32_t max_read_len, uint64_t n_records) {
-    return max_read_len < (1u << kBoundRecordCoordBits) - 32u && partition_path_fits(n_reads, max_read_len, (n_records + 1) / 2);
+bool partition_path_fits_records(uint32_t n_reads, uint32_t max_read_len, uint64_t n_records, const BucketTuning& bt) {
+    return max_read_len < (1u << kBoundRecordCoordBits) - 32u && partition_path_fits(n_reads, max_read_len, (n_records + 1) / 2, bt);
 }
 
 // ---- sharded runs (kernels above) --------------------------------------------------------------------------------------

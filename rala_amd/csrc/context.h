@@ -66,7 +66,8 @@ struct DevBuf {
     }
     // chunk_bytes per physical allocation; order 1: chunk i lies at slot (i * stride) mod n_chunks of the range (neighbours in
     // the range are not neighbours in the order of allocation)
-    hipError_t ensure_chunked(size_t count, size_t chunk_bytes, int order, int device) {
+    // fail_at (tests, option debug_chunk_fail): the mapping fails at chunk fail_at (the caller falls back); negative: never
+    hipError_t ensure_chunked(size_t count, size_t chunk_bytes, int order, int device, int64_t fail_at = -1) {
         if (count <= n && p) return hipSuccess;
         release();
         hipMemAllocationProp prop = {};
@@ -94,9 +95,7 @@ struct DevBuf {
         }
         for (size_t i = 0; i < n_chunks && e == hipSuccess; ++i) {
             hipMemGenericAllocationHandle_t h;
-            if (const char* f = getenv("RALA_HIP_DEBUG_CHUNK_FAIL")) {          // tests: the mapping fails at chunk k (the caller falls back)
-                if ((size_t)atoll(f) == i) { e = hipErrorOutOfMemory; break; }
-            }
+            if (fail_at >= 0 && (size_t)fail_at == i) { e = hipErrorOutOfMemory; break; }
             e = hipMemCreate(&h, chunk_bytes, &prop, 0);
             if (e != hipSuccess) break;
             chunks.push_back(h);
@@ -204,6 +203,10 @@ struct rala_hip_ctx {
     uint32_t debug_pile_variant = 0;            // measurements: PileArgs::variant
     uint32_t debug_dedupe_list_cap = 0;         // tests: duplicate removal's mark list holds this many marks (0 = 2^20); more: the pass over all overlaps
     uint32_t debug_fp_lds_limit = 0xFFFFFFFFu;  // tests: containment fixed points with more killers than this take the long lists' kernel
+    uint32_t debug_fp_give_up = 0;              // tests: the long lists' workgroups do not meet (FixedPointList::debug_give_up: 1 or 2)
+    int64_t debug_chunk_fail = -1;              // tests: the mapping of the rows' chunks fails at this chunk (DevBuf::ensure_chunked)
+    uint32_t debug_part_shift = 0;              // tests / measurements: BucketTuning::part_shift
+    uint32_t debug_count_window = 0;            // tests: BucketTuning::count_window
     bool use_bound_records = true;              // sharded runs: 8-byte bound records instead of two tuples per overlap side where they fit
     bool use_round_batches = true;              // containment fixed point: several rounds per look at the counter
     rala_hip::DevBuf<uint32_t> d_round_log;     // list sizes after the rounds the host did not look at

@@ -298,7 +298,6 @@ hipError_t launch_fixed_point_finish(const FixedPointList& list_in, uint32_t* ba
                                      uint32_t* sync8, uint32_t* error, uint32_t* rounds_out, hipStream_t s) {
     FixedPointList list = list_in;
     list.lds_limit = std::min<uint32_t>(list_in.lds_limit, kLdsEntries);
-    if (const char* g = getenv("RALA_HIP_DEBUG_FP_GIVE_UP")) list.debug_give_up = atoi(g) == 2 ? 2u : 1u;     // tests: the long lists' workgroups do not meet
     constexpr size_t lds_bytes = 3 * (size_t)kLdsEntries * 4;
     // (once per DEVICE: the attribute belongs to the function on the current device, and the ranks of a sharded run are
     // threads of one process on different devices.  Every time, it was part of why the host fell behind the device in

@@ -351,7 +351,7 @@ void launch_refresh_types(const TailList& L, const TailReads& R, hipStream_t s);
 // six arrays of L.n words (killers, conditional killers); zeroed21: 21 zeroed words ([0] is set when a fixed point failed); work: four arrays of n_reads words, uninitialised; base2: 2 * n_reads words, all ones, and mark2: 2 * n_reads
 // bytes, zero (tail_init); map, pack: launch_fixed_point_finish's
 hipError_t launch_tail_contain(const TailList& L, const TailReads& R, uint8_t* alive, uint32_t* const lists[6], uint32_t* zeroed21, uint32_t* const work[4],
-                               uint32_t* base2, uint8_t* mark2, uint32_t* map, uint32_t* pack, uint32_t n_reads, uint32_t lds_limit, hipStream_t s);
+                               uint32_t* base2, uint8_t* mark2, uint32_t* map, uint32_t* pack, uint32_t n_reads, uint32_t lds_limit, uint32_t debug_give_up, hipStream_t s);
 void launch_count_zero_u8(const uint8_t* x, uint32_t n, uint32_t* out, hipStream_t s);    // *out += #zeros
 // list states (the first n0 items are overlaps, the rest internals), dirty[] = 0, n_pits0[] = n_pits[], base2[0 .. 2 n_reads) =
 // all ones, mark2[0 .. 2 n_reads) = 0, map[0 .. n_reads) = all ones, zero22[0 .. 21] = 0 in one launch
@@ -404,11 +404,17 @@ struct FillList {
 };
 
 // ---- partitioned bucketing (bucket_kernels.hip) ------------------------------------------------
+// What a context's options say about the geometry (0: by the rule).  A call fills one from its context and hands the same one
+// to the functions that size the buffers and to the launcher that fills them.
+struct BucketTuning {
+    uint32_t part_shift = 0;        // option "debug_part_shift": reads per first-level partition = 1 << shift, 12 .. 14
+    uint32_t count_window = 0;      // option "debug_count_window": groups of 128 reads per counting pass (0 = what the LDS holds)
+};
 size_t partition_records_needed(uint32_t n_reads, uint64_t n_overlaps);
-uint32_t partition_count(uint32_t n_reads);
-uint32_t partition_group_slots(uint32_t n_reads);
-size_t partition_tile_slots(uint32_t n_reads, uint64_t n_overlaps);
-bool partition_path_fits(uint32_t n_reads, uint32_t max_read_len, uint64_t n_overlaps);
+uint32_t partition_count(uint32_t n_reads, const BucketTuning& bt);
+uint32_t partition_group_slots(uint32_t n_reads, const BucketTuning& bt);
+size_t partition_tile_slots(uint32_t n_reads, uint64_t n_overlaps, const BucketTuning& bt);
+bool partition_path_fits(uint32_t n_reads, uint32_t max_read_len, uint64_t n_overlaps, const BucketTuning& bt);
 // bound events of all reads as an exact CSR (ev_off[n_reads + 1], ev); buffer sizes: bucket_kernels.hip
 // dedupe (may be null): the counting pass does duplicate removal's first pass on the way and writes the validity bytes that hold
 // for the unmarked queries; launch_dedupe_fix behind it (`counted` is recorded behind the counting pass) finishes the marked ones
@@ -425,14 +431,12 @@ struct BucketDedupe {
     // counting pass, for b_coords in front of the first scatter, for a_coords in front of the query side
     hipEvent_t ids = nullptr, b_coords = nullptr, a_coords = nullptr;
 };
-extern uint32_t g_count_window;      // (bucket_kernels.hip, option "debug_count_window": groups of 128 reads per counting pass; 0 = what the LDS holds)
-extern uint32_t g_part_shift;        // (bucket_kernels.hip, option "debug_part_shift": reads per first-level partition = 1 << shift, 12 .. 14; 0 = by the rule)
 bool bucket_count_can_dedupe(const OvlSoA& o, const uint8_t* valid);      // (the id columns on 16-byte boundaries)
 // Units of ev_off (round 6): the partitioned bucketing counts a read's bound PAIRS (an overlap puts one begin and one end on each of
 // its two reads), so 2 n < 2^32 bounds it - 2.1 G overlaps per context instead of the 1.07 G of offsets in events; the readers
 // shift (PileArgs::ev_shift).  The exact CSR and the tuples (single events) keep events.
 constexpr uint32_t kBucketPairShift = 1;
-hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, uint32_t* acount, uint32_t* written,
+hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, const BucketTuning& bt, uint32_t* acount, uint32_t* written,
                                      uint32_t* part_cursor, uint32_t* group, uint32_t* tiles, uint64_t* rec1, uint64_t* rec2,
                                      uint32_t* ev_off, uint32_t* ev, uint32_t workgroups, FillList& fills, hipStream_t s,
                                      const BucketDedupe* dedupe = nullptr, uint32_t ev_shift = kBucketPairShift);
@@ -440,9 +444,9 @@ hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, uint32_t
 // query (two launches; the one that is not needed leaves at once)
 void launch_dedupe_fix(const OvlSoA& o, uint32_t n_reads, const BucketDedupe& d, hipStream_t s);
 // the same from an owner rank's bound records (launch_bucket_tuples(.., records = true)): zero_counts = n_reads + 2 words
-bool partition_path_fits_records(uint32_t n_reads, uint32_t max_read_len, uint64_t n_records);
+bool partition_path_fits_records(uint32_t n_reads, uint32_t max_read_len, uint64_t n_records, const BucketTuning& bt);
 // (shrink: what the bounds are drawn in by - 15 for the primary overlaps, graph.cpp:317-324; 0 for the sensitive ones, :929-933)
-hipError_t launch_bucket_partitioned_records(const uint64_t* records, uint64_t n, uint32_t n_reads, uint32_t* zero_counts,
+hipError_t launch_bucket_partitioned_records(const uint64_t* records, uint64_t n, uint32_t n_reads, const BucketTuning& bt, uint32_t* zero_counts,
                                              uint32_t* part_cursor, uint32_t* group, uint32_t* tiles, uint64_t* rec1, uint64_t* rec2,
                                              uint32_t* ev_off, uint32_t* ev, uint32_t workgroups, FillList& fills, hipStream_t s,
                                              uint32_t shrink = 15u, uint32_t ev_shift = kBucketPairShift);

@@ -915,8 +915,9 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     // One context: the target bounds as ONE 8-byte record per overlap, bucketed by the partitioned path the owners' records
     // of a sharded run take (bucket_kernels.hip; no +-15 here) - where the set suits that path; two tuples per overlap through
     // count / scan / scatter otherwise (and in a sharded run, where the tuples travel first)
+    const BucketTuning bt = {cl->debug_part_shift, cl->debug_count_window};
     const bool sens_records = !sharded && cl->use_partitioned_buckets && n < (1u << kBoundRecordReadBits) - 1u &&
-                              partition_path_fits_records((uint32_t)nl, cl->max_read_len, 2 * n_sens);
+                              partition_path_fits_records((uint32_t)nl, cl->max_read_len, 2 * n_sens, bt);
     if (sens_records) {
         HIPCHECK(cs->d_sens_rec.ensure(n_sens + 8));
         launch_sens_records(so, (uint32_t)n, cs->d_begin.p, cs->d_alive.p, cs->d_sens_tb[0].p, cs->d_sens_tb[1].p, cs->d_sens_rec.p,
@@ -994,12 +995,12 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         // (the first pass' bucketing buffers have served: the bound events themselves stay where initialize left them)
         const uint32_t n_reads_l = (uint32_t)nl;
         HIPCHECK(cl->d_bk_u32[0].ensure(n_reads_l + 2));
-        HIPCHECK(cl->d_bk_part.ensure(partition_count(n_reads_l) + 2));
-        HIPCHECK(cl->d_bk_group.ensure(3 * (size_t)partition_group_slots(n_reads_l)));
-        HIPCHECK(cl->d_bk_tiles.ensure(3 * partition_tile_slots(n_reads_l, n_sens) + 2));
+        HIPCHECK(cl->d_bk_part.ensure(partition_count(n_reads_l, bt) + 2));
+        HIPCHECK(cl->d_bk_group.ensure(3 * (size_t)partition_group_slots(n_reads_l, bt)));
+        HIPCHECK(cl->d_bk_tiles.ensure(3 * partition_tile_slots(n_reads_l, n_sens, bt) + 2));
         for (int k = 0; k < 2; ++k) HIPCHECK(cl->d_bk_rec[k].ensure(partition_records_needed(n_reads_l, n_sens)));
         FillList fills;
-        HIPCHECK(launch_bucket_partitioned_records(cs->d_sens_rec.p, n_sens, n_reads_l, cl->d_bk_u32[0].p, cl->d_bk_part.p, cl->d_bk_group.p,
+        HIPCHECK(launch_bucket_partitioned_records(cs->d_sens_rec.p, n_sens, n_reads_l, bt, cl->d_bk_u32[0].p, cl->d_bk_part.p, cl->d_bk_group.p,
                                                    cl->d_bk_tiles.p, cl->d_bk_rec[0].p, cl->d_bk_rec[1].p, cl->d_sens_off.p, cl->d_sens_ev.p,
                                                    cl->n_compute_units, fills, sl, 0u, 0u));       // (the sensitive CSR: in events)
     } else {
@@ -1508,7 +1509,7 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
         uint32_t* const lists[6] = {ctx->d_kill[0].p, ctx->d_kill[1].p, ctx->d_kill[2].p, ctx->d_kill2[0].p, ctx->d_kill2[1].p,
                                     ctx->d_kill2[2].p};
         HIPCHECK(launch_tail_contain(L, R, ctx->d_alive.p, lists, ctx->d_counts.p + 9, work, ctx->d_t_fin.p, ctx->d_t_mark.p, ctx->d_fp_map.p,
-                                     ctx->d_fp_pack.p, n_reads, ctx->debug_fp_lds_limit, s));
+                                     ctx->d_fp_pack.p, n_reads, ctx->debug_fp_lds_limit, ctx->debug_fp_give_up, s));
     }
     mark("tail: containment scans", M);
     return RALA_HIP_OK;
@@ -1759,7 +1760,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
             HIPCHECK(ctx->d_death[0].ensure(n_reads));
             HIPCHECK(ctx->d_t_work[0].ensure(n_reads));
             uint32_t* const work[4] = {up, lo, ctx->d_death[0].p, ctx->d_t_work[0].p};
-            const FixedPointList rest = {klist[cur].ovl, klist[cur].target, klist[cur].keeper, klist[cur].count, ctx->debug_fp_lds_limit};
+            const FixedPointList rest = {klist[cur].ovl, klist[cur].target, klist[cur].keeper, klist[cur].count, ctx->debug_fp_lds_limit, ctx->debug_fp_give_up};
             HIPCHECK(launch_fixed_point_finish(rest, sure, ctx->d_fp_map.p, ctx->d_fp_pack.p, work, ctx->d_counts.p + 32,
                                                ctx->d_counts.p + 1, ctx->d_counts.p + 2, s));
             finished_on_device = true;
@@ -1941,6 +1942,22 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
     return RALA_HIP_OK;
 }
 
+// what the construct stage asks of the context, for both of its entry points (the host library and the tests match on the texts)
+int check_constructible(rala_hip_ctx* ctx) {
+    if (!ctx->initialized) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_initialize must succeed first");
+    if (ctx->tuple_mode || !ctx->inputs_set) return fail(ctx, RALA_HIP_EINVAL, "construct needs the overlaps (rala_hip_set_overlaps)");
+    if (ctx->constructed) return fail(ctx, RALA_HIP_EINVAL, "object already constructed");
+    return RALA_HIP_OK;
+}
+
+// pass 2's event times into ctx->tm (once the stream has passed ev[7])
+int pass2_times(rala_hip_ctx* ctx) {
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[4], ctx->ev[5]));
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[5], ctx->ev[6]));
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[6], ctx->ev[7]));
+    return RALA_HIP_OK;
+}
+
 }  // namespace
 
 // every row of cl where it lies, under the regions that apply (the getters' view: rala_hip_get_pile_data zeroes outside them)
@@ -1970,21 +1987,19 @@ int rala_hip::pile_row_digests(rala_hip_ctx* ctx, const uint32_t* begin, const u
 // ---- stage entry points shared with the sharded runner (stages.h) ---------------------------------
 int rala_hip::construct_stages(rala_hip_ctx* ctx, Comm* comm, bool sensitive_pass_follows) {
     if (!ctx) return RALA_HIP_EINVAL;
-    if (!ctx->initialized) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_initialize must succeed first");
-    if (ctx->tuple_mode || !ctx->inputs_set) return fail(ctx, RALA_HIP_EINVAL, "construct needs the overlaps (rala_hip_set_overlaps)");
-    if (ctx->constructed) return fail(ctx, RALA_HIP_EINVAL, "object already constructed");
+    int rc = check_constructible(ctx);
+    if (rc != RALA_HIP_OK) return rc;
     ctx->have_repeats = false;
     HIPCHECK(hipSetDevice(ctx->device));
-    int rc = pass2(ctx, comm);
+    rc = pass2(ctx, comm);
     if (rc != RALA_HIP_OK) return rc;
     ctx->tail_on_device = false;
     ctx->host_stale = false;
     const double t0 = now_ms();
     rc = sensitive_pass_follows ? gpu_tail_part_a(ctx) : gpu_tail_run(ctx);      // (repeats_stage builds the graph)
     if (rc != RALA_HIP_OK) return rc;
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[4], ctx->ev[5]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[5], ctx->ev[6]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[6], ctx->ev[7]));
+    rc = pass2_times(ctx);
+    if (rc != RALA_HIP_OK) return rc;
     ctx->tm.tail_host_ms = (float)(now_ms() - t0);
     ctx->constructed = true;
     return RALA_HIP_OK;
@@ -2010,7 +2025,11 @@ int rala_hip::transitive_stage(rala_hip_ctx* ctx, Comm* comm, uint32_t* n_pairs)
         ctx->marks_on_device = rc == RALA_HIP_OK;
         return rc;
     }
-    return rala_hip_remove_transitive_edges(ctx, n_pairs);      // (after the sensitive pass the graph is a host graph)
+    // (the tail ran on the host, or the sensitive pass rebuilt the graph there: a host graph)
+    const uint32_t ne = (uint32_t)ctx->e_src.size();
+    ctx->e_mark.assign(ne, 0);
+    return tr_mark_impl(ctx, (uint32_t)ctx->node_read.size(), ne, ctx->e_src.data(), ctx->e_dst.data(),
+                        ctx->e_len.data(), ctx->e_mark.data(), n_pairs);
 }
 
 // A sender of a sharded run: duplicate removal on the side stream (joined by the second pass), the bounds of the slice
@@ -2193,11 +2212,13 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "ingest_window_bytes")) { ctx->ingest_window_bytes = std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "pile_chunk_mb")) { ctx->pile_chunk_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_ev_events")) { ctx->debug_ev_events = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_count_window")) { g_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_part_shift")) { g_part_shift = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
+    if (!strcmp(key, "debug_count_window")) { ctx->debug_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
+    if (!strcmp(key, "debug_part_shift")) { ctx->debug_part_shift = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_pile_variant")) { ctx->debug_pile_variant = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_dedupe_list_cap")) { ctx->debug_dedupe_list_cap = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_fp_lds_limit")) { ctx->debug_fp_lds_limit = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
+    if (!strcmp(key, "debug_fp_give_up")) { ctx->debug_fp_give_up = value == 2 ? 2u : value != 0 ? 1u : 0u; return RALA_HIP_OK; }
+    if (!strcmp(key, "debug_chunk_fail")) { ctx->debug_chunk_fail = value; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_fail_construct")) { ctx->debug_fail_construct = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "use_gpu_tail")) { ctx->use_gpu_tail = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "use_fixed_buckets")) { ctx->use_fixed_buckets = value != 0; return RALA_HIP_OK; }
@@ -2401,7 +2422,8 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         static const char* chunk_order = getenv("RALA_HIP_PILE_CHUNK_ORDER");
         hipError_t ec = hipErrorNotSupported;
         if (ctx->pile_chunk_mb > 0 && (ctx->pile_elems + 8) * sizeof(uint16_t) >= ((size_t)ctx->pile_chunk_mb << 20)) {
-            ec = ctx->d_pile.ensure_chunked(ctx->pile_elems + 8, (size_t)ctx->pile_chunk_mb << 20, chunk_order ? atoi(chunk_order) : 0, ctx->device);
+            ec = ctx->d_pile.ensure_chunked(ctx->pile_elems + 8, (size_t)ctx->pile_chunk_mb << 20, chunk_order ? atoi(chunk_order) : 0, ctx->device,
+                                            ctx->debug_chunk_fail);
             if (ec != hipSuccess) (void)hipGetLastError();
         }
         if (ec != hipSuccess) HIPCHECK(ctx->d_pile.ensure(ctx->pile_elems + 8));
@@ -2467,10 +2489,11 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     // reads for a histogram of their groups of 128 to fit the LDS (4.9 M).
     // (round 6: whichever pile kernel follows - the position-space kernel reads the rows' offsets in pairs as well)
     const bool partition_allowed = ctx->use_fixed_buckets && ctx->use_partitioned_buckets;
+    const BucketTuning bt = {ctx->debug_part_shift, ctx->debug_count_window};       // (one look: what sizes the buffers fills them)
     // (an owner rank's bound records: the same path from level 1 on, both sides as records; input that does not suit it
     // is turned into tuples)
     const bool from_records = ctx->tuple_mode && ctx->records != nullptr && partition_allowed &&
-                              partition_path_fits_records(n_reads, ctx->max_read_len, ctx->n_records);
+                              partition_path_fits_records(n_reads, ctx->max_read_len, ctx->n_records, bt);
     if (ctx->tuple_mode && ctx->records != nullptr && !from_records) {
         HIPCHECK(ctx->d_tuple.ensure(2 * ctx->n_records + 8));
         launch_records_to_tuples(ctx->records, ctx->n_records, ctx->d_tuple.p, s);
@@ -2481,7 +2504,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     // form of that input)
     const bool from_blocks = ctx->tuple_mode && ctx->blocks_mode;
     const bool partitioned = from_blocks || from_records || (!ctx->tuple_mode && partition_allowed &&
-                                                             partition_path_fits(n_reads, ctx->max_read_len, ctx->n_ovl));
+                                                             partition_path_fits(n_reads, ctx->max_read_len, ctx->n_ovl, bt));
     if (!partitioned && !ctx->tuple_mode && ctx->n_ovl >= 0xFFFFFFF0ull / 4) {
         return fail(ctx, RALA_HIP_ETOOLARGE, "2^30 overlaps and more need the partitioned bucketing (its offsets count bound pairs); this input or these options rule it out");
     }
@@ -2515,12 +2538,12 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     } else if (partitioned) {
         const uint64_t n_rec = from_records ? ctx->n_records : ctx->n_ovl;
         for (int k = 0; k < 3; ++k) HIPCHECK(ctx->d_bk_u32[k].ensure(n_reads + 2));
-        HIPCHECK(ctx->d_bk_part.ensure(partition_count(n_reads) + 2));
-        HIPCHECK(ctx->d_bk_group.ensure(3 * (size_t)partition_group_slots(n_reads)));
-        HIPCHECK(ctx->d_bk_tiles.ensure(3 * partition_tile_slots(n_reads, n_rec) + 2));
+        HIPCHECK(ctx->d_bk_part.ensure(partition_count(n_reads, bt) + 2));
+        HIPCHECK(ctx->d_bk_group.ensure(3 * (size_t)partition_group_slots(n_reads, bt)));
+        HIPCHECK(ctx->d_bk_tiles.ensure(3 * partition_tile_slots(n_reads, n_rec, bt) + 2));
         for (int k = 0; k < 2; ++k) HIPCHECK(ctx->d_bk_rec[k].ensure(partition_records_needed(n_reads, n_rec)));
         if (from_records) {
-            HIPCHECK(launch_bucket_partitioned_records(ctx->records, ctx->n_records, n_reads, ctx->d_bk_u32[0].p, ctx->d_bk_part.p,
+            HIPCHECK(launch_bucket_partitioned_records(ctx->records, ctx->n_records, n_reads, bt, ctx->d_bk_u32[0].p, ctx->d_bk_part.p,
                                                        ctx->d_bk_group.p, ctx->d_bk_tiles.p, ctx->d_bk_rec[0].p, ctx->d_bk_rec[1].p,
                                                        ctx->d_ev_off.p, ctx->d_ev.p, ctx->n_compute_units, fills, s, 15u, ev_shift));
         } else {
@@ -2530,7 +2553,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
                                ctx->debug_dedupe_list_cap ? std::min(kMarks, ctx->debug_dedupe_list_cap) : kMarks,
                                ctx->d_small.p + 9, ctx->ev[8]};     // ([9]: zeroed with d_small above)
             if (fine_upload) { bd.ids = ctx->ev_up[0]; bd.b_coords = ctx->ev_up[1]; bd.a_coords = ctx->ev_up[2]; }
-            HIPCHECK(launch_bucket_partitioned(ctx->ovl, n_reads, ctx->d_bk_u32[0].p, ctx->d_bk_u32[2].p,
+            HIPCHECK(launch_bucket_partitioned(ctx->ovl, n_reads, bt, ctx->d_bk_u32[0].p, ctx->d_bk_u32[2].p,
                                                ctx->d_bk_part.p, ctx->d_bk_group.p, ctx->d_bk_tiles.p, ctx->d_bk_rec[0].p,
                                                ctx->d_bk_rec[1].p, ctx->d_ev_off.p, ctx->d_ev.p, ctx->n_compute_units, fills, s,
                                                dedupe_counted ? &bd : nullptr, ev_shift));
@@ -3034,50 +3057,34 @@ int rala_hip_import_state(rala_hip_ctx* ctx, const uint8_t* valid, const uint32_
 
 int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_t n_sens) {
     if (!ctx) return RALA_HIP_EINVAL;
-    if (!ctx->initialized) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_initialize must succeed first");
-    if (ctx->tuple_mode || !ctx->inputs_set) return fail(ctx, RALA_HIP_EINVAL, "construct needs the overlaps (rala_hip_set_overlaps)");
-    if (ctx->constructed) return fail(ctx, RALA_HIP_EINVAL, "object already constructed");
-    if (sens != nullptr && n_sens != 0 && !ctx->piles_resident) {
-        return fail(ctx, RALA_HIP_EINVAL, "the sensitive pass needs the piles on this context");
-    }
-    ctx->have_repeats = false;
+    // (the state first, as construct_stages asks again: which error a caller gets does not depend on its sensitive overlaps)
+    int rc = check_constructible(ctx);
+    if (rc != RALA_HIP_OK) return rc;
+    const bool with_sens = sens != nullptr && n_sens != 0;
+    if (with_sens && !ctx->piles_resident) return fail(ctx, RALA_HIP_EINVAL, "the sensitive pass needs the piles on this context");
     HIPCHECK(hipSetDevice(ctx->device));
-    { const int rcu = flush_upload(ctx); if (rcu != RALA_HIP_OK) return rcu; }
+    rc = flush_upload(ctx);
+    if (rc != RALA_HIP_OK) return rc;
+    if (ctx->use_gpu_tail) {
+        rc = construct_stages(ctx, nullptr, with_sens);
+        if (rc != RALA_HIP_OK || !with_sens) return rc;
+        // Graph::preprocess(sensitive overlaps) (graph.cpp:882-1054) works on the lists the chimera stage leaves on the
+        // device: repeats annotated, the graph built from what is left
+        rc = repeats_stage(ctx, ctx, nullptr, sens, n_sens);
+        if (rc != RALA_HIP_OK) ctx->constructed = false;
+        return rc;
+    }
+    // ---- the cross-check path (use_gpu_tail = 0): pass 2, then the tail on the host ----
+    ctx->have_repeats = false;
     hipStream_t s = ctx->stream;
     const uint32_t n_reads = (uint32_t)ctx->n_reads;
-    const uint64_t N = ctx->n_ovl;
-    const ReadState rs = read_state(ctx);
-
-    {
-        const int rc_p2 = pass2(ctx, nullptr);
-        if (rc_p2 != RALA_HIP_OK) return rc_p2;
-    }
+    rc = pass2(ctx, nullptr);
+    if (rc != RALA_HIP_OK) return rc;
     const uint32_t M = ctx->t_n0 + ctx->t_n1;
     const uint32_t n_surv[2] = {ctx->t_n0, ctx->t_n1};
-    const bool with_sens = sens != nullptr && n_sens != 0;
     ctx->tail_on_device = false;
     ctx->host_stale = false;
-    if (ctx->use_gpu_tail) {
-        const double t0 = now_ms();
-        const int rc5 = with_sens ? gpu_tail_part_a(ctx) : gpu_tail_run(ctx);
-        if (rc5 != RALA_HIP_OK) return rc5;
-        HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[4], ctx->ev[5]));
-        HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[5], ctx->ev[6]));
-        HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[6], ctx->ev[7]));
-        if (with_sens) {
-            // Graph::preprocess(sensitive overlaps) (graph.cpp:882-1054) works on the lists the
-            // chimera stage leaves: bring them to the host, annotate repeats (kernels + host
-            // orchestration), rebuild the graph from what is left
-            const double t1 = now_ms();
-            const int rc6 = repeats_after_tail(ctx, ctx, nullptr, sens, n_sens);
-            if (rc6 != RALA_HIP_OK) return rc6;
-            ctx->tm.repeats_ms = (float)(now_ms() - t1);
-        }
-        ctx->tm.tail_host_ms = (float)(now_ms() - t0);
-        ctx->constructed = true;
-        return RALA_HIP_OK;
-    }
-    // host tail: lists to the host
+    // lists to the host
     std::vector<HostOvl>* lists[2] = {&ctx->overlaps, &ctx->internals};
     for (int f = 0; f < 8; ++f) {
         HIPCHECK(ctx->p_surv_u32[f].ensure(M));
@@ -3111,20 +3118,18 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
         });
     }
     // refreshed read state: liveness after the scan, hill counters in the pool
-    int rc = download_read_state(ctx);
+    rc = download_read_state(ctx);
     if (rc != RALA_HIP_OK) return rc;
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[4], ctx->ev[5]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[5], ctx->ev[6]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[6], ctx->ev[7]));
+    rc = pass2_times(ctx);
+    if (rc != RALA_HIP_OK) return rc;
 
-    // ---- tail on the host (cross-check path; also used with sensitive overlaps) ----
     const double t0 = now_ms();
     Trace trc;
     {
         const int rc4 = preprocess_chimeras(ctx);
         if (rc4 != RALA_HIP_OK) return rc4;
     }
-    if (sens != nullptr && n_sens != 0) {
+    if (with_sens) {
         const double t1 = now_ms();
         const int rc3 = preprocess_repeats(ctx, ctx, nullptr, sens, n_sens, false);
         if (rc3 != RALA_HIP_OK) return rc3;
@@ -3219,17 +3224,7 @@ int rala_hip_find_repetitive_hills(rala_hip_ctx* ctx, uint64_t read, uint32_t be
 int rala_hip_remove_transitive_edges(rala_hip_ctx* ctx, uint32_t* n_pairs) {
     if (!ctx || !n_pairs) return RALA_HIP_EINVAL;
     if (!ctx->constructed) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_construct must succeed first");
-    HIPCHECK(hipSetDevice(ctx->device));
-    if (ctx->tail_on_device) {
-        const int rc = tr_mark_device(ctx, ctx->t_n_nodes, ctx->t_n_edges, ctx->d_e[0].p, ctx->d_e[1].p, ctx->d_e[2].p,
-                                      n_pairs);
-        ctx->marks_on_device = rc == RALA_HIP_OK;
-        return rc;
-    }
-    const uint32_t ne = (uint32_t)ctx->e_src.size();
-    ctx->e_mark.assign(ne, 0);
-    return tr_mark_impl(ctx, (uint32_t)ctx->node_read.size(), ne, ctx->e_src.data(), ctx->e_dst.data(),
-                        ctx->e_len.data(), ctx->e_mark.data(), n_pairs);
+    return transitive_stage(ctx, nullptr, n_pairs);
 }
 
 int rala_hip_tr_mark(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const uint32_t* src,

@@ -83,17 +83,14 @@ def test_first_level_partition_sizes(hip_ctx_factory, n, g, seed, shift):
     ds = Dataset(n, g, seed)
     st = parity.oracle_stages(ds)
     ctx = hip_ctx_factory()
-    ctx.set_option("debug_part_shift", shift)
-    try:
-        ctx.set_reads(ds.read_len)
-        ctx.set_overlaps(ds.overlaps)
-        ctx.initialize()
-        parity.check_initialize(ctx, st, ds)
-        ctx.construct()
-        parity.check_construct(ctx, st)
-        parity.check_tr(ctx, st)
-    finally:
-        ctx.set_option("debug_part_shift", 0)           # (a process-wide switch)
+    ctx.set_option("debug_part_shift", shift)           # (this context's own: nothing to put back)
+    ctx.set_reads(ds.read_len)
+    ctx.set_overlaps(ds.overlaps)
+    ctx.initialize()
+    parity.check_initialize(ctx, st, ds)
+    ctx.construct()
+    parity.check_construct(ctx, st)
+    parity.check_tr(ctx, st)
 
 
 @pytest.mark.parametrize("n,g,seed,window", [(40_000, 8_000_000, 13, 64), (9000, 1_800_000, 4, 7), (9000, 1_800_000, 4, 1)])
@@ -104,23 +101,20 @@ def test_counting_pass_in_windows(hip_ctx_factory, n, g, seed, window, sensitive
     1 groups on sets of 313 and 71 (option debug_count_window), duplicate removal's first pass riding on the first window only;
     the sensitive pass' records (group_count_records_kernel) the same way"""
     ds = Dataset(n, g, seed)
+    if sensitive:
+        if n <= 9000:       # (the option belongs to a context: to the one that runs the sensitive pass)
+            _check_sensitive(hip_ctx_factory, ds, 1, 1, expect_hills=True, options={"debug_count_window": window})
+        return
     ctx = hip_ctx_factory()
     ctx.set_option("debug_count_window", window)
-    try:
-        if sensitive:
-            if n <= 9000:
-                _check_sensitive(hip_ctx_factory, ds, 1, 1, expect_hills=True)
-            return
-        st = parity.oracle_stages(ds)
-        ctx.set_reads(ds.read_len)
-        ctx.set_overlaps(ds.overlaps)
-        ctx.initialize()
-        parity.check_initialize(ctx, st, ds)
-        ctx.construct()
-        parity.check_construct(ctx, st)
-        parity.check_tr(ctx, st)
-    finally:
-        ctx.set_option("debug_count_window", 0)         # (a process-wide switch)
+    st = parity.oracle_stages(ds)
+    ctx.set_reads(ds.read_len)
+    ctx.set_overlaps(ds.overlaps)
+    ctx.initialize()
+    parity.check_initialize(ctx, st, ds)
+    ctx.construct()
+    parity.check_construct(ctx, st)
+    parity.check_tr(ctx, st)
 
 
 @pytest.mark.parametrize("n,g,seed", [(9000, 1_800_000, 4), (600, 60_000, 9)])
@@ -144,18 +138,18 @@ def test_rows_in_mapped_chunks(hip_ctx_factory, n, g, seed, chunk_mb):
 
 
 @pytest.mark.parametrize("fail_at", [0, 3])
-def test_rows_chunks_that_cannot_be_mapped(hip_ctx_factory, monkeypatch, fail_at):
+def test_rows_chunks_that_cannot_be_mapped(hip_ctx_factory, fail_at):
     """the mapping of the rows' chunks fails (at the first chunk; half way): what was created is unmapped and released, the rows
     come from one hipMalloc and the result is the same; the device's free memory afterwards is what it was"""
     import torch
 
-    monkeypatch.setenv("RALA_HIP_DEBUG_CHUNK_FAIL", str(fail_at))
     ds = Dataset(9000, 1_800_000, 4)
     st = parity.oracle_stages(ds)
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info()[0]
     ctx = hip_ctx_factory()
     ctx.set_option("pile_chunk_mb", 16)
+    ctx.set_option("debug_chunk_fail", fail_at)
     ctx.set_reads(ds.read_len)
     ctx.set_overlaps(ds.overlaps)
     ctx.initialize()
@@ -188,18 +182,15 @@ def test_row_offsets_in_events(hip_ctx_factory, n, g, seed, opts):
 
 @pytest.mark.parametrize("n,g,seed", [(3000, 600_000, 21), (5000, 1_000_000, 7), (600, 60_000, 9), (40_000, 8_000_000, 13)])
 @pytest.mark.parametrize("opts", [{"debug_fp_lds_limit": 0}, {"debug_fp_lds_limit": 40}, {"use_round_batches": 0},
-                                  {"debug_fp_lds_limit": 0, "env": ("RALA_HIP_DEBUG_FP_GIVE_UP", "1")},
-                                  {"debug_fp_lds_limit": 0, "env": ("RALA_HIP_DEBUG_FP_GIVE_UP", "2")}])
-def test_containment_fixed_point_variants(hip_ctx_factory, monkeypatch, n, g, seed, opts):
+                                  {"debug_fp_lds_limit": 0, "debug_fp_give_up": 1},
+                                  {"debug_fp_lds_limit": 0, "debug_fp_give_up": 2}])
+def test_containment_fixed_point_variants(hip_ctx_factory, n, g, seed, opts):
     """The ends of the containment fixed points (second pass, the tail's two scans; fixed_point_kernels.hip): every list
     through the kernel for long lists (resident workgroups, a barrier per round; C5 takes it), a mix of both kernels,
     the host's loop of one look per round - and the long lists' kernel when its workgroups cannot meet (nothing
     guarantees that they are resident together): the last one to leave does the rounds alone.  "2": one
     workgroup stops waiting at every barrier behind the first, the last one included (passing and giving
     up are decided by one word - a barrier is passed by all or by none)."""
-    opts = dict(opts)
-    if "env" in opts:
-        monkeypatch.setenv(*opts.pop("env"))
     ds = Dataset(n, g, seed)
     st = parity.oracle_stages(ds)
     ctx = hip_ctx_factory()
@@ -310,7 +301,7 @@ def test_sensitive_overlaps_in_device_memory(hip_ctx_factory, gpu_tail):
     _check_sensitive(hip_ctx_factory, Dataset(5000, 1_000_000, 7), gpu_tail, 1, expect_hills=True, in_device=True)
 
 
-def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in_device=False, small_pools=False):
+def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in_device=False, small_pools=False, options=None):
     from oracle.oracle import Oracle
 
     n = ds.n_reads
@@ -335,6 +326,8 @@ def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in
     ctx.set_option("use_run_kernel", run_kernel)
     if small_pools:
         ctx.set_option("interval_pool_per_read_x1000", 0)
+    for k, v in (options or {}).items():
+        ctx.set_option(k, v)
     ctx.set_reads(ds.read_len)
     ctx.set_overlaps(ds.overlaps)
     ctx.initialize()
