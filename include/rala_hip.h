@@ -112,6 +112,9 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * before round 6; 0, the default: bound pairs - up to 2^31 overlaps per context),
  * "debug_dedupe_list_cap" (tests: the list of the runs duplicate removal's counting pass marks holds this many marks, 0 = the
  * default 2^20; a list that does not hold them all is given up and the pass over all overlaps does the work),
+ * "gzip_on_device" (default 0; 1: rala_hip_set_overlaps_from_paf / _mhap inflate a single-member gzip file on the device, see there),
+ * "gzip_chunk_bytes" (default 65536: the compressed bytes one wave of that inflater starts in; at least 1024),
+ * "debug_gzip_false_sync" (tests: every n-th of those chunks is given a bogus block start at its first bit; 0, the default: none),
  * "debug_pile_stop_after" (diagnostics: leave the run-space pile kernel after phase k, 99 = all;
  * 100 * m + k: the same without the row stores (m = 1), tools/phase_probe.py) */
 int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value);
@@ -143,7 +146,17 @@ int rala_hip_set_overlaps(rala_hip_ctx* ctx, const rala_hip_overlaps* ovl, uint6
  * kernels tokenise it (ship_ms then counts the compressed bytes; rala_hip_get_inflate_timings: the inflater).  The members
  * accepted are those the host reader's BgzfSource accepts (rala_amd/host/io.cpp); anything else - a plain single-member
  * gzip stream (known from its first 18 bytes, before anything is shipped), a cut file, a bad CRC32 or ISIZE, bytes behind
- * the last member that are no member - gives *irregular & 8 and sets nothing. */
+ * the last member that are no member - gives *irregular & 8 and sets nothing.
+ * With the option "gzip_on_device" set, any other gzip file of ONE member (what gzip, pigz, Python's gzip and `minimap2 | gzip`
+ * write; with bioparser's gzread loop the reference's only compressed input, src/graph.cpp:190-224, 328-352) is inflated on
+ * the device as well, by speculative decoding: the deflate bytes are cut into chunks of "gzip_chunk_bytes", every chunk finds
+ * the first bit in it that can start a block and is decoded from there without knowing the 32 KB in front of it, into 16-bit
+ * symbols (a byte, or "byte k of the window in front of this chunk"); the chain of chunks that ended at each other's starts
+ * from chunk 0 is the stream, the rest is dropped; windows and symbols are resolved in text order, and the result is
+ * proved: CRC32, ISIZE mod 2^32, the final block ending exactly at the 8 trailer bytes.  Anything else - a header RFC 1952
+ * does not allow, an invalid block, a cut stream, a second member or other bytes behind the trailer - gives *irregular & 8
+ * and sets nothing.  The compressed bytes, two bytes per byte of text and the text must fit in device memory together
+ * (RALA_HIP_ENOMEM otherwise; the caller takes the host reader).  rala_hip_get_gzip_timings: the passes. */
 typedef struct rala_hip_ingest_timings {
     float ship_ms;          /* file -> device memory (reads and copies overlapped) */
     float tokenize_ms;      /* count + scan + parse on the device */
@@ -167,6 +180,24 @@ typedef struct rala_hip_inflate_timings {
     uint64_t members;           /* gzip members with text */
 } rala_hip_inflate_timings;
 int rala_hip_get_inflate_timings(rala_hip_ctx* ctx, rala_hip_inflate_timings* out);
+/* The speculative inflater of the last rala_hip_set_overlaps_from_paf / _mhap call (zeros when it did not run). */
+typedef struct rala_hip_gzip_timings {
+    float find_ms;                  /* block starts searched in every chunk */
+    float decode_ms;                /* the counting pass and the writing pass */
+    float resolve_ms;               /* windows, symbols -> text, CRC32 */
+    uint64_t compressed_bytes;      /* the file's bytes shipped to the device */
+    uint64_t text_bytes;
+    uint64_t chunks;                /* chunks of gzip_chunk_bytes, the first one included */
+    uint64_t chunks_with_candidate; /* of the others: a candidate block start was found */
+    uint64_t chunks_confirmed;      /* of those: on the chain from chunk 0 (the stream was decoded by this many waves + 1) */
+    uint64_t chunks_refuted;        /* of those: passed by a wave of the chain that did not land on them */
+    uint64_t max_wave_text_bytes;   /* the most text one wave of the chain produced */
+} rala_hip_gzip_timings;
+int rala_hip_get_gzip_timings(rala_hip_ctx* ctx, rala_hip_gzip_timings* out);
+/* The header of a gzip member (RFC 1952) in the first n bytes of a file (no context, no device), as the device ingest reads
+ * it: ID1 ID2, CM = 8, FLG with FEXTRA / FNAME / FCOMMENT / FHCRC and its reserved bits clear.  *valid = 1: the deflate
+ * bytes begin at *deflate_off; 0: not such a header, or it does not end within the n bytes. */
+int rala_hip_gzip_head(const uint8_t* bytes, uint64_t n, uint64_t* deflate_off, int* valid);
 /* The member index of a BGZF file held in memory (no context, no device): the chain of gzip members from byte 0, as the
  * device ingest builds it - the bytes scanned for member headers in blocks of block_bytes (0: the ingest's 32 MB), then
  * walked from offset 0.  *valid = 0: not a BGZF file the host reader would take (first 18 bytes not a BGZF header, a cut

@@ -247,6 +247,16 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint8_t> d_bgzf_comp, d_bgzf_jobs;
     rala_hip::DevBuf<uint32_t> d_bgzf_flag;
     rala_hip_inflate_timings inflate_tm = {};
+    // single-member gzip files (option gzip_on_device; ingest.hip: gzip_inflate): the chunks' starts and spans, the true
+    // chunks' jobs and text offsets, the 16-bit symbols, the segments' CRCs, the resident text
+    bool gzip_on_device = false;
+    int64_t gzip_chunk_bytes = 64 << 10;        // option: compressed bytes per chunk
+    uint32_t debug_gzip_false_sync = 0;         // tests: every n-th chunk is given a bogus start at its first bit
+    rala_hip::DevBuf<uint64_t> d_gzip_starts, d_gzip_off;
+    rala_hip::DevBuf<uint8_t> d_gzip_spans, d_gzip_jobs, d_gzip_text;
+    rala_hip::DevBuf<uint16_t> d_gzip_sym;
+    rala_hip::DevBuf<uint32_t> d_gzip_crc;
+    rala_hip_gzip_timings gzip_tm = {};
 
     // overlaps
     uint64_t n_ovl = 0;

@@ -21,7 +21,11 @@
 // as inflate_table takes them (over-subscribed: never; incomplete: only a single code of one bit for literals/lengths and
 // distances), no distance in front of the member's start, length symbols 286/287 and distance symbols 30/31 invalid, stored
 // blocks with LEN = ~NLEN, and the CRC.  Anything else sets flag 8 and writes nothing of that member.
+//
+// Below the BGZF kernel: a single-member gzip stream by speculative decoding over chunks of the compressed bytes (its own header comment).
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "kernels.h"
 
@@ -399,11 +403,583 @@ __global__ __launch_bounds__(kWave) void bgzf_inflate_kernel(const uint8_t* __re
     for (uint32_t i = head + 4 * n_words + lane; i < isize; i += kWave) dst[i] = out[i];
 }
 
+
+// ====================================================================================================================
+// A single-member gzip stream (what gzip, pigz, Python's gzip and `minimap2 | gzip` write) -> text, by speculative decoding
+// over independent chunks of the compressed bytes (the method of pugz / rapidgzip on CPUs):
+//   find     every chunk but the first looks for the first bit offset in it that can start a deflate block;
+//   count    every chunk with a start is decoded from there without its output - text sizes do not depend on what the 32 KB
+//            in front of a chunk hold - until it lands on a later chunk's start (or the final block ends); a start that is
+//            passed without being landed on is refuted.  The host follows "ended at the start of chunk j" from chunk 0:
+//            the true chunks, their text offsets, the text's size - exact, so no buffer of a guessed capacity exists
+//            that could overflow (the price: the true chunks are decoded twice; the first time without ring, stores or copies);
+//   write    the true chunks again, into 16-bit symbols at their text offsets: a value below 256 is a byte, 0x8000 | k is
+//            "byte k of the 32 768 in front of this chunk's start" - the ring in LDS starts as those markers, so a match that
+//            reaches in front of the chunk copies markers, and no symbol ever points at another symbol;
+//   windows  in text order, the 32 768 symbols in front of every true chunk are turned into bytes in place (a marker of
+//            chunk j points into the window in front of chunk j, which is bytes already);
+//   resolve  one streaming pass: every symbol to its byte in the text buffer, the CRC32 of every 16 KB of it on the way.
+// Whatever this cannot prove - CRC32, ISIZE, the final block ending exactly at the trailer - is flag 8 for the caller.
+constexpr uint64_t kNoStart = ~0ull;
+constexpr uint32_t kRing = 32768;           // deflate's window: the symbols a match can reach
+constexpr uint32_t kProbe = 64;             // symbols a candidate block must decode to (fewer where its end-of-block comes first)
+constexpr uint32_t kFlushAt = 8192;         // unflushed symbols in the ring at which they go to global memory
+constexpr uint32_t kSeg = 16384;            // bytes of text per workgroup of the resolve pass
+constexpr uint32_t kSegThreads = 256;
+constexpr uint32_t kSegSlice = 68;          // bytes of a thread's CRC slice (17 dwords: the threads' reads fall on different banks)
+
+// the file's bytes as the wave sees them: Input with 64-bit offsets from the (aligned) buffer's start; bytes from `end` on read as zero
+struct Stream {
+    const uint8_t* base;
+    uint64_t end;
+    uint64_t wb;
+    uint32_t cur, nxt;
+
+    __device__ __forceinline__ uint32_t load(uint64_t off) const {
+        if (off >= end) return 0u;
+        uint32_t v = *(const uint32_t*)(base + off);
+        if (off + 4 > end) v &= 0xFFFFFFFFu >> (8u * (uint32_t)(off + 4 - end));
+        return v;
+    }
+    __device__ __forceinline__ void seek(uint64_t ip) {
+        wb = ip & ~3ull;
+        cur = load(wb + 4 * lane_id());
+        nxt = load(wb + 256 + 4 * lane_id());
+    }
+    __device__ __forceinline__ uint32_t fetch32(uint64_t ip) {
+        uint32_t w = (uint32_t)((ip - wb) >> 2);
+        if (w >= 64) {
+            cur = nxt;
+            wb += 256;
+            w -= 64;
+            nxt = load(wb + 256 + 4 * lane_id());
+        }
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)w);
+        const uint32_t hi = w + 1 < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(w + 1)) : (uint32_t)__builtin_amdgcn_readlane((int)nxt, 0);
+        const uint32_t sh = ((uint32_t)ip & 3u) * 8u;
+        return sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+    }
+};
+
+// the wave's bit buffer over a Stream (wave-uniform): nb bits in bb, the stream's next bit in bit 0; ip = the next byte into it
+struct Bits {
+    Stream in;
+    uint64_t bb;
+    uint64_t ip;
+    uint32_t nb;
+
+    __device__ __forceinline__ void refill() {
+        if (nb <= 32) {
+            bb |= (uint64_t)in.fetch32(ip) << nb;
+            nb += 32;
+            ip += 4;
+        }
+    }
+    __device__ __forceinline__ uint32_t take(uint32_t k) {          // k <= 16 after a refill
+        const uint32_t v = (uint32_t)bb & ((1u << k) - 1u);
+        bb >>= k;
+        nb -= k;
+        return v;
+    }
+    __device__ __forceinline__ uint64_t consumed() const { return 8ull * ip - nb; }       // bits from the buffer's start
+    __device__ __forceinline__ void restart(uint64_t byte) {
+        ip = byte;
+        bb = 0;
+        nb = 0;
+        in.seek(byte);
+    }
+    __device__ __forceinline__ void start(const uint8_t* base, uint64_t end, uint64_t bit) {
+        in.base = base;
+        in.end = end;
+        restart(bit >> 3);
+        refill();
+        take((uint32_t)bit & 7u);
+    }
+};
+
+// the header of a dynamic block behind BFINAL and BTYPE (RFC 1951 3.2.7) into T's tables, as bgzf_inflate_kernel reads it;
+// false: zlib's inflate refuses it
+__device__ __forceinline__ bool read_dynamic(Bits& r, Lds& T, uint64_t limit) {
+    const uint32_t lane = lane_id();
+    r.refill();
+    const uint32_t nlen = r.take(5) + 257, ndist = r.take(5) + 1, ncode = r.take(4) + 4;
+    if (nlen > 286 || ndist > 30) return false;
+    __syncthreads();
+    if (lane < 19) T.lens_cl[lane] = 0;
+    __syncthreads();
+    for (uint32_t k = 0; k < ncode; ++k) {
+        r.refill();
+        const uint32_t v = r.take(3);
+        if (lane == 0) T.lens_cl[kClOrder[k]] = (uint8_t)v;
+    }
+    __syncthreads();
+    if (!build_table(T.lens_cl, 19, true, T.cnt_d, T.sym_cl, T.lut_cl, kClBits)) return false;
+    uint32_t have = 0, prev = 0;
+    while (have < nlen + ndist) {
+        r.refill();
+        const uint32_t e = uni(T.lut_cl[(uint32_t)r.bb & ((1u << kClBits) - 1u)]);
+        if (e == 0) return false;
+        r.take(e >> 9);
+        const uint32_t s = e & 511u;
+        if (s < 16) {
+            if (lane == 0) T.lens[have] = (uint8_t)s;
+            prev = s;
+            ++have;
+            continue;
+        }
+        uint32_t len = 0, copy;
+        if (s == 16) {
+            if (have == 0) return false;
+            len = prev;
+            copy = 3 + r.take(2);
+        } else if (s == 17) {
+            copy = 3 + r.take(3);
+        } else {
+            copy = 11 + r.take(7);
+        }
+        if (have + copy > nlen + ndist) return false;
+        for (uint32_t j = lane; j < copy; j += kWave) T.lens[have + j] = (uint8_t)len;
+        prev = len;
+        have += copy;
+        if (r.consumed() > limit) return false;
+    }
+    if (r.consumed() > limit) return false;
+    __syncthreads();
+    if (T.lens[256] == 0) return false;                     // (no end-of-block code)
+    if (!build_table(T.lens, nlen, false, T.cnt_ll, T.sym_ll, T.lut_ll, kLitBits)) return false;
+    const uint32_t dl = lane < ndist ? T.lens[nlen + lane] : 0u;
+    __syncthreads();
+    if (lane < 32) T.lens[288 + lane] = (uint8_t)dl;
+    __syncthreads();
+    return build_table(T.lens + 288, ndist, false, T.cnt_d, T.sym_d, T.lut_d, kDistBits);
+}
+
+__device__ __forceinline__ void build_fixed(Lds& T) {
+    __syncthreads();
+    for (uint32_t s = lane_id(); s < 320; s += kWave) T.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
+    __syncthreads();
+    build_table(T.lens, 288, false, T.cnt_ll, T.sym_ll, T.lut_ll, kLitBits);
+    build_table(T.lens + 288, 32, false, T.cnt_d, T.sym_d, T.lut_d, kDistBits);
+}
+
+// 64 bits of the stream from bit `bit` on (words = the buffer's 8-byte words; behind them zero)
+__device__ __forceinline__ uint64_t peek64(const uint64_t* words, uint64_t n_words, uint64_t bit) {
+    const uint64_t i = bit >> 6;
+    const uint32_t sh = (uint32_t)bit & 63u;
+    const uint64_t a = i < n_words ? words[i] : 0ull, b = i + 1 < n_words ? words[i + 1] : 0ull;
+    return sh ? (a >> sh) | (b << (64u - sh)) : a;
+}
+
+// does a deflate block that can be a chunk's start begin at `bit`?  A non-final dynamic block (wave-uniform; the lanes have
+// looked at the first 74 bits already, this reads them again) whose tables zlib takes and whose first kProbe symbols are
+// valid codes, the literals among them text
+__device__ __forceinline__ bool probe_block(Lds& T, const uint8_t* comp, uint64_t end, uint64_t bit) {
+    const uint64_t limit = 8ull * end;
+    Bits r;
+    r.start(comp, end, bit);
+    r.refill();
+    if (r.take(3) != 4u) return false;
+    if (!read_dynamic(r, T, limit)) return false;
+    for (uint32_t n = 0; n < kProbe; ++n) {
+        r.refill();
+        uint32_t e = uni(T.lut_ll[(uint32_t)r.bb & ((1u << kLitBits) - 1u)]);
+        if (e == 0) e = uni(decode_canonical(T.cnt_ll, T.sym_ll, (uint32_t)r.bb, 15));
+        if (e == 0) return false;
+        r.take(e >> 9);
+        const uint32_t s = e & 511u;
+        if (s < 256) {
+            if (!(s == '\t' || s == '\n' || (s >= 0x20 && s <= 0x7e))) return false;
+        } else if (s == 256) {
+            break;
+        } else if (s <= 285) {
+            const uint32_t k = s - 257;
+            r.take(kLenExtra[k]);
+            r.refill();
+            uint32_t d = uni(T.lut_d[(uint32_t)r.bb & ((1u << kDistBits) - 1u)]);
+            if (d == 0) d = uni(decode_canonical(T.cnt_d, T.sym_d, (uint32_t)r.bb, 15));
+            if (d == 0 || (d & 511u) >= 30) return false;           // (a valid distance code is a distance within 32 768)
+            r.take(d >> 9);
+            r.take(kDistExtra[d & 511u]);
+        } else {
+            return false;
+        }
+        if (r.consumed() > limit) return false;
+    }
+    return r.consumed() <= limit;
+}
+
+// starts[c] = the bit (from the buffer's start) where chunk c's first candidate block begins, kNoStart: none.  Chunk c covers
+// the bytes [deflate_off + c * chunk_bytes, .. + chunk_bytes) below `end` (the trailer's first byte); chunk 0 starts at
+// deflate_off by definition.  The lanes test 64 bit offsets at a time on the first 17 + 3 * HCLEN bits (BFINAL 0, BTYPE 2,
+// HLIT and HDIST in range, the code-length code complete); what passes is probed by the whole wave, lowest offset first.
+// false_sync n (tests): every n-th chunk starts at its first bit instead.
+__global__ __launch_bounds__(kWave) void gzip_find_kernel(const uint8_t* __restrict__ comp, uint64_t end, uint64_t n_words, uint64_t deflate_off,
+                                                           uint64_t chunk_bytes, uint32_t false_sync, uint64_t* __restrict__ starts) {
+    __shared__ Lds T;
+    const uint32_t c = blockIdx.x, lane = lane_id();
+    if (c == 0) {
+        if (lane == 0) starts[0] = 8ull * deflate_off;
+        return;
+    }
+    const uint64_t b0 = 8ull * (deflate_off + (uint64_t)c * chunk_bytes);
+    const uint64_t b1 = min(b0 + 8ull * chunk_bytes, 8ull * end);
+    if (false_sync && c % false_sync == 0) {
+        if (lane == 0) starts[c] = b0;
+        return;
+    }
+    const uint64_t* words = (const uint64_t*)comp;
+    uint64_t found = kNoStart;
+    for (uint64_t base = b0; base < b1 && found == kNoStart; base += kWave) {
+        const uint64_t b = base + lane;
+        const uint64_t v = peek64(words, n_words, b);
+        bool ok = b < b1 && (v & 7u) == 4u && ((v >> 3) & 31u) <= 29u && ((v >> 8) & 31u) <= 29u;
+        if (ok) {
+            const uint64_t w = peek64(words, n_words, b + 62);
+            const uint32_t ncode = (uint32_t)((v >> 13) & 15u) + 4;
+            uint32_t kraft = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 19; ++k) {
+                const uint32_t l = (uint32_t)((k < 15 ? v >> (17 + 3 * k) : w >> (3 * (k - 15))) & 7u);
+                if (k < ncode && l) kraft += 128u >> l;
+            }
+            ok = kraft == 128u;
+        }
+        uint64_t mask = __ballot(ok);
+        while (mask) {
+            const uint32_t first = (uint32_t)__ffsll((unsigned long long)mask) - 1u;
+            mask &= mask - 1;
+            if (probe_block(T, comp, end, base + first)) {
+                found = base + first;
+                break;
+            }
+        }
+    }
+    if (lane == 0) starts[c] = found;
+}
+
+// One span of the stream decoded by the wave from start_bit (the control flow of bgzf_inflate_kernel).  first: the stream's
+// first chunk - nothing lies in front of it, a distance beyond its text is invalid.
+// kWrite false: the text is counted only; the span ends at the first block boundary that is a later chunk's start (starts[],
+//   chunks chunk + 1 ..; those passed are counted as refuted) or with the final block.
+// kWrite true: the span ends at stop_bit (kNoStart: with the final block) and must give text_n symbols, which go through
+//   the ring to sym[0 .. text_n).
+template <bool kWrite>
+__device__ __forceinline__ GzipSpan inflate_span(Lds& T, uint16_t* ring, const uint8_t* comp, uint64_t end, uint64_t start_bit, bool first,
+                                                 const uint64_t* starts, uint32_t n_chunks, uint32_t chunk, uint64_t stop_bit,
+                                                 uint64_t text_n, uint16_t* sym) {
+    constexpr uint32_t M = kRing - 1;
+    const uint32_t lane = lane_id();
+    const uint64_t limit = 8ull * end;
+    Bits r;
+    r.start(comp, end, start_bit);
+    uint64_t pos = 0, flushed = 0;
+    uint32_t next = chunk + 1, refuted = 0, status = 2;
+    bool bad = false, last = false;
+    const uint32_t a0 = kWrite ? (uint32_t)(((uintptr_t)sym >> 1) & 7u) : 0u;       // sym + p is 16-byte aligned where (a0 + p) % 8 == 0
+    // symbols [flushed, upto) from the ring to global memory: single ones up to a 16-byte boundary, then 8 at a time
+    auto flush = [&](uint64_t upto) {
+        const uint32_t head = (uint32_t)min((uint64_t)((8u - ((a0 + (uint32_t)flushed) & 7u)) & 7u), upto - flushed);
+        if (lane < head) sym[flushed + lane] = ring[(uint32_t)(flushed + lane) & M];
+        flushed += head;
+        const uint64_t n_vec = (upto - flushed) >> 3;
+        for (uint64_t v = lane; v < n_vec; v += kWave) {
+            const uint32_t q = (uint32_t)(flushed + 8 * v);
+            uint32_t w[4];
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e) w[e] = (uint32_t)ring[(q + 2 * e) & M] | (uint32_t)ring[(q + 2 * e + 1) & M] << 16;
+            *(uint4*)(sym + flushed + 8 * v) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        flushed += 8 * n_vec;
+        const uint32_t tail = (uint32_t)(upto - flushed);
+        if (lane < tail) sym[flushed + lane] = ring[(uint32_t)(flushed + lane) & M];
+        flushed = upto;
+    };
+    if (kWrite) {
+        for (uint32_t e = lane; e < kRing; e += kWave) ring[e] = (uint16_t)(0x8000u | e);
+    }
+    __syncthreads();
+    for (bool begun = false; !bad; begun = true) {
+        if (begun) {                                                // a block boundary
+            if (last) { status = 1; break; }
+            const uint64_t p = r.consumed();
+            if (kWrite) {
+                if (p == stop_bit) { status = 0; break; }
+            } else {
+                while (next < n_chunks) {
+                    const uint64_t s = starts[next];
+                    if (s != kNoStart && s >= p) break;
+                    refuted += s != kNoStart;
+                    ++next;
+                }
+                if (next < n_chunks && starts[next] == p) { status = 0; break; }
+            }
+        }
+        r.refill();
+        last = r.take(1) != 0;
+        const uint32_t type = r.take(2);
+        if (type == 0) {                                            // stored
+            const uint64_t p = (r.consumed() + 7) >> 3;             // (the rest of the byte is dropped)
+            if (p + 4 > end) { bad = true; break; }
+            r.in.seek(p);
+            const uint32_t ln = r.in.fetch32(p);
+            const uint32_t len = ln & 0xFFFFu;
+            if ((ln >> 16) != (~len & 0xFFFFu) || p + 4 + len > end) { bad = true; break; }
+            if (kWrite) {
+                if (pos + len > text_n) { bad = true; break; }
+                for (uint32_t done = 0; done < len;) {
+                    const uint32_t piece = min(len - done, 4096u);
+                    for (uint32_t j = lane; j < piece; j += kWave) ring[(uint32_t)(pos + j) & M] = comp[p + 4 + done + j];
+                    pos += piece;
+                    done += piece;
+                    if (pos - flushed >= kFlushAt) flush(pos - ((a0 + (uint32_t)pos) & 7u));
+                }
+            } else {
+                pos += len;
+            }
+            r.restart(p + 4 + len);
+            continue;
+        }
+        if (type == 3) { bad = true; break; }
+        if (type == 1) {
+            build_fixed(T);
+        } else if (!read_dynamic(r, T, limit)) {
+            bad = true;
+            break;
+        }
+        for (;;) {                                                  // the block's symbols
+            r.refill();
+            uint32_t e = uni(T.lut_ll[(uint32_t)r.bb & ((1u << kLitBits) - 1u)]);
+            if (e == 0) e = uni(decode_canonical(T.cnt_ll, T.sym_ll, (uint32_t)r.bb, 15));
+            if (e == 0) { bad = true; break; }
+            r.take(e >> 9);
+            const uint32_t s = e & 511u;
+            if (s < 256) {
+                if (kWrite) {
+                    if (pos >= text_n) { bad = true; break; }
+                    if (lane == 0) ring[(uint32_t)pos & M] = (uint16_t)s;
+                }
+                ++pos;
+            } else if (s == 256) {
+                break;
+            } else if (s <= 285) {
+                const uint32_t k = s - 257;
+                const uint32_t length = kLenBase[k] + r.take(kLenExtra[k]);
+                r.refill();
+                uint32_t d = uni(T.lut_d[(uint32_t)r.bb & ((1u << kDistBits) - 1u)]);
+                if (d == 0) d = uni(decode_canonical(T.cnt_d, T.sym_d, (uint32_t)r.bb, 15));
+                if (d == 0 || (d & 511u) >= 30) { bad = true; break; }
+                r.take(d >> 9);
+                const uint32_t dk = d & 511u;
+                const uint32_t dist = kDistBase[dk] + r.take(kDistExtra[dk]);
+                if (first && dist > pos) { bad = true; break; }
+                if (kWrite) {
+                    if (pos + length > text_n) { bad = true; break; }
+                    const uint32_t from = (uint32_t)pos + kRing - dist, to = (uint32_t)pos;
+                    if (dist >= length) {
+                        for (uint32_t j = lane; j < length; j += kWave) ring[(to + j) & M] = ring[(from + j) & M];
+                    } else {
+                        for (uint32_t j = lane; j < length; j += kWave) ring[(to + j) & M] = ring[(from + j % dist) & M];
+                    }
+                }
+                pos += length;
+            } else {
+                bad = true;
+                break;
+            }
+            if (r.consumed() > limit) { bad = true; break; }
+            if (kWrite && pos - flushed >= kFlushAt) flush(pos - ((a0 + (uint32_t)pos) & 7u));
+        }
+        if (r.consumed() > limit) bad = true;
+    }
+    if (bad) status = 2;
+    if (kWrite && status != 2) flush(pos);
+    GzipSpan o;
+    o.end_bit = r.consumed();
+    o.text = pos;
+    o.next = next;
+    o.status = status;
+    o.refuted = refuted;
+    o.pad = 0;
+    return o;
+}
+
+__global__ __launch_bounds__(kWave) void gzip_count_kernel(const uint8_t* __restrict__ comp, uint64_t end, const uint64_t* __restrict__ starts,
+                                                            uint32_t n_chunks, GzipSpan* __restrict__ spans) {
+    __shared__ Lds T;
+    const uint32_t c = blockIdx.x;
+    const uint64_t s = starts[c];
+    GzipSpan o = {};
+    o.status = 3;                                                   // no start: nothing decoded
+    if (s != kNoStart) o = inflate_span<false>(T, nullptr, comp, end, s, c == 0, starts, n_chunks, c, kNoStart, 0, nullptr);
+    if (lane_id() == 0) spans[c] = o;
+}
+
+__global__ __launch_bounds__(kWave) void gzip_write_kernel(const uint8_t* __restrict__ comp, uint64_t end, const GzipJob* __restrict__ jobs,
+                                                            uint16_t* __restrict__ sym, uint32_t* flags) {
+    __shared__ __align__(16) uint16_t ring[kRing];
+    __shared__ Lds T;
+    const GzipJob job = jobs[blockIdx.x];
+    const GzipSpan o = inflate_span<true>(T, ring, comp, end, job.start_bit, blockIdx.x == 0, nullptr, 0, 0, job.stop_bit, job.text_n,
+                                          sym + job.text_off);
+    const bool ok = o.text == job.text_n && o.status == (job.stop_bit == kNoStart ? 1u : 0u);
+    if (!ok && lane_id() == 0) atomicOr(flags, 8u);
+}
+
+// the true chunk that holds text position p: the last j with text_off[j] <= p (text_off[0] = 0)
+__device__ __forceinline__ uint32_t owner_of(const uint64_t* text_off, uint32_t n_true, uint64_t p) {
+    uint32_t lo = 0, hi = n_true;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (text_off[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// symbol at p (a marker) -> the byte it stands for, read from the window in front of its chunk (bytes by now); 0x8000 set:
+// it points in front of the text, or at something that is no byte
+__device__ __forceinline__ uint32_t through_window(const uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t p, uint32_t s) {
+    const uint64_t src = text_off[owner_of(text_off, n_true, p)] + (s & 0x7FFFu);
+    return src < kRing ? 0x8000u : sym[src - kRing];
+}
+
+// The windows, one workgroup, in text order: the symbols [text_off[i] - 32 768, text_off[i]) become bytes in place - 8 symbols per
+// thread and load, a vector's markers looked up side by side (their chunk: i - 1, or a few steps further back where chunks are small).
+__global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const uint64_t* __restrict__ text_off, uint32_t n_true, uint32_t* flags) {
+    bool wrong = false;
+    for (uint32_t i = 1; i < n_true; ++i) {
+        const uint64_t hi = text_off[i], lo = hi > kRing ? hi - kRing : 0;
+        for (uint64_t p0 = (lo & ~7ull) + 8ull * threadIdx.x; p0 < hi; p0 += 8 * 1024) {
+            const uint4 q = *(const uint4*)(sym + p0);
+            uint32_t w[4] = {q.x, q.y, q.z, q.w};
+            bool any = false;
+#pragma unroll
+            for (uint32_t e = 0; e < 8; ++e) {
+                const uint64_t p = p0 + e;
+                const uint32_t s = (w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                if (p >= lo && p < hi && (s & 0x8000u)) {
+                    uint32_t j = i - 1;
+                    while (text_off[j] > p) --j;
+                    const uint64_t src = text_off[j] + (s & 0x7FFFu);
+                    const uint32_t v = src < kRing ? 0x8000u : sym[src - kRing];
+                    wrong = wrong || (v & 0x8000u);
+                    w[e >> 1] = (w[e >> 1] & ~(0xFFFFu << (16 * (e & 1)))) | (v & 0xFFu) << (16 * (e & 1));
+                    any = true;
+                }
+            }
+            if (any) *(uint4*)(sym + p0) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    if (wrong) atomicOr(flags, 8u);
+}
+
+// kSeg bytes of text per workgroup: symbols in (8 per thread and load), markers through their chunk's window, the bytes
+// staged in LDS, their CRC register (from zero, no final inversion: the host chains the segments') and out in whole 16 bytes.
+__global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_t* __restrict__ sym, const uint64_t* __restrict__ text_off, uint32_t n_true,
+                                                                    uint64_t text_n, uint8_t* __restrict__ text, uint32_t* __restrict__ seg_crc, uint32_t* flags) {
+    __shared__ __align__(16) uint8_t out[kSeg];
+    __shared__ uint32_t crc_table[256];
+    __shared__ uint32_t wave_part[kSegThreads / kWave];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t base = (uint64_t)blockIdx.x * kSeg;
+    const uint32_t n = (uint32_t)min((uint64_t)kSeg, text_n - base);
+    {
+        uint32_t r = tid;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r = (r & 1u) ? (r >> 1) ^ kPoly : r >> 1;
+        crc_table[tid] = r;
+    }
+    bool wrong = false;
+    for (uint32_t k = 8 * tid; k < n; k += 8 * kSegThreads) {
+        const uint4 q = *(const uint4*)(sym + base + k);            // (the buffer is readable behind text_n)
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+        uint32_t b[2] = {0, 0};
+#pragma unroll
+        for (uint32_t e = 0; e < 8; ++e) {
+            uint32_t s = (w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+            if (k + e < n && (s & 0x8000u)) {
+                s = through_window(sym, text_off, n_true, base + k + e, s);
+                wrong = wrong || (s & 0x8000u);
+            }
+            b[e >> 2] |= (s & 0xFFu) << (8 * (e & 3));
+        }
+        *(uint2*)(out + k) = make_uint2(b[0], b[1]);
+    }
+    if (wrong) atomicOr(flags, 8u);
+    __syncthreads();
+    const uint32_t s0 = min(tid * kSegSlice, n), s1 = min(s0 + kSegSlice, n);
+    uint32_t r = 0;
+    for (uint32_t i = s0; i < s1; ++i) r = crc_table[(r ^ out[i]) & 0xFFu] ^ (r >> 8);
+    uint32_t part = s1 > s0 && n > s1 ? multmodp(x2nmodp(n - s1, 3), r) : r;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) part ^= (uint32_t)__shfl_xor((int)part, off, kWave);
+    if ((tid & (kWave - 1)) == 0) wave_part[tid / kWave] = part;
+    for (uint32_t k = 16 * tid; k < n; k += 16 * kSegThreads) {
+        if (k + 16 <= n) {
+            *(uint4*)(text + base + k) = *(const uint4*)(out + k);
+        } else {
+            for (uint32_t i = k; i < n; ++i) text[base + i] = out[i];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < kSegThreads / kWave; ++k) total ^= wave_part[k];
+        seg_crc[blockIdx.x] = total;
+    }
+}
+
+constexpr X2n kX2nHost = make_x2n();
+// (host) a CRC register shifted over n bytes
+uint32_t crc_shift(uint32_t r, uint64_t n) {
+    uint32_t p = 1u << 31, k = 3;
+    while (n) {
+        if (n & 1) p = multmodp(kX2nHost.v[k & 31], p);
+        n >>= 1;
+        ++k;
+    }
+    return multmodp(p, r);
+}
+
 }  // namespace
 
 void launch_bgzf_inflate(const uint8_t* comp, const BgzfJob* jobs, uint32_t n_jobs, uint8_t* text, uint64_t text_cap, uint32_t* flags,
                          hipStream_t s) {
     if (n_jobs) hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(n_jobs), dim3(kWave), 0, s, comp, jobs, text, text_cap, flags);
+}
+
+}  // namespace rala_hip
+
+namespace rala_hip {
+
+uint32_t gzip_segment_bytes() { return kSeg; }
+
+void launch_gzip_find(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t n_chunks,
+                      uint32_t false_sync, uint64_t* starts, hipStream_t s) {
+    hipLaunchKernelGGL(gzip_find_kernel, dim3(n_chunks), dim3(kWave), 0, s, comp, end, n_words, deflate_off, chunk_bytes, false_sync, starts);
+}
+
+void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s) {
+    hipLaunchKernelGGL(gzip_count_kernel, dim3(n_chunks), dim3(kWave), 0, s, comp, end, starts, n_chunks, spans);
+}
+
+void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, uint32_t n_jobs, uint16_t* sym, uint32_t* flags, hipStream_t s) {
+    if (n_jobs) hipLaunchKernelGGL(gzip_write_kernel, dim3(n_jobs), dim3(kWave), 0, s, comp, end, jobs, sym, flags);
+}
+
+void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
+                         uint32_t* flags, hipStream_t s) {
+    if (text_n == 0) return;
+    if (n_true > 1) hipLaunchKernelGGL(gzip_windows_kernel, dim3(1), dim3(1024), 0, s, sym, text_off, n_true, flags);
+    const uint64_t n_seg = (text_n + kSeg - 1) / kSeg;
+    hipLaunchKernelGGL(gzip_resolve_kernel, dim3((uint32_t)n_seg), dim3(kSegThreads), 0, s, sym, text_off, n_true, text_n, text, seg_crc, flags);
+}
+
+uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n) {
+    uint32_t acc = 0;
+    for (uint64_t b = 0, k = 0; b < text_n; b += kSeg, ++k) acc = crc_shift(acc, std::min<uint64_t>(kSeg, text_n - b)) ^ seg_crc[k];
+    return ~(acc ^ crc_shift(0xFFFFFFFFu, text_n));
 }
 
 }  // namespace rala_hip

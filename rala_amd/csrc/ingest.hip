@@ -505,6 +505,181 @@ int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi
     return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, t1 - (t_ship - t0), t1, f.n_readers);
 }
 
+
+// ---- a single-member gzip file (gzip, pigz, Python's gzip): inflated by speculative decoding --------------------------
+// The header of a gzip member (RFC 1952 2.3) in the first n bytes of a file: where its deflate bytes begin.  false: not a
+// header inflate would take (magic, CM != 8, reserved flag bits) or one that does not end within the n bytes.
+bool gzip_head(const uint8_t* h, uint64_t n, uint64_t* deflate_off) {
+    if (n < 10 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xE0) != 0) return false;
+    const uint32_t flg = h[3];
+    uint64_t o = 10;
+    if (flg & 4) {                                                  // FEXTRA
+        if (o + 2 > n) return false;
+        o += 2 + (h[o] | (uint64_t)h[o + 1] << 8);
+        if (o > n) return false;
+    }
+    for (uint32_t bit = 8; bit <= 16; bit <<= 1) {                  // FNAME, FCOMMENT: zero-terminated
+        if (!(flg & bit)) continue;
+        const void* z = o < n ? memchr(h + o, 0, (size_t)(n - o)) : nullptr;
+        if (!z) return false;
+        o = (uint64_t)((const uint8_t*)z - h) + 1;
+    }
+    if (flg & 2) o += 2;                                            // FHCRC (not checked, as zlib's gzread does not)
+    if (o > n) return false;
+    *deflate_off = o;
+    return true;
+}
+
+constexpr uint64_t kGzipHeadReach = 1u << 20;       // a header (name, comment, extra field) longer than this is the host reader's
+
+struct GzipFile {
+    uint64_t file_n = 0, text_n = 0;
+    float ship_ms = 0;
+    uint32_t n_readers = 0;
+    rala_hip_gzip_timings tm = {};
+};
+
+// The whole file to the device, found / counted / chained / written / resolved there (inflate_kernels.hip), the text left in
+// ctx->d_gzip_text with newlines behind it.  *valid = false: not a stream this can prove - a header the parse refuses, an
+// invalid block on the chain, a final block that does not end at the trailer, a wrong ISIZE or CRC32.
+int gzip_inflate(rala_hip_ctx* ctx, const char* path, uint32_t threads, GzipFile& g, bool* valid) {
+    *valid = false;
+    Fd file;
+    file.fd = open(path, O_RDONLY);
+    if (file.fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+    struct stat st;
+    if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    const uint64_t file_n = g.file_n = (uint64_t)st.st_size;
+    std::vector<uint8_t> head((size_t)std::min(file_n, kGzipHeadReach));
+    uint8_t trailer[8];
+    if (file_n < 18 || pread(file.fd, head.data(), head.size(), 0) != (ssize_t)head.size() ||
+        pread(file.fd, trailer, 8, (off_t)(file_n - 8)) != 8) return RALA_HIP_OK;
+    uint64_t deflate_off = 0;
+    if (!gzip_head(head.data(), head.size(), &deflate_off) || deflate_off + 8 >= file_n) return RALA_HIP_OK;
+    const uint64_t end = file_n - 8;
+    const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, ctx->gzip_chunk_bytes);
+    const uint64_t n_chunks = (end - deflate_off + chunk - 1) / chunk;
+    if (n_chunks >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    hipStream_t s = ctx->stream;
+    const double t0 = now_ms();
+    if (ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess || ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess ||
+        ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess || ctx->d_bgzf_flag.ensure(1) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    }
+    const uint8_t* comp = ctx->d_bgzf_comp.p;
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+    if (ship_file(file.fd, 0, file_n, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, []() { return true; }, &g.n_readers)) {
+        return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    }
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    g.ship_ms = (float)(t1 - t0);
+    // find, then count
+    launch_gzip_find(comp, end, (file_n + 56) / 8, deflate_off, chunk, (uint32_t)n_chunks, ctx->debug_gzip_false_sync, ctx->d_gzip_starts.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t2 = now_ms();
+    launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s);
+    INGEST_CHECK(hipGetLastError());
+    std::vector<uint64_t> starts(n_chunks);
+    std::vector<GzipSpan> spans(n_chunks);
+    INGEST_CHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t3 = now_ms();
+    // the chain from chunk 0: the true chunks, their text offsets
+    rala_hip_gzip_timings& tm = g.tm;
+    tm.compressed_bytes = file_n;
+    tm.chunks = n_chunks;
+    for (uint64_t c = 1; c < n_chunks; ++c) tm.chunks_with_candidate += starts[c] != kGzipNoStart;
+    std::vector<GzipJob> jobs;
+    std::vector<uint64_t> text_off;
+    uint64_t text_n = 0, end_bit = 0;
+    for (uint64_t c = 0;;) {
+        const GzipSpan& sp = spans[c];
+        if (sp.status > 1 || (sp.status == 0 && (sp.next <= c || sp.next >= n_chunks))) return RALA_HIP_OK;
+        GzipJob j;
+        j.start_bit = starts[c];
+        j.stop_bit = sp.status == 0 ? starts[sp.next] : kGzipNoStart;
+        j.text_off = text_n;
+        j.text_n = sp.text;
+        jobs.push_back(j);
+        text_off.push_back(text_n);
+        text_n += sp.text;
+        tm.chunks_refuted += sp.refuted;
+        tm.max_wave_text_bytes = std::max<uint64_t>(tm.max_wave_text_bytes, sp.text);
+        if (sp.status == 1) { end_bit = sp.end_bit; break; }
+        c = sp.next;
+    }
+    tm.chunks_confirmed = jobs.size() - 1;
+    tm.text_bytes = text_n;
+    tm.find_ms = (float)(t2 - t1);
+    // the final block ends in the byte in front of the trailer; ISIZE
+    if ((end_bit + 7) / 8 != end || (uint32_t)text_n != le32(trailer + 4)) return RALA_HIP_OK;
+    const uint64_t n_seg = (text_n + gzip_segment_bytes() - 1) / gzip_segment_bytes();
+    if (n_seg >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
+    if (ctx->d_gzip_sym.ensure(text_n + 64) != hipSuccess || ctx->d_gzip_text.ensure(text_n + paf_chunk_bytes() + 8192) != hipSuccess ||
+        ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess ||
+        ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess) {
+        ctx->d_gzip_sym.release();
+        ctx->d_gzip_text.release();
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the inflated text");
+    }
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t3b = now_ms();
+    launch_gzip_write(comp, end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t4 = now_ms();
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)jobs.size(), text_n, ctx->d_gzip_text.p, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    // what lies behind the text reads as newlines (as for the plain file)
+    INGEST_CHECK(hipMemsetAsync(ctx->d_gzip_text.p + text_n, '\n', paf_chunk_bytes() + 8192, s));
+    std::vector<uint32_t> seg_crc(n_seg);
+    uint32_t flag = 0;
+    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t5 = now_ms();
+    ctx->d_gzip_sym.release();
+    ctx->d_bgzf_comp.release();
+    tm.decode_ms = (float)((t3 - t2) + (t4 - t3b));        // the counting pass and the writing pass
+    tm.resolve_ms = (float)(t5 - t4);
+    if (flag || gzip_crc_of_segments(seg_crc.data(), text_n) != le32(trailer)) {
+        ctx->d_gzip_text.release();
+        return RALA_HIP_OK;
+    }
+    g.text_n = text_n;
+    *valid = true;
+    return RALA_HIP_OK;
+}
+
+// gzip's paf_tokenise_range: the lines that start in bytes [lo, hi) of the resident text
+int gzip_tokenise_range(rala_hip_ctx* ctx, GzipFile& g, uint64_t lo, uint64_t hi, bool check_lengths, const PafTarget& T, PafRange* out) {
+    *out = PafRange();
+    hi = std::min(hi, g.text_n);
+    lo = std::min(lo, hi);
+    const uint64_t n = hi - lo;
+    const uint64_t n_avail = std::min<uint64_t>(g.text_n - lo, n + paf_halo_bytes());
+    const uint32_t chunk = paf_chunk_bytes();
+    const uint64_t n_chunks = (n + chunk - 1) / chunk;
+    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    if (!tokeniser_memory(ctx, n, n_chunks, 0, T)) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+    const uint8_t* const text = ctx->d_gzip_text.p + lo;
+    bool first_is_start = lo == 0;
+    if (lo) {
+        uint8_t before = 0;
+        INGEST_CHECK(hipMemcpy(&before, text - 1, 1, hipMemcpyDeviceToHost));
+        first_is_start = before == '\n';
+    }
+    out->file_bytes = g.file_n;
+    const double t = now_ms();
+    return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, t, t, g.n_readers);
+}
+
 }  // namespace
 
 extern "C" {
@@ -566,7 +741,9 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
     // A gzip file: BGZF is inflated on the device (the windows then lie over its text), anything else is the host reader's -
     // known from the first 18 bytes, before anything is shipped
     ctx->inflate_tm = rala_hip_inflate_timings();
+    ctx->gzip_tm = rala_hip_gzip_timings();
     std::unique_ptr<BgzfFile> bg;
+    std::unique_ptr<GzipFile> gz;
     if (file_n >= 2) {
         uint8_t head[18] = {0};
         ssize_t got = -1;
@@ -577,7 +754,25 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         }
         if (got >= 2 && head[0] == 0x1f && head[1] == 0x8b) {
             bool valid = bgzf_head(head, (uint64_t)got);
-            if (valid) {
+            if (!valid && ctx->gzip_on_device) {
+                // (option gzip_on_device) any other gzip file: one member, inflated by speculative decoding - the whole text
+                // is resident afterwards, the windows lie over it
+                if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
+                if (ctx->n_name_buckets == 0 && !mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
+                INGEST_CHECK(hipSetDevice(ctx->device));
+                gz.reset(new GzipFile);
+                const int rc = gzip_inflate(ctx, path, threads, *gz, &valid);
+                ctx->gzip_tm = gz->tm;
+                if (rc != RALA_HIP_OK || !valid) {
+                    ctx->d_bgzf_comp.release();
+                    ctx->d_gzip_sym.release();
+                    ctx->d_gzip_text.release();
+                    if (rc != RALA_HIP_OK) return rc;
+                    *irregular = 8;
+                    return RALA_HIP_OK;
+                }
+                file_n = gz->text_n;
+            } else if (valid) {
                 if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
                 if (ctx->n_name_buckets == 0 && !mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
                 INGEST_CHECK(hipSetDevice(ctx->device));
@@ -589,11 +784,12 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
                 *irregular = 8;
                 return RALA_HIP_OK;
             }
-            file_n = bg->text_n;
+            if (bg) file_n = bg->text_n;
         }
     }
     auto tokenise_range = [&](uint64_t lo, uint64_t hi, const PafTarget& to, PafRange* part) {
-        return bg ? bgzf_tokenise_range(ctx, *bg, lo, hi, check_lengths != 0, threads, to, part)
+        return gz ? gzip_tokenise_range(ctx, *gz, lo, hi, check_lengths != 0, to, part) :
+               bg ? bgzf_tokenise_range(ctx, *bg, lo, hi, check_lengths != 0, threads, to, part)
                   : paf_tokenise_range(ctx, path, lo, hi, check_lengths != 0, threads, 0, to, part);
     };
     if (file_n <= window) {
@@ -641,6 +837,18 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         if (getenv("RALA_HIP_TRACE")) {
             fprintf(stderr, "[trace] device inflate: %lu BGZF members, %.3f GB compressed shipped (index and ship %.1f ms), %.3f GB of text "
                     "inflated in %.2f ms\n", (unsigned long)bg->jobs.size(), bg->shipped / 1e9, bg->ship_ms, bg->text_n / 1e9, bg->inflate_ms);
+        }
+    }
+    if (gz) {
+        ctx->d_gzip_text.release();
+        ctx->ingest_tm.ship_ms += gz->ship_ms;
+        if (getenv("RALA_HIP_TRACE")) {
+            const rala_hip_gzip_timings& g = ctx->gzip_tm;
+            fprintf(stderr, "[trace] device inflate: one gzip member, %.3f GB compressed shipped in %.1f ms, %lu chunks (%lu with a candidate, %lu "
+                    "confirmed, %lu refuted), %.3f GB of text (at most %.3f GB by one wave): find %.2f ms, decode %.2f ms, resolve %.2f ms\n",
+                    g.compressed_bytes / 1e9, gz->ship_ms, (unsigned long)g.chunks, (unsigned long)g.chunks_with_candidate,
+                    (unsigned long)g.chunks_confirmed, (unsigned long)g.chunks_refuted, g.text_bytes / 1e9, g.max_wave_text_bytes / 1e9,
+                    g.find_ms, g.decode_ms, g.resolve_ms);
         }
     }
     if (R.flags) {
@@ -704,6 +912,19 @@ int rala_hip_get_ingest_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out)
 int rala_hip_get_inflate_timings(rala_hip_ctx* ctx, rala_hip_inflate_timings* out) {
     if (!ctx || !out) return RALA_HIP_EINVAL;
     *out = ctx->inflate_tm;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_gzip_timings(rala_hip_ctx* ctx, rala_hip_gzip_timings* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->gzip_tm;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_head(const uint8_t* bytes, uint64_t n, uint64_t* deflate_off, int* valid) {
+    if ((!bytes && n) || !deflate_off || !valid) return RALA_HIP_EINVAL;
+    *deflate_off = 0;
+    *valid = gzip_head(bytes, n, deflate_off) ? 1 : 0;
     return RALA_HIP_OK;
 }
 

@@ -510,6 +510,35 @@ struct BgzfJob {
 void launch_bgzf_inflate(const uint8_t* comp, const BgzfJob* jobs, uint32_t n_jobs, uint8_t* text, uint64_t text_cap, uint32_t* flags,
                          hipStream_t s);
 
+// ---- a single-member gzip stream -> text by speculative decoding (inflate_kernels.hip) -------------
+// Offsets are bytes / bits from the start of `comp`, which holds the whole file (aligned, 64 readable bytes behind it, n_words
+// = its 8-byte words); end = the trailer's first byte.
+constexpr uint64_t kGzipNoStart = ~0ull;
+// what the counting pass found from one chunk's start: status 0 = it ended at the start of chunk `next`, 1 = its final block
+// ended at bit end_bit, 2 = invalid, 3 = the chunk has no start; text = the bytes it gives; refuted = later starts it passed
+struct GzipSpan {
+    uint64_t end_bit, text;
+    uint32_t next, status, refuted, pad;
+};
+// one true chunk for the writing pass: decoded from start_bit to the block boundary stop_bit (kGzipNoStart: to the final block's
+// end), its text_n symbols to sym + text_off; job 0 is the stream's first chunk
+struct GzipJob {
+    uint64_t start_bit, stop_bit, text_off, text_n;
+};
+// starts[c], c < n_chunks: where chunk c's first candidate block begins (chunk 0: 8 * deflate_off), kGzipNoStart = none;
+// false_sync n != 0 (tests): every n-th chunk is given its first bit as its start
+void launch_gzip_find(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t n_chunks,
+                      uint32_t false_sync, uint64_t* starts, hipStream_t s);
+void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s);
+// flags |= 8 where a job does not give what the counting pass said
+void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, uint32_t n_jobs, uint16_t* sym, uint32_t* flags, hipStream_t s);
+// text_off[j] = job j's text offset; sym (readable 64 symbols behind text_n) -> text, and the CRC register of every
+// gzip_segment_bytes() of it in seg_crc; flags |= 8: a symbol that points in front of the text
+void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
+                         uint32_t* flags, hipStream_t s);
+uint32_t gzip_segment_bytes();
+uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n);        // (host) the text's CRC32
+
 // ---- scans (scan_kernels.hip) --------------------------------------------------
 // exclusive prefix sum of n uint32 values; out may alias in; out[n] receives the total
 size_t scan_workspace_bytes(uint64_t n);

@@ -31,7 +31,7 @@ SYMBOLS = (
     "rala_hip_copy_device_state", "rala_hip_layout", "rala_hip_find_repetitive_hills",
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
-    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_mg_destroy", "rala_hip_mg_last_error", "rala_hip_mg_set_reads", "rala_hip_mg_slice_cuts",
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
@@ -67,6 +67,16 @@ class Timings(ctypes.Structure):
 class MgTimings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("emit_ms", "exchange_ms", "owner_ms", "gather_ms", "construct_ms",
                                               "repeats_ms", "tr_ms", "total_ms")] + [("tuples_sent", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GzipTimings(ctypes.Structure):
+    """rala_hip_gzip_timings"""
+    _fields_ = [(n, ctypes.c_float) for n in ("find_ms", "decode_ms", "resolve_ms")] + [(n, ctypes.c_uint64) for n in (
+        "compressed_bytes", "text_bytes", "chunks", "chunks_with_candidate", "chunks_confirmed", "chunks_refuted",
+        "max_wave_text_bytes")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -145,6 +155,8 @@ def lib(build=True):
         L.rala_hip_mg_get_pile_data.argtypes = [vp, u64, vp]
         L.rala_hip_mg_get_pile_row_digests.argtypes = [vp, vp, vp, vp]
         L.rala_hip_mg_get_timings.argtypes = [vp, ctypes.POINTER(MgTimings)]
+        L.rala_hip_get_gzip_timings.argtypes = [vp, ctypes.POINTER(GzipTimings)]
+        L.rala_hip_gzip_head.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i32)]
         _lib = L
     return _lib
 

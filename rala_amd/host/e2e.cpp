@@ -3,11 +3,13 @@
 // loading excluded like in the metric's definition.  Read names are "r<i>" (what rala_amd.synth
 // writes).  Ingest: an uncompressed file's text goes to the device and is tokenised there
 // (rala_hip_set_overlaps_from_paf; ms_parse = ship + tokenise, ms_upload = the name table), a
-// BGZF file's members are inflated there first; a plain gzip file, a file the device tokeniser
+// BGZF file's members are inflated there first, a single-member gzip file too where
+// io::device_gzip_wanted(); a file the device tokeniser
 // calls irregular, or device_ingest = 0: the host readers (multi-threaded parse, then the columns'
 // upload).
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <chrono>
@@ -44,10 +46,16 @@ extern "C" int rala_e2e_from_paf_with(const char* paf_path, const uint32_t* read
         int irregular = 0;
         rc = rala_hip_set_name_table(ctx, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
         t1 = clock::now();
+        // (a single-member gzip file: inflated on the device where io::device_gzip_wanted() says so; no room for it there: the host reader)
+        if (rc == RALA_HIP_OK && rala::io::has_suffix(path, ".gz") && rala::io::device_gzip_wanted()) rc = rala_hip_set_option(ctx, "gzip_on_device", 1);
+        // (measurements, tools/e2e_bench.py: the chunk size of that inflater)
+        if (rc == RALA_HIP_OK && getenv("RALA_E2E_GZIP_CHUNK")) rc = rala_hip_set_option(ctx, "gzip_chunk_bytes", atoll(getenv("RALA_E2E_GZIP_CHUNK")));
         if (rc == RALA_HIP_OK) rc = rala_hip_set_overlaps_from_paf(ctx, paf_path, 1, num_threads, &bad, &irregular);
         t2 = clock::now();
-        if (rc != RALA_HIP_OK || bad >= 0) { rala_hip_destroy(ctx); return -2; }
-        on_device = irregular == 0;
+        const bool no_room = rc == RALA_HIP_ENOMEM;
+        if ((rc != RALA_HIP_OK && !no_room) || bad >= 0) { rala_hip_destroy(ctx); return -2; }
+        rc = RALA_HIP_OK;
+        on_device = irregular == 0 && !no_room;
         if (on_device) {
             rala_hip_get_overlap_columns(ctx, &n_ovl, nullptr, nullptr);
             // (reported as: ms_upload = the name table, ms_parse = the text's way to the device + the tokeniser)

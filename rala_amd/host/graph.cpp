@@ -265,12 +265,19 @@ void Graph::initialize() {
     // too large for its 32-bit counts, no room for its text in device memory - falls through to the host reader, which knows
     // what to do with such files (a FIFO named *.paf used to end with "unable to open file").
     // (round 6: an uncompressed MHAP file too - twelve numeric columns, no names to look up; one GPU - several take the host reader)
-    // A BGZF-compressed .paf.gz / .mhap.gz on one GPU as well: inflated on the device (any other gzip file is irregular there);
+    // A BGZF-compressed .paf.gz / .mhap.gz on one GPU as well: inflated on the device (any other gzip file is irregular there
+    // unless the option below is set);
     // several GPUs take the host reader for every .gz file.
     const bool gz = io::has_suffix(overlaps_path_, ".paf.gz") || io::has_suffix(overlaps_path_, ".mhap.gz");
     const bool mhap_text = io::has_suffix(overlaps_path_, ".mhap") || io::has_suffix(overlaps_path_, ".mhap.gz");
     const bool device_ingest = (io::has_suffix(overlaps_path_, ".paf") || ((mhap_text || gz) && ranks_.empty())) &&
                                !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
+    // A single-member gzip file (gzip, pigz, `minimap2 | gzip`) is inflated on the device too where io::device_gzip_wanted()
+    // says so (option gzip_on_device: speculative decoding); what that cannot prove is flag 8 like
+    // any other irregular file, and the host reader below decides
+    if (gz && ranks_.empty() && device_ingest && io::device_gzip_wanted()) {
+        check(ctx_, rala_hip_set_option(ctx_, "gzip_on_device", 1), "initialize");
+    }
     auto falls_back = [](int rc) { return rc == RALA_HIP_ENOTAFILE || rc == RALA_HIP_ETOOLARGE || rc == RALA_HIP_ENOMEM; };
     auto length_error = [](int64_t bad) {
         fprintf(stderr, "[rala::Overlap::transmute] error: "

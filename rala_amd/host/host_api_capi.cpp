@@ -133,9 +133,11 @@ struct PafOnDevice {
     std::vector<uint32_t> col[7];
     std::vector<uint8_t> strand;
     rala_hip_ingest_timings tm = {};
+    rala_hip_gzip_timings gz = {};
 };
 
-static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap);
+static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap,
+                            const char* const* keys = nullptr, const int64_t* values = nullptr, uint32_t n_options = 0);
 void* hp_paf_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads) {
     return text_on_device(path, names, read_len, n_reads, check_lengths, threads, false);
 }
@@ -143,7 +145,14 @@ void* hp_paf_device(const char* path, const char* names, const uint32_t* read_le
 void* hp_mhap_device(const char* path, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads) {
     return text_on_device(path, "", read_len, n_reads, check_lengths, threads, true);
 }
-static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap) {
+// The two with options of the context set first (rala_hip_set_option: n_options keys and values; mhap != 0: an MHAP file, no
+// names) - tests/test_gpu_gzip.py; hp_paf_device_gzip_info gives what rala_hip_get_gzip_timings gave.
+void* hp_text_device_with(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads,
+                          int mhap, const char* const* keys, const int64_t* values, uint32_t n_options) {
+    return text_on_device(path, mhap ? "" : names, read_len, n_reads, check_lengths, threads, mhap != 0, keys, values, n_options);
+}
+static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap,
+                            const char* const* keys, const int64_t* values, uint32_t n_options) {
     std::vector<std::string> nm;
     const char* p = names;
     for (uint64_t i = 0; i < n_reads && !mhap; ++i) {
@@ -157,13 +166,15 @@ static void* text_on_device(const char* path, const char* names, const uint32_t*
     rala_hip_ctx* ctx = nullptr;
     out->rc = rala_hip_create(0, &ctx);
     if (out->rc != RALA_HIP_OK) return out;
-    out->rc = rala_hip_set_reads(ctx, read_len, n_reads);
+    for (uint32_t k = 0; k < n_options && out->rc == RALA_HIP_OK; ++k) out->rc = rala_hip_set_option(ctx, keys[k], values[k]);
+    if (out->rc == RALA_HIP_OK) out->rc = rala_hip_set_reads(ctx, read_len, n_reads);
     if (out->rc == RALA_HIP_OK && !mhap) out->rc = rala_hip_set_name_table(ctx, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
     if (out->rc == RALA_HIP_OK) {
         out->rc = mhap ? rala_hip_set_overlaps_from_mhap(ctx, path, check_lengths, threads, &out->bad, &out->irregular)
                        : rala_hip_set_overlaps_from_paf(ctx, path, check_lengths, threads, &out->bad, &out->irregular);
     }
     if (out->rc == RALA_HIP_OK) rala_hip_get_ingest_timings(ctx, &out->tm);
+    if (out->rc == RALA_HIP_OK) rala_hip_get_gzip_timings(ctx, &out->gz);
     if (out->rc == RALA_HIP_OK && !out->irregular && out->bad < 0) {
         out->rc = rala_hip_get_overlap_columns(ctx, &out->n, nullptr, nullptr);
         uint32_t* cols[7];
@@ -267,6 +278,15 @@ void hp_paf_device_info(void* h, int64_t* info) {
     const auto* o = (const PafOnDevice*)h;
     info[0] = o->rc; info[1] = o->irregular; info[2] = o->bad; info[3] = (int64_t)o->n;
     info[4] = (int64_t)(o->tm.ship_ms * 1000.0f); info[5] = (int64_t)(o->tm.tokenize_ms * 1000.0f);
+}
+// info[0 .. 9] = find us, decode us, resolve us, compressed bytes, text bytes, chunks, with a candidate, confirmed, refuted,
+// the most text bytes of one wave
+void hp_paf_device_gzip_info(void* h, int64_t* info) {
+    const rala_hip_gzip_timings& g = ((const PafOnDevice*)h)->gz;
+    info[0] = (int64_t)(g.find_ms * 1000.0f); info[1] = (int64_t)(g.decode_ms * 1000.0f); info[2] = (int64_t)(g.resolve_ms * 1000.0f);
+    info[3] = (int64_t)g.compressed_bytes; info[4] = (int64_t)g.text_bytes; info[5] = (int64_t)g.chunks;
+    info[6] = (int64_t)g.chunks_with_candidate; info[7] = (int64_t)g.chunks_confirmed; info[8] = (int64_t)g.chunks_refuted;
+    info[9] = (int64_t)g.max_wave_text_bytes;
 }
 void hp_paf_device_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uint32_t* a_end, uint32_t* b_begin, uint32_t* b_end,
                         uint32_t* length, uint8_t* strand) {

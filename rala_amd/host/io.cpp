@@ -67,6 +67,11 @@ bool has_suffix(const std::string& src, const std::string& suffix) {
     return src.size() >= suffix.size() && src.compare(src.size() - suffix.size(), suffix.size(), suffix) == 0;
 }
 
+bool device_gzip_wanted() {
+    const char* e = getenv("RALA_DEVICE_GZIP");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool read_fasta(const std::string& path, const SequenceSink& sink) {
     Lines in(path);
     if (!in.ok()) return false;

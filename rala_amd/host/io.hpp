@@ -34,6 +34,9 @@ bool read_paf(const std::string& path, const std::function<void(const PafRecord&
 bool read_mhap(const std::string& path, const std::function<void(const MhapRecord&)>& sink);
 
 bool has_suffix(const std::string& src, const std::string& suffix);
+/*! @brief is a single-member gzip overlap file inflated on the device (rala_hip option "gzip_on_device")?  RALA_DEVICE_GZIP=1 / =0
+ * says so, read where the file is opened; without it: no - see README.md, "Compressed overlap files", for what was measured */
+bool device_gzip_wanted();
 
 // ---- one-pass, multi-threaded ingest of an uncompressed PAF file into binary columns -------
 // (the reference tokenises every line into a heap Overlap twice,
