@@ -21,6 +21,8 @@
 // as inflate_table takes them (over-subscribed: never; incomplete: only a single code of one bit for literals/lengths and
 // distances), no distance in front of the member's start, length symbols 286/287 and distance symbols 30/31 invalid, stored
 // blocks with LEN = ~NLEN, and the CRC.  Anything else sets flag 8 and writes nothing of that member.
+// The contract is tested (tests/test_gpu_inflate_crafted.py, both inflaters) against the case list of tests/deflate_craft.py -
+// handmade streams that zlib's compressor never writes, valid and invalid - with zlib's inflate and the host reader as the verdict.
 //
 // Below the BGZF kernel: a single-member gzip stream by speculative decoding over chunks of the compressed bytes (its own header comment).
 #include <hip/hip_runtime.h>

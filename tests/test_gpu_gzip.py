@@ -3,7 +3,9 @@
 exactly what the plain file gives through the device tokeniser - columns, the first length-check offender, the irregular
 verdict - across zlib levels and strategies, flush points, header fields and chunk sizes; refuted block starts change
 nothing; a file this cannot prove gives irregular & 8 with nothing set; the graph and the CLI from a .gz file are those
-from the text.  A fallback (flag 8) on a good file is a failure in every case here.
+from the text.  A fallback (flag 8) on a good file is a failure in every case here.  The streams here are zlib's compressor's
+(and one handmade block); what zlib's inflate takes but its compressor never writes, and what it refuses, is held against
+the same kernels in tests/test_gpu_inflate_crafted.py.
 
 Data: Dataset(2000, 150 000) is about 9 MB of PAF; zlib's default strategy at memLevel 8 closes a block every 16 383
 symbols, a few tens of KB of text each, so such a file holds a few hundred dynamic blocks and chunks of 4 - 16 KB of
@@ -21,6 +23,7 @@ import pytest
 from rala_amd import build, hip
 from rala_amd.synth import Dataset
 
+from deflate_craft import LEN_BASE, LEN_EXTRA, _bits, gz_member
 import test_gpu_ingest as gi
 import test_ingest_cpu as host
 
@@ -30,12 +33,6 @@ STRATEGIES = {"default": zlib.Z_DEFAULT_STRATEGY, "filtered": zlib.Z_FILTERED, "
               "fixed": zlib.Z_FIXED}
 GZ_KEYS = ("find_us", "decode_us", "resolve_us", "compressed_bytes", "text_bytes", "chunks", "with_candidate", "confirmed", "refuted",
            "max_wave_text")
-
-
-def gz_member(body, data, name=None):
-    """a gzip member around raw deflate bytes `body` of text `data` (FNAME when a name is given)"""
-    h = b"\x1f\x8b\x08" + (b"\x08" if name else b"\x00") + b"\x00" * 4 + b"\x00\xff" + (name + b"\x00" if name else b"")
-    return h + body + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF)
 
 
 def deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, flushes=0, flush=zlib.Z_FULL_FLUSH):
@@ -141,24 +138,6 @@ def test_gzip_paf_and_mhap_equal_the_plain_file(tmp_path, level, strategy):
             gz = good(device(plain + ".gz", names, ds.read_len, mhap=is_mhap, **options), w, size)
             if dynamic and options:
                 spread(gz)
-
-
-def _bits():
-    out = []
-
-    def put(v, n):                      # n bits of v, least significant first (extra bits, headers)
-        for k in range(n):
-            out.append((v >> k) & 1)
-
-    def huff(code, n):                  # a Huffman code: most significant bit first
-        for k in range(n - 1, -1, -1):
-            out.append((code >> k) & 1)
-
-    return out, put, huff
-
-
-LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
 
 
 def fixed_block_of_far_matches(total):
