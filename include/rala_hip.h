@@ -115,6 +115,8 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * "gzip_on_device" (default 0; 1: rala_hip_set_overlaps_from_paf / _mhap inflate a single-member gzip file on the device, see there),
  * "gzip_chunk_bytes" (default 65536: the compressed bytes one wave of that inflater starts in; at least 1024),
  * "debug_gzip_false_sync" (tests: every n-th of those chunks is given a bogus block start at its first bit; 0, the default: none),
+ * "debug_sequence_window" (tests: rala_hip_index_sequences takes the read file's text through windows of this many bytes; 0, the
+ * default: a quarter of the free device memory, 2 GiB at most),
  * "debug_pile_stop_after" (diagnostics: leave the run-space pile kernel after phase k, 99 = all;
  * 100 * m + k: the same without the row stores (m = 1), tools/phase_probe.py) */
 int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value);
@@ -206,6 +208,32 @@ int rala_hip_gzip_head(const uint8_t* bytes, uint64_t n, uint64_t* deflate_off, 
  * exclusive scan of the text sizes) are written to the arrays given (any may be null). */
 int rala_hip_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, uint64_t cap, uint64_t* n_members, uint64_t* file_off,
                         uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* text_off, int* valid);
+/* ---- the read file: names, lengths and offsets of every sequence, indexed on the device ---------------------------------
+ * Replaces the first sequence pass of Graph::initialize (src/graph.cpp:249-264: bioparser's FASTA / FASTQ parser, a heap
+ * Sequence per read of which the name and the length are kept) and lets the second one (src/graph.cpp:527-551) cut the
+ * bases of the reads the graph keeps out of the file instead of parsing it again.  format 0: FASTA - a record starts with
+ * '>' at byte 0 of the text or directly behind a newline, its name ends at the first blank, tab or line end, its bases are
+ * the lines up to the next record, newlines (and a carriage return in front of one) taken out; bytes in front of the first
+ * '>' are ignored.  format 1: FASTQ of four lines per record - a header that is not empty, bases, a line that starts with
+ * '+', qualities as long as the bases.  The text goes through device memory in windows (`threads` reader threads, pinned
+ * staging, as for the overlaps; option "debug_sequence_window": the window's bytes, for tests); a BGZF file is inflated on
+ * the device, offsets are then offsets into its text.  What the host readers (rala_amd/host/io.cpp: read_fasta, read_fastq)
+ * give for such a file is what this gives.  *irregular != 0: nothing was set, the context's reads are what they were - take
+ * the host reader: 1 FASTQ of another shape (multi-line records, blank lines, a cut record, a quality line of another
+ * length), 2 a name of more than 1024 bytes, 4 a header line of more than 4096 bytes, 8 a gzip file that is not BGZF (known
+ * from its first 18 bytes) or a BGZF file the inflater refuses.  A FIFO: RALA_HIP_ENOTAFILE; a read of 2^32 bases or more:
+ * RALA_HIP_ETOOLARGE.  After a successful call the lengths are the context's reads, as rala_hip_set_reads leaves them. */
+int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, uint32_t threads, uint64_t* n_records,
+                             uint64_t* name_bytes, int* irregular);
+/* The index of the last successful rala_hip_index_sequences (bioparser's FASTA / FASTQ parsers, per record what they put into a
+ * Sequence: src/sequence.cpp:11-23), n_records entries each, any pointer may be NULL: the name = name_len bytes at names +
+ * name_off (names: name_bytes bytes, the names in record order); the bases = the length bytes that remain of the text
+ * [data_off, data_off + data_span) when every newline and every carriage return in front of one is taken out. */
+int rala_hip_get_sequence_index(rala_hip_ctx* ctx, uint64_t* name_off, uint32_t* name_len, uint64_t* data_off,
+                                uint64_t* data_span, uint32_t* length, char* names);
+/* ship_ms: the file (BGZF: its compressed bytes) to the device; tokenize_ms: the kernels (BGZF: the inflater among them);
+ * bytes: the text's; lines: the records (the "loaded sequences" stage of src/graph.cpp:246-266) */
+int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out);
 /* The sensitive overlaps (rala -s; Graph::preprocess, src/graph.cpp:901-939) of an uncompressed PAF file the same way, without
  * the length check (Overlap::transmute_ has none, src/overlap.cpp:84-114): the lines that start in bytes [lo, hi) of the file
  * (hi = ~0: to its end; a rank of a sharded run takes a share - any split of the sensitive set will do).  *out receives DEVICE

@@ -257,6 +257,14 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint16_t> d_gzip_sym;
     rala_hip::DevBuf<uint32_t> d_gzip_crc;
     rala_hip_gzip_timings gzip_tm = {};
+    // the sequence index (ingest.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
+    int64_t debug_sequence_window = 0;          // tests: the window over the read file's text (0: as the overlap ingest's, 2 GiB at most)
+    rala_hip::DevBuf<uint64_t> d_seq_event[2], d_seq_name_pos, d_seq_data_off, d_seq_data_stripped, d_seq_name_off, d_seq_span;
+    rala_hip::DevBuf<uint32_t> d_seq_name_len, d_seq_length, d_seq_tile[2], d_seq_name_at, d_seq_flags;
+    rala_hip::DevBuf<uint8_t> d_seq_arena;
+    uint64_t n_seq_records = 0, n_seq_name_bytes = 0;
+    bool seq_index_valid = false;
+    rala_hip_ingest_timings seq_tm = {};
 
     // overlaps
     uint64_t n_ovl = 0;

@@ -424,18 +424,17 @@ int bgzf_open(rala_hip_ctx* ctx, const char* path, uint32_t threads, uint64_t wi
     return RALA_HIP_OK;
 }
 
-// bgzf's paf_tokenise_range: the lines that start in bytes [lo, hi) of the file's TEXT
-int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads, const PafTarget& T,
-                        PafRange* out) {
-    *out = PafRange();
-    hi = std::min(hi, f.text_n);
-    lo = std::min(lo, hi);
-    const uint64_t n = hi - lo;
-    const uint64_t n_avail = std::min<uint64_t>(f.text_n - lo, n + paf_halo_bytes());
-    const uint32_t chunk = paf_chunk_bytes();
-    const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
-    const uint64_t cap = n_chunks * chunk + 4096 + 64;
+// The text [lo, lo + n_avail) of a BGZF file (and the byte in front of it) in device memory: the members that cover it
+// shipped (unless the file is resident) and inflated into ctx->d_paf_text, `pad` in the bytes behind the text up to cap.
+// meanwhile runs while the readers work (false: `room` could not be made).  out->flag != 0: the inflater refused a member
+// (the text's memory is given back).
+struct BgzfText {
+    uint8_t* text = nullptr;
+    uint32_t flag = 0;
+    double t0 = 0, t_ship = 0, t1 = 0;
+};
+int bgzf_text_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t n_avail, uint64_t cap, int pad, uint32_t threads,
+                    const std::function<bool()>& meanwhile, const char* room, BgzfText* out) {
     hipStream_t s = ctx->stream;
     // the members that hold the text [lo - 1, lo + n_avail) (the byte in front of lo says whether lo starts a line)
     const uint64_t need_lo = lo ? lo - 1 : 0, need_hi = lo + n_avail;
@@ -449,22 +448,21 @@ int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi
     const uint64_t shift = lo - base;
     const uint64_t extent = j1 > j0 ? f.jobs[j1 - 1].text_off + f.jobs[j1 - 1].isize - base : 0;
     const uint64_t size = std::max(shift + cap, extent) + 64;
-    const double t0 = now_ms();
+    out->t0 = now_ms();
     if (ctx->d_paf_text.ensure(size) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
     uint64_t comp_base = 0;
-    auto columns = [&]() { return tokeniser_memory(ctx, n, n_chunks, 0, T); };
     if (!f.resident && j1 > j0) {
         comp_base = f.jobs[j0].off;
         const uint64_t c_len = f.jobs[j1 - 1].off + f.jobs[j1 - 1].bsize - comp_base;
         if (ctx->d_bgzf_comp.ensure(c_len + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
-        const int shipped = ship_file(f.file.fd, comp_base, c_len, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, columns, &f.n_readers);
-        if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+        const int shipped = ship_file(f.file.fd, comp_base, c_len, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, meanwhile, &f.n_readers);
+        if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
         if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying the compressed file failed");
         f.shipped += c_len;
-    } else if (!columns()) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+    } else if (!meanwhile()) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
     }
-    const double t_ship = now_ms();
+    out->t_ship = now_ms();
     std::vector<BgzfJob> jobs(j1 - j0);
     for (size_t j = j0; j < j1; ++j) {
         const BgzfMember& m = f.jobs[j];
@@ -485,16 +483,38 @@ int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi
         INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
     }
     uint8_t* const text = ctx->d_paf_text.p + shift;
-    // what lies behind the text reads as newlines (as for the plain file)
-    INGEST_CHECK(hipMemsetAsync(text + n_avail, '\n', cap - n_avail, s));
+    INGEST_CHECK(hipMemsetAsync(text + n_avail, pad, cap - n_avail, s));
     INGEST_CHECK(hipStreamSynchronize(s));
-    const double t1 = now_ms();
-    f.inflate_ms += (float)(t1 - t_ship);
-    if (flag) {
-        ctx->d_paf_text.release();
-        out->flags = flag;
+    out->t1 = now_ms();
+    f.inflate_ms += (float)(out->t1 - out->t_ship);
+    if (flag) ctx->d_paf_text.release();
+    out->text = text;
+    out->flag = flag;
+    return RALA_HIP_OK;
+}
+
+// bgzf's paf_tokenise_range: the lines that start in bytes [lo, hi) of the file's TEXT
+int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads, const PafTarget& T,
+                        PafRange* out) {
+    *out = PafRange();
+    hi = std::min(hi, f.text_n);
+    lo = std::min(lo, hi);
+    const uint64_t n = hi - lo;
+    const uint64_t n_avail = std::min<uint64_t>(f.text_n - lo, n + paf_halo_bytes());
+    const uint32_t chunk = paf_chunk_bytes();
+    const uint64_t n_chunks = (n + chunk - 1) / chunk;
+    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    const uint64_t cap = n_chunks * chunk + 4096 + 64;
+    // what lies behind the text reads as newlines (as for the plain file)
+    BgzfText bt;
+    const int rc = bgzf_text_range(ctx, f, lo, n_avail, cap, '\n', threads, [&]() { return tokeniser_memory(ctx, n, n_chunks, 0, T); },
+                                   "device memory for the overlap columns", &bt);
+    if (rc != RALA_HIP_OK) return rc;
+    if (bt.flag) {
+        out->flags = bt.flag;
         return RALA_HIP_OK;
     }
+    const uint8_t* const text = bt.text;
     bool first_is_start = lo == 0;
     if (lo) {
         uint8_t before = 0;
@@ -502,7 +522,7 @@ int bgzf_tokenise_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t hi
         first_is_start = before == '\n';
     }
     out->file_bytes = f.file_n;
-    return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, t1 - (t_ship - t0), t1, f.n_readers);
+    return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, bt.t1 - (bt.t_ship - bt.t0), bt.t1, f.n_readers);
 }
 
 
@@ -678,6 +698,83 @@ int gzip_tokenise_range(rala_hip_ctx* ctx, GzipFile& g, uint64_t lo, uint64_t hi
     out->file_bytes = g.file_n;
     const double t = now_ms();
     return tokenise_text(ctx, text, n, n_avail, first_is_start, check_lengths, 0, T, out, t, t, g.n_readers);
+}
+
+// ---- the sequence index: FASTA / FASTQ text -> names, lengths, offsets (sequence_kernels.hip) ----------------------
+// One window of the text, in device memory at `text` (launch_sequence_count's layout): count, scan, the events and records
+// written behind those of the windows before it, the names gathered behind theirs.  *flags: the kernels' verdict.
+struct SequenceRun {
+    bool fastq = false;
+    uint64_t text_n = 0;
+    uint64_t n_events = 0, n_stripped = 0, n_records = 0, name_bytes = 0;
+    bool last_is_newline = true;        // the byte in front of the next window
+};
+int index_window(rala_hip_ctx* ctx, SequenceRun& R, const uint8_t* text, uint64_t lo, uint64_t n, uint64_t n_avail, uint32_t* flags) {
+    hipStream_t s = ctx->stream;
+    const uint64_t n_tiles = (n + sequence_tile_bytes() - 1) / sequence_tile_bytes();
+    *flags = 0;
+    if (!n_tiles) return RALA_HIP_OK;
+    INGEST_CHECK(ctx->d_seq_tile[0].ensure(n_tiles + 2));
+    INGEST_CHECK(ctx->d_seq_tile[1].ensure(n_tiles + 2));
+    INGEST_CHECK(ctx->d_seq_flags.ensure(1));
+    INGEST_CHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)));
+    launch_sequence_count(text, n, R.last_is_newline, R.fastq, ctx->d_seq_tile[0].p, ctx->d_seq_tile[1].p, s);
+    launch_exclusive_scan(ctx->d_seq_tile[0].p, ctx->d_seq_tile[0].p, n_tiles, ctx->d_scan_ws.p, s);
+    launch_exclusive_scan(ctx->d_seq_tile[1].p, ctx->d_seq_tile[1].p, n_tiles, ctx->d_scan_ws.p, s);
+    uint32_t events = 0, stripped = 0;
+    uint8_t last = 0;
+    INGEST_CHECK(hipMemcpyAsync(&events, ctx->d_seq_tile[0].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(&stripped, ctx->d_seq_tile[1].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(&last, text + n - 1, 1, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    INGEST_CHECK(hipGetLastError());
+    // (a FASTQ record is four events; one whose lines are spread over two windows is counted where its header lies)
+    const uint64_t ev_after = R.n_events + events;
+    const uint64_t rec_before = R.n_records, rec_after = R.fastq ? (ev_after + 3) / 4 : ev_after;
+    if (ctx->d_seq_event[0].grow(R.n_events, ev_after + 1) != hipSuccess || ctx->d_seq_event[1].grow(R.n_events, ev_after + 1) != hipSuccess ||
+        ctx->d_seq_name_pos.grow(rec_before, rec_after + 1) != hipSuccess || ctx->d_seq_name_len.grow(rec_before, rec_after + 1) != hipSuccess ||
+        ctx->d_seq_data_off.grow(rec_before, rec_after + 1) != hipSuccess || ctx->d_seq_data_stripped.grow(rec_before, rec_after + 1) != hipSuccess ||
+        ctx->d_seq_name_off.grow(rec_before, rec_after + 1) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
+    }
+    INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+    SequenceWindow W;
+    W.text = text; W.n = n; W.n_avail = n_avail; W.text_off = lo; W.text_n = R.text_n;
+    W.first_is_start = R.last_is_newline ? 1u : 0u;
+    W.tile_event0 = ctx->d_seq_tile[0].p; W.tile_stripped0 = ctx->d_seq_tile[1].p;
+    W.event0 = R.n_events; W.stripped0 = R.n_stripped;
+    SequenceColumns C;
+    C.event_pos = ctx->d_seq_event[0].p; C.event_stripped = ctx->d_seq_event[1].p;
+    C.name_pos = ctx->d_seq_name_pos.p; C.name_len = ctx->d_seq_name_len.p;
+    C.data_off = ctx->d_seq_data_off.p; C.data_stripped = ctx->d_seq_data_stripped.p;
+    launch_sequence_records(W, R.fastq, C, ctx->d_seq_flags.p, s);
+    INGEST_CHECK(hipGetLastError());
+    // the headers of this window: FASTA - every event; FASTQ - the events 4r
+    const uint64_t hdr_before = R.fastq ? (R.n_events + 3) / 4 : R.n_events;
+    const uint64_t n_hdr = rec_after - hdr_before;
+    uint32_t bytes = 0;
+    if (n_hdr) {
+        INGEST_CHECK(ctx->d_seq_name_at.ensure(n_hdr + 2));
+        INGEST_CHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_hdr + 2)));
+        launch_exclusive_scan(ctx->d_seq_name_len.p + hdr_before, ctx->d_seq_name_at.p, n_hdr, ctx->d_scan_ws.p, s);
+        INGEST_CHECK(hipMemcpyAsync(&bytes, ctx->d_seq_name_at.p + n_hdr, 4, hipMemcpyDeviceToHost, s));
+    }
+    INGEST_CHECK(hipMemcpyAsync(flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    if (*flags) return RALA_HIP_OK;
+    if (n_hdr) {
+        if (ctx->d_seq_arena.grow(R.name_bytes, R.name_bytes + bytes + 1) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the names");
+        launch_sequence_names(text, lo, ctx->d_seq_name_pos.p + hdr_before, ctx->d_seq_name_len.p + hdr_before, ctx->d_seq_name_at.p, n_hdr,
+                              R.name_bytes, ctx->d_seq_arena.p, ctx->d_seq_name_off.p + hdr_before, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipStreamSynchronize(s));
+    }
+    R.n_events = ev_after;
+    R.n_stripped += stripped;
+    R.n_records = rec_after;
+    R.name_bytes += bytes;
+    R.last_is_newline = last == '\n';
+    return RALA_HIP_OK;
 }
 
 }  // namespace
@@ -900,6 +997,152 @@ int rala_hip_get_overlap_columns(rala_hip_ctx* ctx, uint64_t* n, uint32_t* const
         if (cols[k] && ctx->n_ovl) INGEST_CHECK(hipMemcpy(cols[k], src[k], ctx->n_ovl * 4, hipMemcpyDeviceToHost));
     }
     if (strand && ctx->n_ovl) INGEST_CHECK(hipMemcpy(strand, ctx->ovl.strand, ctx->n_ovl, hipMemcpyDeviceToHost));
+    return RALA_HIP_OK;
+}
+
+int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, uint32_t threads, uint64_t* n_records, uint64_t* name_bytes,
+                             int* irregular) {
+    if (!ctx || !path || !n_records || !name_bytes || !irregular || (format != 0 && format != 1)) return RALA_HIP_EINVAL;
+    *n_records = *name_bytes = 0;
+    *irregular = 0;
+    ctx->seq_index_valid = false;
+    ctx->n_seq_records = ctx->n_seq_name_bytes = 0;
+    ctx->seq_tm = rala_hip_ingest_timings();
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    Fd file;
+    file.fd = open(path, O_RDONLY);
+    if (file.fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+    struct stat st;
+    if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    const uint64_t file_n = (uint64_t)st.st_size;
+    // the window over the text: the overlap ingest's rule, and every count of a window in 32 bits
+    uint64_t window = (uint64_t)ctx->debug_sequence_window;
+    if (window == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        window = std::max<uint64_t>(256ull << 20, free_b / 4);
+    }
+    window = std::min<uint64_t>(window, 1ull << 31);
+    // a gzip file: BGZF is inflated on the device, anything else is the host reader's - known from the first 18 bytes
+    std::unique_ptr<BgzfFile> bg;
+    uint8_t head[18] = {0};
+    const ssize_t got = pread(file.fd, head, sizeof(head), 0);
+    if (got >= 2 && head[0] == 0x1f && head[1] == 0x8b) {
+        bool valid = bgzf_head(head, (uint64_t)got);
+        if (valid) {
+            bg.reset(new BgzfFile);
+            const int rc = bgzf_open(ctx, path, threads, window, *bg, &valid);
+            if (rc != RALA_HIP_OK) { ctx->d_bgzf_comp.release(); return rc; }
+        }
+        if (!valid) {
+            ctx->d_bgzf_comp.release();
+            *irregular = 8;
+            return RALA_HIP_OK;
+        }
+    }
+    SequenceRun R;
+    R.fastq = format == 1;
+    R.text_n = bg ? bg->text_n : file_n;
+    hipStream_t s = ctx->stream;
+    const uint64_t tile = sequence_tile_bytes();
+    double ship_ms = bg ? bg->ship_ms : 0, kernel_ms = 0;
+    uint32_t flags = 0;
+    int rc = RALA_HIP_OK;
+    for (uint64_t lo = 0; lo < R.text_n && rc == RALA_HIP_OK && !flags; lo += window) {
+        const uint64_t n = std::min(window, R.text_n - lo);
+        const uint64_t n_avail = std::min<uint64_t>(R.text_n - lo, n + sequence_halo_bytes());
+        const uint64_t cap = (n + tile - 1) / tile * tile + sequence_halo_bytes() + 64;
+        const uint8_t* text = nullptr;
+        const double t0 = now_ms();
+        double t1 = t0;
+        // what lies behind the text reads as zeros: a carriage return in the text's last byte is a base, as on the host
+        if (bg) {
+            BgzfText bt;
+            rc = bgzf_text_range(ctx, *bg, lo, n_avail, cap, 0, threads, []() { return true; }, "device memory", &bt);
+            if (rc != RALA_HIP_OK) break;
+            if (bt.flag) { flags = 8; break; }
+            text = bt.text;
+            t1 = bt.t1;
+            ship_ms += bt.t_ship - bt.t0;
+        } else {
+            if (ctx->d_paf_text.ensure(cap) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text"); break; }
+            if (hipMemsetAsync(ctx->d_paf_text.p + n_avail, 0, cap - n_avail, s) != hipSuccess ||
+                ship_file(file.fd, lo, n_avail, ctx->d_paf_text.p, ctx->device, threads, nullptr, []() { return true; }, nullptr) ||
+                hipStreamSynchronize(s) != hipSuccess) {
+                rc = ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+                break;
+            }
+            text = ctx->d_paf_text.p;
+            t1 = now_ms();
+            ship_ms += t1 - t0;
+        }
+        rc = index_window(ctx, R, text, lo, n, n_avail, &flags);
+        kernel_ms += now_ms() - t1;
+    }
+    ctx->d_paf_text.release();                  // (a window of the file: not kept)
+    ctx->d_bgzf_comp.release();
+    if (rc != RALA_HIP_OK) return rc;
+    if (!flags && R.fastq && (R.n_events & 3u) != 0) flags = kSeqNotFourLines;       // a record cut after 1, 2 or 3 lines
+    const double tf = now_ms();
+    std::vector<uint32_t> length(R.n_records);
+    if (!flags && R.n_records) {
+        if (ctx->d_seq_span.ensure(R.n_records) != hipSuccess || ctx->d_seq_length.ensure(R.n_records) != hipSuccess) {
+            return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
+        }
+        SequenceColumns C;
+        C.event_pos = ctx->d_seq_event[0].p; C.event_stripped = ctx->d_seq_event[1].p;
+        C.name_pos = ctx->d_seq_name_pos.p; C.name_len = ctx->d_seq_name_len.p;
+        C.data_off = ctx->d_seq_data_off.p; C.data_stripped = ctx->d_seq_data_stripped.p;
+        INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+        launch_sequence_finish(R.n_records, R.n_events, R.text_n, R.n_stripped, R.fastq, C, ctx->d_seq_span.p, ctx->d_seq_length.p, ctx->d_seq_flags.p, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipMemcpyAsync(length.data(), ctx->d_seq_length.p, R.n_records * 4, hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipStreamSynchronize(s));
+    }
+    kernel_ms += now_ms() - tf;
+    ctx->seq_tm.ship_ms = (float)ship_ms;
+    ctx->seq_tm.tokenize_ms = (float)kernel_ms;
+    ctx->seq_tm.bytes = R.text_n;
+    ctx->seq_tm.lines = R.n_records;
+    if (getenv("RALA_HIP_TRACE")) {
+        fprintf(stderr, "[trace] device sequence index: %.2f GB of text shipped in %.1f ms, %lu records indexed in %.2f ms (flags %u)\n", R.text_n / 1e9,
+                ship_ms, (unsigned long)R.n_records, kernel_ms, flags);
+    }
+    if (flags & kSeqTooLong) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "a sequence of 2^32 bases or more");
+    if (flags) {
+        *irregular = (int)flags;
+        return RALA_HIP_OK;
+    }
+    // the lengths are the context's reads from here on
+    const int rcr = rala_hip_set_reads(ctx, length.data(), R.n_records);
+    if (rcr != RALA_HIP_OK) return rcr;
+    ctx->n_seq_records = R.n_records;
+    ctx->n_seq_name_bytes = R.name_bytes;
+    ctx->seq_index_valid = true;
+    *n_records = R.n_records;
+    *name_bytes = R.name_bytes;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_sequence_index(rala_hip_ctx* ctx, uint64_t* name_off, uint32_t* name_len, uint64_t* data_off, uint64_t* data_span,
+                                uint32_t* length, char* names) {
+    if (!ctx) return RALA_HIP_EINVAL;
+    if (!ctx->seq_index_valid) return ingest_fail(ctx, RALA_HIP_EINVAL, "no sequence index (rala_hip_index_sequences)");
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    const uint64_t n = ctx->n_seq_records;
+    if (n && name_off) INGEST_CHECK(hipMemcpy(name_off, ctx->d_seq_name_off.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && name_len) INGEST_CHECK(hipMemcpy(name_len, ctx->d_seq_name_len.p, n * 4, hipMemcpyDeviceToHost));
+    if (n && data_off) INGEST_CHECK(hipMemcpy(data_off, ctx->d_seq_data_off.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && data_span) INGEST_CHECK(hipMemcpy(data_span, ctx->d_seq_span.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && length) INGEST_CHECK(hipMemcpy(length, ctx->d_seq_length.p, n * 4, hipMemcpyDeviceToHost));
+    if (ctx->n_seq_name_bytes && names) INGEST_CHECK(hipMemcpy(names, ctx->d_seq_arena.p, ctx->n_seq_name_bytes, hipMemcpyDeviceToHost));
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->seq_tm;
     return RALA_HIP_OK;
 }
 

@@ -498,6 +498,46 @@ void launch_paf_parse(const uint8_t* text, uint64_t n, uint64_t n_avail, bool fi
                       uint64_t n_buckets, const char* arena, const uint32_t* read_len, uint32_t n_reads, bool check_lengths,
                       const PafColumns& out, uint32_t* flags, unsigned long long* first_bad, hipStream_t s, bool mhap = false);
 
+// ---- FASTA / FASTQ text -> the sequence index (sequence_kernels.hip) -------------------------
+// why a file is not indexed here (rala_hip_index_sequences' *irregular; 8 is the inflater's, as for the overlaps)
+constexpr uint32_t kSeqNotFourLines = 1;        // FASTQ that is not four lines per record
+constexpr uint32_t kSeqLongName = 2;            // a name of more than 1024 bytes
+constexpr uint32_t kSeqHeaderBeyondHalo = 4;    // a header line that does not end within sequence_halo_bytes()
+constexpr uint32_t kSeqTooLong = 16;            // (not irregular: RALA_HIP_ETOOLARGE) a read of 2^32 bases or more
+uint32_t sequence_tile_bytes();
+uint32_t sequence_halo_bytes();
+// One window of the text: the n bytes whose events (FASTA: record starts, FASTQ: line starts) are this launch's, n_avail >= n
+// bytes of text readable for the header lines that start among them, zeros behind those up to the next multiple of
+// sequence_tile_bytes() + 64; text_off: where byte 0 lies in the whole text of text_n bytes; first_is_start: the byte in front
+// of byte 0 is a newline (or there is none); tile_event0 / tile_stripped0: the exclusive scans of launch_sequence_count's
+// counts; event0 / stripped0: the events and the stripped bytes of the windows in front of this one
+struct SequenceWindow {
+    const uint8_t* text;
+    uint64_t n, n_avail, text_off, text_n;
+    uint32_t first_is_start;
+    const uint32_t *tile_event0, *tile_stripped0;
+    uint64_t event0, stripped0;
+};
+// per event: its text offset, the stripped bytes in front of it; per record: where its name lies in the text, the name's
+// length, the first byte behind its header line and the stripped bytes in front of that
+struct SequenceColumns {
+    uint64_t *event_pos, *event_stripped;
+    uint64_t* name_pos;
+    uint32_t* name_len;
+    uint64_t *data_off, *data_stripped;
+};
+void launch_sequence_count(const uint8_t* text, uint64_t n, bool first_is_start, bool fastq, uint32_t* tile_events, uint32_t* tile_stripped,
+                           hipStream_t s);
+void launch_sequence_records(const SequenceWindow& W, bool fastq, const SequenceColumns& out, uint32_t* flags, hipStream_t s);
+// the names of n records of the window into arena + arena_off, in record order (name_at: the exclusive scan of name_len);
+// name_off[i] = where record i's name begins in the arena
+void launch_sequence_names(const uint8_t* text, uint64_t text_off, const uint64_t* name_pos, const uint32_t* name_len, const uint32_t* name_at,
+                           uint64_t n, uint64_t arena_off, uint8_t* arena, uint64_t* name_off, hipStream_t s);
+// behind the last window: data_off (FASTQ: written here), data_span and length of every record from neighbouring events;
+// flags: kSeqNotFourLines (a quality line of another length than its bases), kSeqTooLong
+void launch_sequence_finish(uint64_t n_records, uint64_t n_events, uint64_t text_n, uint64_t stripped_n, bool fastq, const SequenceColumns& c,
+                            uint64_t* data_span, uint32_t* length, uint32_t* flags, hipStream_t s);
+
 // ---- BGZF members -> text (inflate_kernels.hip) ---------------------------------------------
 // one gzip member of a BGZF file: its raw-deflate bytes at comp + comp_off (deflate_len of them, then CRC32 and ISIZE), its
 // text (isize bytes, 1 .. 65536) to text + text_off

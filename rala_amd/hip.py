@@ -33,6 +33,7 @@ SYMBOLS = (
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
     "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
+    "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
     "rala_hip_mg_destroy", "rala_hip_mg_last_error", "rala_hip_mg_set_reads", "rala_hip_mg_slice_cuts",
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
     "rala_hip_mg_owner_context",
@@ -67,6 +68,14 @@ class Timings(ctypes.Structure):
 class MgTimings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("emit_ms", "exchange_ms", "owner_ms", "gather_ms", "construct_ms",
                                               "repeats_ms", "tr_ms", "total_ms")] + [("tuples_sent", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class IngestTimings(ctypes.Structure):
+    """rala_hip_ingest_timings"""
+    _fields_ = [("ship_ms", ctypes.c_float), ("tokenize_ms", ctypes.c_float), ("bytes", ctypes.c_uint64), ("lines", ctypes.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -157,6 +166,9 @@ def lib(build=True):
         L.rala_hip_mg_get_timings.argtypes = [vp, ctypes.POINTER(MgTimings)]
         L.rala_hip_get_gzip_timings.argtypes = [vp, ctypes.POINTER(GzipTimings)]
         L.rala_hip_gzip_head.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i32)]
+        L.rala_hip_index_sequences.argtypes = [vp, ctypes.c_char_p, i32, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32)]
+        L.rala_hip_get_sequence_index.argtypes = [vp] + [vp] * 6
+        L.rala_hip_get_sequence_timings.argtypes = [vp, ctypes.POINTER(IngestTimings)]
         _lib = L
     return _lib
 
@@ -295,6 +307,29 @@ class Context:
         self.read_len = rl
         self.n_reads = int(rl.shape[0])
         self._check(self.L.rala_hip_set_reads(self.h, rl.ctypes.data, self.n_reads))
+
+    def index_sequences(self, path, fastq=False, threads=4):
+        """rala_hip_index_sequences + rala_hip_get_sequence_index -> (irregular, index); index (None when irregular): names (list of
+        bytes), length, data_off, data_span.  The lengths are the context's reads afterwards."""
+        n, nb, irregular = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        self._check(self.L.rala_hip_index_sequences(self.h, os.fsencode(path), 1 if fastq else 0, threads, ctypes.byref(n), ctypes.byref(nb),
+                                                    ctypes.byref(irregular)))
+        if irregular.value:
+            return irregular.value, None
+        name_off, data_off, data_span = (np.zeros(n.value, dtype=np.uint64) for _ in range(3))
+        name_len, length = (np.zeros(n.value, dtype=np.uint32) for _ in range(2))
+        arena = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        self._check(self.L.rala_hip_get_sequence_index(self.h, name_off.ctypes.data, name_len.ctypes.data, data_off.ctypes.data,
+                                                       data_span.ctypes.data, length.ctypes.data, arena.ctypes.data))
+        raw = arena.tobytes()
+        names = [raw[int(o):int(o) + int(k)] for o, k in zip(name_off, name_len)]
+        self.n_reads = n.value
+        return 0, {"names": names, "name_off": name_off, "length": length, "data_off": data_off, "data_span": data_span}
+
+    def sequence_timings(self):
+        t = IngestTimings()
+        self._check(self.L.rala_hip_get_sequence_timings(self.h, ctypes.byref(t)))
+        return t.as_dict()
 
     def set_overlaps(self, ov, later=False):
         """later: RALA_HIP_MEM_HOST_ASYNC - the columns (page-locked, valid until initialize() has returned) are uploaded by

@@ -1,8 +1,11 @@
 #include "graph.hpp"
 
+#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -246,10 +249,62 @@ void read_overlaps(const std::string& path, const std::unordered_map<std::string
 
 }  // namespace
 
+// The read file indexed on the device (rala_hip_index_sequences; reference src/graph.cpp:249-264): names_, read_len_ and
+// name_to_id_ from the index, which is kept for construct()'s second pass.  false: the switch is off, or the file is one the
+// device does not take (irregular, a plain gzip file, a FIFO, no room) - the host reader then does what it always did.
+bool Graph::index_sequences() {
+    if (!io::device_sequences_wanted()) return false;
+    const bool fastq = io::has_suffix(sequences_path_, ".fastq") || io::has_suffix(sequences_path_, ".fq") ||
+                       io::has_suffix(sequences_path_, ".fastq.gz") || io::has_suffix(sequences_path_, ".fq.gz");
+    uint64_t n = 0, name_bytes = 0;
+    int irregular = 0;
+    // (several GPUs: the main context indexes the file; rala_hip_mg_set_reads receives the lengths as always)
+    const int rc = rala_hip_index_sequences(ctx_, sequences_path_.c_str(), fastq ? 1 : 0, std::max(1u, num_threads_), &n, &name_bytes, &irregular);
+    if (rc != RALA_HIP_OK || irregular) return false;
+    std::vector<uint64_t> name_off(n);
+    std::vector<uint32_t> name_len(n);
+    std::string arena(name_bytes, '\0');
+    io::SequenceIndex& ix = sequence_index_;
+    ix.data_off.resize(n); ix.data_span.resize(n); ix.length.resize(n);
+    check(ctx_, rala_hip_get_sequence_index(ctx_, name_off.data(), name_len.data(), ix.data_off.data(), ix.data_span.data(), ix.length.data(),
+                                            &arena[0]), "initialize");
+    // a BGZF file: where its members lie, for the second pass
+    if (io::has_suffix(sequences_path_, ".gz")) {
+        bool ok = false;
+        const int fd = open(sequences_path_.c_str(), O_RDONLY);
+        struct stat st;
+        if (fd >= 0 && fstat(fd, &st) == 0 && st.st_size > 0) {
+            void* map = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (map != MAP_FAILED) {
+                uint64_t members = 0;
+                int valid = 0;
+                rala_hip_bgzf_index((const uint8_t*)map, (uint64_t)st.st_size, 0, 0, &members, nullptr, nullptr, nullptr, nullptr, &valid);
+                if (valid) {
+                    ix.member_off.resize(members); ix.member_text_off.resize(members);
+                    ix.member_bytes.resize(members); ix.member_text_bytes.resize(members);
+                    rala_hip_bgzf_index((const uint8_t*)map, (uint64_t)st.st_size, 0, members, &members, ix.member_off.data(), ix.member_bytes.data(),
+                                        ix.member_text_bytes.data(), ix.member_text_off.data(), &valid);
+                    ok = valid != 0;
+                }
+                munmap(map, (size_t)st.st_size);
+            }
+        }
+        if (fd >= 0) close(fd);
+        if (!ok) { sequence_index_ = io::SequenceIndex(); return false; }
+    }
+    names_.reserve(n);
+    read_len_ = ix.length;
+    for (uint64_t i = 0; i < n; ++i) {
+        names_.emplace_back(arena.data() + name_off[i], name_len[i]);
+        name_to_id_[names_.back()] = i;
+    }
+    return true;
+}
+
 // reference src/graph.cpp:244-425
 void Graph::initialize() {
     StageTimer timer;
-    if (!read_sequences(sequences_path_, [&](const std::string& name, const std::string& data) {
+    if (!index_sequences() && !read_sequences(sequences_path_, [&](const std::string& name, const std::string& data) {
             name_to_id_[name] = names_.size();
             names_.push_back(name);
             read_len_.push_back((uint32_t)data.size());
@@ -552,16 +607,28 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
     for (uint64_t k = 0; k < n_nodes; k += 2) read_to_node[node_read[k]] = (int64_t)k;
     // nodes in read order (graph.cpp:553-574): collect the trimmed sequences first
     std::vector<std::string> node_name(n_nodes / 2), node_data(n_nodes / 2), node_rc(n_nodes / 2);
-    uint64_t seq_id = 0;
-    read_sequences(sequences_path_, [&](const std::string& name, const std::string& data) {
-        const uint64_t i = seq_id++;
-        if (i >= n || read_to_node[i] < 0) return;
+    auto keep = [&](uint64_t i, const std::string& name, const std::string& data) {
         auto seq = createSequence(name, data);
         seq->trim(begin[i], end[i]);
         const uint64_t k = (uint64_t)read_to_node[i] / 2;
         node_name[k] = name;
         node_data[k] = seq->data();
         node_rc[k] = seq->reverse_complement();
+    };
+    bool sliced = false;
+    if (!sequence_index_.empty()) {
+        // the device indexed the file: the bases of the reads the graph keeps are cut out of it, nothing is parsed again
+        std::vector<uint64_t> wanted;
+        for (uint64_t i = 0; i < n; ++i) if (read_to_node[i] >= 0) wanted.push_back(i);
+        std::vector<std::string> bases;
+        sliced = io::slice_sequences(sequences_path_, sequence_index_, wanted, std::max(1u, num_threads_), bases);
+        for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], names_[wanted[w]], bases[w]);
+    }
+    uint64_t seq_id = 0;
+    if (!sliced) read_sequences(sequences_path_, [&](const std::string& name, const std::string& data) {
+        const uint64_t i = seq_id++;
+        if (i >= n || read_to_node[i] < 0) return;
+        keep(i, name, data);
     });
     for (uint64_t k = 0; k < n_nodes / 2; ++k) {
         graph_.add_sequence_nodes(node_read[2 * k], node_name[k], node_data[k], node_rc[k]);

@@ -87,6 +87,8 @@ private:
     std::vector<std::unique_ptr<Pile>> piles_;
     io::NameTable name_table_;
     io::OverlapColumns overlaps_;       // parsed once
+    io::SequenceIndex sequence_index_;  // where the reads' bases lie in the file (the device indexed it; empty: the host reader did)
+    bool index_sequences();
 
     AssemblyGraph graph_;
     uint32_t layout_seed_ = 0;          // one fixed seed per layout round

@@ -72,6 +72,11 @@ bool device_gzip_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool device_sequences_wanted() {
+    const char* e = getenv("RALA_DEVICE_SEQUENCES");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool read_fasta(const std::string& path, const SequenceSink& sink) {
     Lines in(path);
     if (!in.ok()) return false;
@@ -189,6 +194,8 @@ bool read_mhap(const std::string& path, const std::function<void(const MhapRecor
 #include <mutex>
 #include <new>
 #include <thread>
+
+#include "thread_pool/thread_pool.hpp"
 
 namespace rala {
 namespace io {
@@ -835,6 +842,28 @@ struct BlockColumns {
     int64_t error_read = -1;
 };
 
+// the deflate stream, CRC32 and ISIZE of one BGZF member (n bytes) -> its text (none for the end-of-file marker); false: not
+// what the trailer promises
+bool inflate_member(const unsigned char* comp, size_t n, std::vector<char>& out) {
+    out.clear();
+    if (n < 8) return false;
+    const unsigned char* tail = comp + n - 8;
+    const uint32_t crc = tail[0] | (uint32_t)tail[1] << 8 | (uint32_t)tail[2] << 16 | (uint32_t)tail[3] << 24;
+    const uint32_t isize = tail[4] | (uint32_t)tail[5] << 8 | (uint32_t)tail[6] << 16 | (uint32_t)tail[7] << 24;
+    if (isize > (1u << 16)) return false;
+    if (isize == 0) return true;                             // (the end-of-file marker; nothing to inflate into)
+    out.resize(isize);
+    z_stream z;
+    memset(&z, 0, sizeof(z));
+    if (inflateInit2(&z, -15) != Z_OK) return false;
+    z.next_in = (Bytef*)comp; z.avail_in = (uInt)(n - 8);
+    z.next_out = (Bytef*)out.data(); z.avail_out = isize;
+    const int rc = inflate(&z, Z_FINISH);
+    const bool ok = rc == Z_STREAM_END && z.avail_out == 0;
+    inflateEnd(&z);
+    return ok && (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)out.data(), isize) == crc;
+}
+
 // A BGZF file (bgzip, htslib: a series of gzip members of at most 64 KB, each with its compressed size in a "BC" extra
 // field - RFC 1952 plus the SAM specification, section 4.1) inflated by several threads: the blocks are read in file order,
 // handed to the inflaters, and given out in file order again.  A plain gzip stream has one member and nothing to split; the
@@ -921,25 +950,7 @@ private:
         return 1;
     }
     static void inflate_block(Job& j) {
-        const size_t n = j.comp.size();
-        const unsigned char* tail = j.comp.data() + n - 8;
-        const uint32_t crc = tail[0] | (uint32_t)tail[1] << 8 | (uint32_t)tail[2] << 16 | (uint32_t)tail[3] << 24;
-        const uint32_t isize = tail[4] | (uint32_t)tail[5] << 8 | (uint32_t)tail[6] << 16 | (uint32_t)tail[7] << 24;
-        if (isize > (1u << 16)) { j.bad = true; return; }
-        if (isize == 0) {                                    // (the end-of-file marker; nothing to inflate into)
-            std::vector<unsigned char>().swap(j.comp);
-            return;
-        }
-        j.out.resize(isize);
-        z_stream z;
-        memset(&z, 0, sizeof(z));
-        if (inflateInit2(&z, -15) != Z_OK) { j.bad = true; return; }
-        z.next_in = j.comp.data(); z.avail_in = (uInt)(n - 8);
-        z.next_out = (Bytef*)j.out.data(); z.avail_out = isize;
-        const int rc = inflate(&z, Z_FINISH);
-        const bool ok = rc == Z_STREAM_END && z.avail_out == 0;
-        inflateEnd(&z);
-        if (!ok || (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)j.out.data(), isize) != crc) j.bad = true;
+        if (!inflate_member(j.comp.data(), j.comp.size(), j.out)) j.bad = true;
         std::vector<unsigned char>().swap(j.comp);
     }
     void work() {
@@ -971,6 +982,107 @@ private:
 };
 
 }  // namespace
+
+// ---- the second pass over the read file, from the device's sequence index ----------------------
+namespace {
+
+// what Lines::next takes out of the text, piece by piece: every newline, and a carriage return directly in front of one
+// (the one that ends a piece waits for the next piece's first byte)
+struct Stripper {
+    std::string& dst;
+    bool pending_cr = false;
+    void feed(const char* b, const char* e) {
+        while (b < e) {
+            if (pending_cr) {
+                if (*b != '\n') dst.push_back('\r');
+                pending_cr = false;
+            }
+            const char* nl = (const char*)memchr(b, '\n', (size_t)(e - b));
+            const char* last = nl ? nl : e;
+            if (last > b && last[-1] == '\r') {
+                --last;
+                pending_cr = nl == nullptr;
+            }
+            dst.append(b, last);
+            b = nl ? nl + 1 : e;
+        }
+    }
+    void finish() {
+        if (pending_cr) dst.push_back('\r');
+        pending_cr = false;
+    }
+};
+
+}  // namespace
+
+bool slice_sequences(const std::string& path, const SequenceIndex& index, const std::vector<uint64_t>& wanted, uint32_t num_threads,
+    std::vector<std::string>& out) {
+    out.assign(wanted.size(), std::string());
+    if (wanted.empty()) return true;
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return false;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || st.st_size <= 0) { close(fd); return false; }
+    const size_t file_n = (size_t)st.st_size;
+    void* map = mmap(nullptr, file_n, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (map == MAP_FAILED) return false;
+    const char* const base = (const char*)map;
+    const bool bgzf = !index.member_off.empty();
+    const size_t n_members = index.member_off.size();
+    // reads [k0, k1) of `wanted`; a BGZF file: the members in file order, each inflated once per task, when a wanted read
+    // reaches into it
+    auto task = [&](size_t k0, size_t k1) -> bool {
+        std::vector<char> text;
+        size_t have = ~(size_t)0;
+        for (size_t k = k0; k < k1; ++k) {
+            const uint64_t r = wanted[k];
+            if (r >= index.data_off.size()) return false;
+            uint64_t pos = index.data_off[r];
+            const uint64_t end = pos + index.data_span[r];
+            std::string& dst = out[k];
+            dst.reserve(index.length[r]);
+            Stripper strip{dst};
+            if (!bgzf) {
+                if (end > file_n || end < pos) return false;
+                strip.feed(base + pos, base + end);
+            } else {
+                size_t m = (size_t)(std::upper_bound(index.member_text_off.begin(), index.member_text_off.end(), pos) -
+                                    index.member_text_off.begin());
+                m = m ? m - 1 : 0;
+                while (pos < end) {
+                    while (m < n_members && index.member_text_off[m] + index.member_text_bytes[m] <= pos) ++m;
+                    if (m >= n_members) return false;
+                    if (m != have) {
+                        const uint64_t off = index.member_off[m], bytes = index.member_bytes[m];
+                        if (off + bytes > file_n || bytes < 20) return false;
+                        const unsigned char* h = (const unsigned char*)base + off;
+                        const size_t hdr = 12 + (h[10] | (size_t)h[11] << 8);
+                        if (hdr + 8 > bytes || !inflate_member(h + hdr, bytes - hdr, text) || text.size() != index.member_text_bytes[m]) return false;
+                        have = m;
+                    }
+                    const uint64_t t0 = index.member_text_off[m];
+                    const uint64_t stop = std::min<uint64_t>(end, t0 + text.size());
+                    strip.feed(text.data() + (pos - t0), text.data() + (stop - t0));
+                    pos = stop;
+                }
+            }
+            strip.finish();
+            if (dst.size() != index.length[r]) return false;
+        }
+        return true;
+    };
+    auto pool = thread_pool::createThreadPool(std::max(1u, num_threads));
+    const size_t n_tasks = std::min<size_t>(wanted.size(), (size_t)pool->num_threads() * 8);
+    std::vector<std::future<bool>> done;
+    for (size_t t = 0; t < n_tasks; ++t) {
+        done.emplace_back(pool->submit_task(task, wanted.size() * t / n_tasks, wanted.size() * (t + 1) / n_tasks));
+    }
+    bool ok = true;
+    for (auto& f : done) { f.wait(); ok = f.get() && ok; }
+    munmap(map, file_n);
+    return ok;
+}
 
 bool read_overlaps_streamed(const std::string& path, bool mhap, const NameTable& names, const std::vector<uint32_t>& read_len,
     bool check_lengths, uint32_t num_threads, OverlapColumns& out, int64_t* length_error) {

@@ -38,6 +38,29 @@ bool has_suffix(const std::string& src, const std::string& suffix);
  * says so, read where the file is opened; without it: no - see README.md, "Compressed overlap files", for what was measured */
 bool device_gzip_wanted();
 
+/*! @brief is the read file indexed on the device (rala_hip_index_sequences) and its second pass cut out of the file with that
+ * index?  RALA_DEVICE_SEQUENCES=1 / =0 says so, read where the file is opened; without it: no - see README.md, "Compressed
+ * overlap files", for what was measured */
+bool device_sequences_wanted();
+
+// ---- the second pass over the read file, from the device's sequence index ----------------------
+// Where every read's bases lie (rala_hip_get_sequence_index): the text [data_off, data_off + data_span) with every newline
+// and every carriage return in front of one taken out, `length` bases.  A BGZF file: offsets are offsets into its text, and
+// the members' file offsets, sizes (BSIZE + 1), text sizes and text offsets (rala_hip_bgzf_index's arrays) say where that
+// text lies; a plain file has none.
+struct SequenceIndex {
+    std::vector<uint64_t> data_off, data_span;
+    std::vector<uint32_t> length;
+    std::vector<uint64_t> member_off, member_text_off;
+    std::vector<uint32_t> member_bytes, member_text_bytes;
+    bool empty() const { return data_off.empty(); }
+};
+// out[k] = the bases of read wanted[k] (ascending), as read_fasta / read_fastq hand them to their sink: the file is mapped,
+// num_threads threads copy the spans - of a BGZF file after inflating the members that cover them, and no others.
+// false: the file cannot be mapped, or is not what the index describes.
+bool slice_sequences(const std::string& path, const SequenceIndex& index, const std::vector<uint64_t>& wanted, uint32_t num_threads,
+    std::vector<std::string>& out);
+
 // ---- one-pass, multi-threaded ingest of an uncompressed PAF file into binary columns -------
 // (the reference tokenises every line into a heap Overlap twice,
 // src/graph.cpp:328,443)

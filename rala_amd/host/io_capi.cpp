@@ -1,5 +1,6 @@
 // C surface of the overlap readers for the CPU test-suite (tests/test_ingest_cpu.py): the
-// multi-threaded PAF reader against the line-by-line one.  Not part of the product boundary.
+// multi-threaded PAF reader against the line-by-line one; and of the sequence readers (tests/test_sequences_cpu.py,
+// tests/test_gpu_sequences.py): what read_fasta / read_fastq give, and the second pass's slicer.  Not part of the product boundary.
 #include <stdint.h>
 #include <string.h>
 
@@ -12,6 +13,20 @@
 #include "io.hpp"
 
 namespace {
+
+// FNV-1a-64
+uint64_t hash_of(const std::string& s) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (unsigned char c : s) h = (h ^ c) * 0x100000001b3ull;
+    return h;
+}
+
+struct Sequences {
+    std::string names;                  // one behind the other
+    std::vector<uint32_t> name_len, length;
+    std::vector<uint64_t> hash;         // of each read's bases
+    bool ok = false;
+};
 
 struct Parsed {
     rala::io::OverlapColumns cols;
@@ -92,5 +107,54 @@ void io_paf_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uin
     memcpy(length, c.length.data(), n * 4); memcpy(strand, c.strand.data(), n);
 }
 void io_paf_free(void* h) { delete (Parsed*)h; }
+
+// io::read_fasta (fastq = 0) / io::read_fastq (1): per record the name, the number of bases and a hash of them
+void* io_seq_parse(const char* path, int fastq) {
+    auto* out = new Sequences();
+    auto sink = [&](const std::string& name, const std::string& data) {
+        out->names += name;
+        out->name_len.push_back((uint32_t)name.size());
+        out->length.push_back((uint32_t)data.size());
+        out->hash.push_back(hash_of(data));
+    };
+    out->ok = fastq ? rala::io::read_fastq(path, sink) : rala::io::read_fasta(path, sink);
+    return out;
+}
+int io_seq_ok(void* h) { return ((Sequences*)h)->ok; }
+uint64_t io_seq_size(void* h) { return ((Sequences*)h)->length.size(); }
+uint64_t io_seq_name_bytes(void* h) { return ((Sequences*)h)->names.size(); }
+void io_seq_copy(void* h, char* names, uint32_t* name_len, uint32_t* length, uint64_t* hash) {
+    const auto& q = *(Sequences*)h;
+    memcpy(names, q.names.data(), q.names.size());
+    memcpy(name_len, q.name_len.data(), q.name_len.size() * 4);
+    memcpy(length, q.length.data(), q.length.size() * 4);
+    memcpy(hash, q.hash.data(), q.hash.size() * 8);
+}
+void io_seq_free(void* h) { delete (Sequences*)h; }
+
+// io::slice_sequences with an index of n records (n_members BGZF members, 0: a plain file): the hash and the number of
+// bases of every wanted read; 1 = ok
+int io_seq_slice(const char* path, uint64_t n, const uint64_t* data_off, const uint64_t* data_span, const uint32_t* length,
+                 uint64_t n_members, const uint64_t* member_off, const uint32_t* member_bytes, const uint32_t* member_text_bytes,
+                 const uint64_t* member_text_off, const uint64_t* wanted, uint64_t n_wanted, uint32_t threads, uint64_t* hash,
+                 uint32_t* bases) {
+    rala::io::SequenceIndex ix;
+    ix.data_off.assign(data_off, data_off + n);
+    ix.data_span.assign(data_span, data_span + n);
+    ix.length.assign(length, length + n);
+    if (n_members) {
+        ix.member_off.assign(member_off, member_off + n_members);
+        ix.member_bytes.assign(member_bytes, member_bytes + n_members);
+        ix.member_text_bytes.assign(member_text_bytes, member_text_bytes + n_members);
+        ix.member_text_off.assign(member_text_off, member_text_off + n_members);
+    }
+    std::vector<std::string> out;
+    if (!rala::io::slice_sequences(path, ix, std::vector<uint64_t>(wanted, wanted + n_wanted), threads, out)) return 0;
+    for (uint64_t k = 0; k < n_wanted; ++k) {
+        hash[k] = hash_of(out[k]);
+        bases[k] = (uint32_t)out[k].size();
+    }
+    return 1;
+}
 
 }  // extern "C"
