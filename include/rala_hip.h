@@ -105,6 +105,12 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * 12 .. 14; 0 = by the rule - 4096 reads, more where that would make more than 256 partitions),
  * "pile_chunk_mb" (default 1024: the rows of all piles lie in physical chunks of this many MB mapped side by side into one range -
  * hipMemCreate / hipMemMap - which the first pile kernel's stores like better than where one hipMalloc puts them; 0 = one hipMalloc),
+ * "pile_rows" (default 1: the coverage rows of all piles are resident, 2 bytes per base; 0, read by the next rala_hip_initialize:
+ * no row is allocated or stored - a row is a pure function of the read's bound events, which stay on the device anyway, and is
+ * rebuilt from them whenever a getter or the sensitive pass asks; every call answers what it answers with 1, except that
+ * rala_hip_get_pile_row_digests' `outside` is 0, and one rala_hip_initialize takes one sensitive construct - see
+ * rala_hip_get_pile_rows_info), "pile_rows_scratch_mb" (default 256: with pile_rows = 0, the device memory a batch of rebuilt rows
+ * may take; it grows to the longest single row),
  * "debug_chunk_fail" (tests: the mapping of those chunks fails at chunk k, and the rows come from one hipMalloc; -1, the default: never),
  * "debug_count_window" (tests: the partitioned bucketing counts this many groups of 128 reads per pass over the ids;
  * 0 = what a workgroup's LDS holds, 38 400 - one pass up to 4.9 M reads),
@@ -441,6 +447,19 @@ int rala_hip_get_pile_data(rala_hip_ctx* ctx, uint64_t read, uint16_t* data);
  * [begin, end); outside[r] = the sum of the values STORED outside it (zero right after rala_hip_initialize; later stages narrow a
  * region without rewriting its row).  A filtered read answers 0 to all three. */
 int rala_hip_get_pile_row_digests(rala_hip_ctx* ctx, uint64_t* fnv, uint64_t* inside, uint64_t* outside);
+/* Where the rows are (option "pile_rows"; either pointer may be NULL).  resident_bytes: the size of the rows' allocation - at least
+ * 2 bytes per base of all reads with pile_rows = 1, 0 with pile_rows = 0.  rows_materialised: rows rebuilt from their events since
+ * the last rala_hip_initialize (always 0 with pile_rows = 1).
+ * With pile_rows = 0: rala_hip_get_pile_data rebuilds the one row; rala_hip_get_pile_row_digests walks all reads in batches of
+ * "pile_rows_scratch_mb" and hashes every batch where it was rebuilt - fnv and inside are what the resident rows give, outside is 0
+ * by definition (nothing is stored, so nothing is stored outside a region); the rala_hip_mg_ twins do the same on the owner
+ * contexts (rala_hip_mg_owner_context takes the options).  A rebuilt row is Pile::add_layers over the primary bounds and, after a
+ * construct with sensitive overlaps, a second one over the sensitive bounds of the targets: those bounds are kept until the next
+ * rala_hip_initialize (of a construct that failed they are not used), and rala_hip_construct refuses a second set of sensitive
+ * overlaps after one that succeeded on the same rala_hip_initialize (RALA_HIP_EINVAL) - where the rows are resident its layers
+ * would pile up on the first one's, here they would replace them; a sharded run initializes every time.  "debug_pile_stop_after"
+ * other than 99 is refused by rala_hip_initialize in this mode. */
+int rala_hip_get_pile_rows_info(rala_hip_ctx* ctx, uint64_t* resident_bytes, uint64_t* rows_materialised);
 /* Pits / hills / repeat hills of all reads as CSR: offsets[n_reads + 1], then pairs
  * (first, second) and one aux word per interval (pit: min coverage inside; hill:
  * spanning-overlap count; repeat hill: bridged flag).  kind: 0 pits, 1 hills, 2 repeat

@@ -304,6 +304,18 @@ struct rala_hip_ctx {
     // bound CSR
     rala_hip::DevBuf<uint32_t> d_ev_off, d_cursor, d_ev, d_slot_rank[2], d_ev_fixed;
     uint32_t pile_chunk_mb = 1024;      // the rows' buffer as physical chunks of this size (0: one hipMalloc) - pipeline.hip
+    // Rows on demand (option pile_rows = 0; pile_rows_kernel.hip): initialize allocates no rows and its kernels store none; a row
+    // is rebuilt from the read's events - which stay where initialize left them - into d_rows_scratch when somebody asks
+    uint32_t pile_rows = 1;             // the option (read by the next rala_hip_initialize)
+    uint32_t pile_rows_scratch_mb = 256;        // option: what a batch of rebuilt rows may take (grows to the longest row)
+    bool rowless = false;               // how the last rala_hip_initialize ran
+    bool sens_csr_ready = false;        // d_sens_off / d_sens_ev hold the bounds of a sensitive construct that SUCCEEDED since the last initialize
+    bool sens_pass_running = false;     // ... of the sensitive pass that is under way (its repeat-hill kernels read the rows with them on top)
+    uint64_t rows_materialised = 0;     // rows rebuilt since the last initialize
+    rala_hip::DevBuf<uint16_t> d_rows_scratch;
+    rala_hip::DevBuf<uint64_t> d_rows_off;      // per read: where its row lies in the scratch (valid for the reads of the last batch)
+    rala_hip::DevBuf<uint32_t> d_rows_list;
+    std::vector<uint64_t> h_rows_off;
     bool debug_ev_events = false;
     uint32_t ev_shift = 0;              // units of d_ev_off: 1 << ev_shift events (kernels.h: kBucketPairShift)
     rala_hip::DevBuf<unsigned char> d_scan_ws;

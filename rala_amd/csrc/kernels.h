@@ -29,7 +29,7 @@ struct PileArgs {
     // inputs
     const uint32_t* read_len;
     const uint64_t* pile_off;      // element offset of each pile row (rows padded to 8 elements)
-    uint16_t* pile;                // all piles, row after row
+    uint16_t* pile;                // all piles, row after row; null (option pile_rows = 0): the kernels store no row
     const uint32_t* ev_off;        // CSR of bound events per read (n_reads + 1), in units of 1 << ev_shift events
     const uint32_t* ev;            // pos << 1 | is_end
     const uint32_t* ev_cnt;        // non-null: fixed slots instead of the CSR - read r has ev_cnt[r] events
@@ -83,6 +83,28 @@ uint32_t pile_lds_bytes(uint32_t lw);
 uint32_t pile_lw_for(uint32_t read_len);
 uint64_t pile_big_words(uint32_t cap_reg, uint32_t cap_list, uint32_t cap_raw);    // per workgroup
 void launch_pile_build_annotate(const PileArgs& args, uint32_t grid, bool in_lds, hipStream_t stream);
+
+// Rows on demand (pile_rows_kernel.hip; option pile_rows = 0): the coverage row of every listed read rebuilt from its bound
+// events - Pile::add_layers over the primary events and, where sens_off is given, a second one over the sensitive bounds, mod
+// 2^16 - into rows + dst_off[read] (16-byte aligned, room for the length rounded up to 8 values; the padding is zero).  One
+// workgroup per read, the row in tiles of kRowsTile bases; any length, any number of events.
+constexpr uint32_t kRowsTile = 8192;
+struct RowsArgs {
+    const uint32_t* reads;         // the reads of this launch; null: first, first + 1, ...
+    uint32_t first;
+    uint32_t n_items;
+    const uint32_t* read_len;
+    const uint64_t* dst_off;       // indexed by read
+    uint16_t* rows;
+    const uint32_t* ev_off;        // the primary events as PileArgs has them: CSR in units of 1 << ev_shift events, or
+    const uint32_t* ev;
+    const uint32_t* ev_cnt;        // (non-null) fixed slots of ev_stride events
+    uint32_t ev_stride;
+    uint32_t ev_shift;
+    const uint32_t* sens_off;      // may be null: CSR of the sensitive bounds (in events)
+    const uint32_t* sens_ev;
+};
+void launch_pile_rows(const RowsArgs& args, hipStream_t stream);
 
 // verify_kernels.hip: per row FNV-1a-64 of Pile::data() (zero outside [begin, end)), the row's sum inside and the stored values' sum
 // outside the region; a dead read answers 0 to all three.  Any output may be null.

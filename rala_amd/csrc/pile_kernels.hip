@@ -49,7 +49,8 @@ uint64_t pile_big_words(uint32_t cap_reg, uint32_t cap_list, uint32_t cap_raw) {
 
 // kLds: big arrays in LDS (dynamic shared memory) or in a per-workgroup HBM slab.
 // kBig: the region lists and raw intervals in global memory (A.big_space), at the sizes the host chose.
-template <bool kLds, bool kBig>
+// kRows = false (option pile_rows = 0, PileArgs::pile null): the pile is not streamed to HBM; everything else as it is.
+template <bool kLds, bool kBig, bool kRows = true>
 __global__ __launch_bounds__(kBlock) void pile_build_annotate(PileArgs A) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void pile_build_annotate(PileArgs A) {
             int32_t total;
             int32_t run = block_scan_excl<kBlock>(s, OpAdd(), (int32_t)0, (int32_t*)tmp32, total);
             uint16_t* Dw = P + kPadL;
-            if (A.add_to_existing) {
+            if (kRows && A.add_to_existing) {
                 const uint16_t* old = A.pile + A.pile_off[r];
                 for (uint32_t j = lo; j < hi; ++j) {
                     run += diff[j];
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void pile_build_annotate(PileArgs A) {
             for (uint32_t j = E + tid; j < n; j += kBlock) Dw[j] = 0;
         }
         __syncthreads();
-        {
+        if constexpr (kRows) {
             uint4* dst = (uint4*)(A.pile + A.pile_off[r]);
             const uint4* src = (const uint4*)(P + kPadL);
             const uint32_t nv = (n + 7) / 8;        // pile rows are padded to 8 elements
@@ -491,6 +492,24 @@ __global__ __launch_bounds__(kBlock) void pile_build_annotate(PileArgs A) {
 void launch_pile_build_annotate(const PileArgs& args, uint32_t grid, bool in_lds, hipStream_t stream) {
     if (grid == 0) return;
     const bool big = args.big_space != nullptr;
+    if (!args.pile) {
+        // without rows (option pile_rows = 0)
+        if (in_lds) {
+            const uint32_t bytes = pile_lds_bytes(args.lw);
+            if (big) {
+                hipFuncSetAttribute((const void*)pile_build_annotate<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                hipLaunchKernelGGL((pile_build_annotate<true, true, false>), dim3(grid), dim3(kBlock), bytes, stream, args);
+            } else {
+                hipFuncSetAttribute((const void*)pile_build_annotate<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                hipLaunchKernelGGL((pile_build_annotate<true, false, false>), dim3(grid), dim3(kBlock), bytes, stream, args);
+            }
+        } else if (big) {
+            hipLaunchKernelGGL((pile_build_annotate<false, true, false>), dim3(grid), dim3(kBlock), SC_WORDS * 4u, stream, args);
+        } else {
+            hipLaunchKernelGGL((pile_build_annotate<false, false, false>), dim3(grid), dim3(kBlock), SC_WORDS * 4u, stream, args);
+        }
+        return;
+    }
     if (in_lds) {
         const uint32_t bytes = pile_lds_bytes(args.lw);
         if (big) {

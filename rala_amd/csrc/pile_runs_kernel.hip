@@ -639,7 +639,10 @@ __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t*
 // The others round 6 measured - s_nop pads, sleeps and work in front of the first load, one / four reads per workgroup, priorities,
 // non-temporal event loads, the XCC_ID probe, the expansion's look-ups one group ahead, XCDs taking chunks in turn - are a patch:
 // docs/history/experiments/r6_pile_kernel_variants.patch (their results: docs/history/r6_pile_kernel_notebook.md).
-template <uint32_t kCap, bool kDiag, int kSens, bool kOne = false, uint32_t kBases = 16384, uint32_t kWaves = 1, bool kPlain = false, uint32_t kVar = 0>
+// kRows = false (option pile_rows = 0, PileArgs::pile null): no row is stored - the expansion is left out at compile time, the
+// annotations are the same (rows on demand: pile_rows_kernel.hip).  The default is the kernel as it was.
+template <uint32_t kCap, bool kDiag, int kSens, bool kOne = false, uint32_t kBases = 16384, uint32_t kWaves = 1, bool kPlain = false, uint32_t kVar = 0,
+          bool kRows = true>
 __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases > 16384 ? 4 : 5) void pile_runs_kernel(PileArgs A, uint32_t* overflow_list, uint32_t* overflow_count) {
     static_assert(kWaves == 1 || kOne, "several reads per workgroup: the first kernel of a chain only");
     static_assert(kSens == 0 || !kDiag, "the sensitive pass has no diagnostic instantiation");
@@ -683,7 +686,7 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
 
     // diagnostics: 77 = everything but the row stores; 100 + k = leave after phase k, without them
     const uint32_t stop_k = A.stop_after >= 100 ? A.stop_after % 100 : A.stop_after;
-    const bool row_stores = !kDiag || !(A.stop_after == 77 || A.stop_after >= 100);
+    const bool row_stores = kRows && (!kDiag || !(A.stop_after == 77 || A.stop_after >= 100));
 #define RUN_STOP(k)                                                        \
     if (kDiag && stop_k == (k)) {                                          \
         if (lane == 0) A.alive[A.order ? A.order[item] : item] = 0;        \
@@ -1875,9 +1878,27 @@ void launch_pile_dense_list(const PileArgs& args, uint32_t n_reads, uint32_t* li
 // 4.07 - 4.10 ms, one 4.16, four 4.23 (docs/history/gpurun/r4_waves2.sh) - two.
 constexpr uint32_t kPileWavesPerGroup = 2;
 
+// the chain without rows (PileArgs::pile null): the same tiers with kRows = false
+static void launch_pile_runs_rowless(const PileArgs& args, uint32_t grid, int tier, uint32_t* overflow_list, uint32_t* overflow_count,
+                                     hipStream_t stream) {
+#define RALA_LAUNCH_ROWLESS(grid_, block_, ...)                                                                          \
+    hipLaunchKernelGGL((pile_runs_kernel<__VA_ARGS__, false>), dim3(grid_), dim3(block_), 0, stream, args, overflow_list, overflow_count)
+    if (tier == 0 && grid >= args.n_items && !args.n_items_dev) {
+        // (one workgroup per item; the product's shape - two reads per workgroup, XCD ranges - where the product takes it)
+        if (!args.order && !args.ev_cnt) RALA_LAUNCH_ROWLESS(8u * ((args.n_items + 15u) / 16u), 128, kRunEventCap, false, 0, true, 16384, 2, true, 0);
+        else RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, true, 16384, 1, false, 0);
+    } else if (tier == 3) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, false, 32768, 1, false, 0);
+    else if (tier == 0 || tier == 4) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, false, 16384, 1, false, 0);
+    else if (tier == 1) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCapMid, false, 0, false, 16384, 1, false, 0);
+    else RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCapBig, false, 0, false, 16384, 1, false, 0);
+#undef RALA_LAUNCH_ROWLESS
+}
+
 void launch_pile_runs(const PileArgs& args, uint32_t grid, int tier, uint32_t* overflow_list, uint32_t* overflow_count,
                       hipStream_t stream) {
     if (grid == 0) return;
+    // (without rows there is no diagnostic run: rala_hip_initialize refuses debug_pile_stop_after != 99 with pile_rows = 0)
+    if (!args.pile) { launch_pile_runs_rowless(args, grid, tier, overflow_list, overflow_count, stream); return; }
     // diagnostics: extra dynamic LDS lowers the occupancy (sensitivity experiments)
     static const uint32_t extra_lds = getenv("RALA_PILE_EXTRA_LDS") ? (uint32_t)atoi(getenv("RALA_PILE_EXTRA_LDS")) : 0u;
     const bool diag = args.stop_after != 99;
@@ -1947,6 +1968,18 @@ void launch_pile_runs(const PileArgs& args, uint32_t grid, int tier, uint32_t* o
 void launch_pile_sens(const PileArgs& args, uint32_t grid, int tier, int mode, uint32_t* overflow_list,
                       uint32_t* overflow_count, hipStream_t stream) {
     if (grid == 0) return;
+    if (mode == 1 && !args.pile) {
+        // without rows (option pile_rows = 0): medians as ever, the expansion to HBM left out (mode 2 never touches a row)
+#define RALA_LAUNCH_SENS_ROWLESS(...)                                                                                   \
+    hipLaunchKernelGGL((pile_runs_kernel<__VA_ARGS__, false>), dim3(grid), dim3(64), 0, stream, args, overflow_list, overflow_count)
+        if (tier == 0 && grid >= args.n_items && !args.n_items_dev) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, true, 16384, 1, false, 0);
+        else if (tier == 3) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, false, 32768, 1, false, 0);
+        else if (tier == 0) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, false, 16384, 1, false, 0);
+        else if (tier == 2) RALA_LAUNCH_SENS_ROWLESS(kRunEventCapBig, false, 1, false, 16384, 1, false, 0);
+        else RALA_LAUNCH_SENS_ROWLESS(kRunEventCapMid, false, 1, false, 16384, 1, false, 0);
+#undef RALA_LAUNCH_SENS_ROWLESS
+        return;
+    }
 #define RALA_LAUNCH_SENS(cap, m)                                                                                        \
     hipLaunchKernelGGL((pile_runs_kernel<cap, false, m>), dim3(grid), dim3(64), 0, stream, args, overflow_list,         \
                        overflow_count)

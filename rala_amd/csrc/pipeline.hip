@@ -576,11 +576,79 @@ int preprocess_chimeras(rala_hip_ctx* ctx) {
     return RALA_HIP_OK;
 }
 
+// ---- rows on demand (option pile_rows = 0; pile_rows_kernel.hip) -------------------------------------------------------
+// rows start on 128-byte boundaries in the scratch, as they do in the resident buffer
+inline uint64_t scratch_row_elems(uint32_t len) { return ((uint64_t)len + 63u) & ~(uint64_t)63u; }
+// what a batch of rebuilt rows may take, in values: the option, or the longest row where that is larger
+uint64_t rows_scratch_cap(const rala_hip_ctx* ctx) {
+    return std::max<uint64_t>(((uint64_t)ctx->pile_rows_scratch_mb << 20) / sizeof(uint16_t), scratch_row_elems(ctx->max_read_len));
+}
+// The rows of `count` reads - reads[0 .. count) (host), or first, first + 1, ... where reads is null - rebuilt into
+// ctx->d_rows_scratch on stream st; ctx->d_rows_off[read] says where (what pile_off is to the resident rows).  with_sens: the
+// sensitive bounds of the last sensitive construct on top (Pile::add_layers a second time, graph.cpp:941-969).  The stream is
+// waited for.
+int materialize_rows(rala_hip_ctx* ctx, const uint32_t* reads, uint32_t first, uint32_t count, bool with_sens, hipStream_t st) {
+    if (count == 0) return RALA_HIP_OK;
+    if (!ctx->ev_ready) return fail(ctx, RALA_HIP_EINVAL, "the bound events of rala_hip_initialize are gone: no row can be rebuilt");
+    const uint64_t n = ctx->n_reads;
+    HIPCHECK(ctx->d_rows_off.ensure(n + 1));
+    ctx->h_rows_off.resize(n);
+    uint64_t total = 0;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t r = reads ? reads[i] : first + i;
+        if (r >= n) return fail(ctx, RALA_HIP_EINVAL, "bad read in a list of rows");
+        ctx->h_rows_off[r] = total;
+        total += scratch_row_elems(ctx->h_read_len[r]);
+        lo = std::min(lo, r); hi = std::max(hi, r);
+    }
+    HIPCHECK(ctx->d_rows_scratch.ensure(total + 64));
+    HIPCHECK(hipMemcpyAsync(ctx->d_rows_off.p + lo, ctx->h_rows_off.data() + lo, (size_t)(hi - lo + 1) * 8, hipMemcpyHostToDevice, st));
+    if (reads) {
+        HIPCHECK(ctx->d_rows_list.ensure(count));
+        HIPCHECK(hipMemcpyAsync(ctx->d_rows_list.p, reads, (size_t)count * 4, hipMemcpyHostToDevice, st));
+    }
+    RowsArgs ra;
+    ra.reads = reads ? ctx->d_rows_list.p : nullptr; ra.first = first; ra.n_items = count;
+    ra.read_len = ctx->d_read_len.p; ra.dst_off = ctx->d_rows_off.p; ra.rows = ctx->d_rows_scratch.p;
+    ra.ev_off = ctx->d_ev_off.p; ra.ev = ctx->ev_fixed ? ctx->d_ev_fixed.p : ctx->d_ev.p;
+    ra.ev_cnt = ctx->ev_fixed ? ctx->d_cursor.p : nullptr; ra.ev_stride = kRunEventCapBig; ra.ev_shift = ctx->ev_shift;
+    ra.sens_off = with_sens ? ctx->d_sens_off.p : nullptr; ra.sens_ev = with_sens ? ctx->d_sens_ev.p : nullptr;
+    launch_pile_rows(ra, st);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));             // (`reads` is pageable host memory)
+    ctx->rows_materialised += count;
+    return RALA_HIP_OK;
+}
+
+int run_repeats_classes_on_rows(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st);
+// position-space sensitive-pass kernel over `reads` where the rows are: the resident ones, or - option pile_rows = 0 - batch
+// after batch of them rebuilt in the scratch, a.pile / a.pile_off pointing there (mode 1 works on top of the primary rows; mode
+// 2 reads them with the sensitive layers of this construct on top, as the resident rows hold them by then)
+int run_repeats_classes(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st) {
+    if (!ctx->rowless) return run_repeats_classes_on_rows(ctx, a, reads, mode, st);
+    const uint64_t cap = rows_scratch_cap(ctx);
+    for (size_t i = 0; i < reads.size();) {
+        size_t j = i;
+        uint64_t total = 0;
+        do total += scratch_row_elems(ctx->h_read_len[reads[j++]]);
+        while (j < reads.size() && total + scratch_row_elems(ctx->h_read_len[reads[j]]) <= cap);
+        const std::vector<uint32_t> part(reads.begin() + i, reads.begin() + j);
+        int rc = materialize_rows(ctx, part.data(), 0, (uint32_t)part.size(), mode == 2 && (ctx->sens_csr_ready || ctx->sens_pass_running), st);
+        if (rc != RALA_HIP_OK) return rc;
+        a.pile = ctx->d_rows_scratch.p; a.pile_off = ctx->d_rows_off.p;
+        rc = run_repeats_classes_on_rows(ctx, a, part, mode, st);
+        if (rc != RALA_HIP_OK) return rc;
+        i = j;
+    }
+    return RALA_HIP_OK;
+}
+
 // position-space sensitive-pass kernel over `reads`, grouped by LDS image size, on stream st (the main stream, or the aux
 // stream beside a mode's run-space kernels: nothing here waits for another stream).  Mode 2: a read whose region lists or
 // raw hills outgrow the kernel's LDS lists is noted and runs again with the lists in global memory, doubled until the read
 // fits (as run_unbounded_piles).
-int run_repeats_classes(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st) {
+int run_repeats_classes_on_rows(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st) {
     Trace trc;
     std::vector<uint32_t> order;
     build_classes(ctx, reads, order);
@@ -1017,6 +1085,13 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     launch_list_targets(cl->d_sens_off.p, (uint32_t)nl, cl->d_sens_list.p, cl->d_chain_cnt.p + 4, sl);
     uint32_t n_targets = 0;
     uint32_t small[16] = {};
+    // (rows on demand: for the rest of this pass a target's row has these bounds on top; for the getters once the pass has
+    // succeeded - the CSR then stays until the next rala_hip_initialize)
+    struct PassRunning {
+        rala_hip_ctx* c;
+        explicit PassRunning(rala_hip_ctx* ctx_) : c(ctx_) { c->sens_pass_running = true; }
+        ~PassRunning() { c->sens_pass_running = false; }
+    } pass_running(cl);
 
     RepeatArgs a;
     a.read_len = cl->d_read_len.p; a.pile_off = cl->d_pile_off.p; a.pile = cl->d_pile.p;
@@ -1029,7 +1104,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     // the same in run space: the primary events + the sensitive bounds
     PileArgs pa;
     memset(&pa, 0, sizeof(pa));
-    pa.read_len = cl->d_read_len.p; pa.pile_off = cl->d_pile_off.p; pa.pile = cl->d_pile.p;
+    pa.read_len = cl->d_read_len.p; pa.pile_off = cl->d_pile_off.p; pa.pile = cl->rowless ? nullptr : cl->d_pile.p;
     pa.ev_off = cl->d_ev_off.p; pa.ev = cl->ev_fixed ? cl->d_ev_fixed.p : cl->d_ev.p;
     pa.ev_cnt = cl->ev_fixed ? cl->d_cursor.p : nullptr; pa.ev_stride = kRunEventCapBig; pa.ev_shift = cl->ev_shift;
     pa.stop_after = 99;
@@ -1202,6 +1277,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     }
     trc("rep: filter overlaps", cs->overlaps.size());
     cs->have_repeats = true;
+    cl->sens_csr_ready = true;
     return RALA_HIP_OK;
 }
 
@@ -1974,13 +2050,44 @@ int rala_hip::pile_row_digests(rala_hip_ctx* ctx, const uint32_t* begin, const u
     HIPCHECK(hipMemcpy(d_be.p + n, end, n * 4, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(d_al.p, alive, n, hipMemcpyHostToDevice));
     hipStream_t s = ctx->stream;
+    if (ctx->rowless) {
+        // no row is resident: the reads in batches of what the scratch holds, every batch rebuilt and hashed where it lies.
+        // Nothing is stored, so nothing is stored outside a region: `outside` is 0 by definition.
+        const uint64_t cap = rows_scratch_cap(ctx);
+        for (uint64_t r0 = 0; r0 < n;) {
+            uint64_t r1 = r0, total = 0;
+            do total += scratch_row_elems(ctx->h_read_len[r1++]);
+            while (r1 < n && total + scratch_row_elems(ctx->h_read_len[r1]) <= cap);
+            const int rc = materialize_rows(ctx, nullptr, (uint32_t)r0, (uint32_t)(r1 - r0), ctx->sens_csr_ready, s);
+            if (rc != RALA_HIP_OK) return rc;
+            launch_pile_row_digests(ctx->d_rows_scratch.p, ctx->d_rows_off.p + r0, ctx->d_read_len.p + r0, d_be.p + r0, d_be.p + n + r0, d_al.p + r0,
+                                    (uint32_t)(r1 - r0), fnv ? d_out.p + r0 : nullptr, inside ? d_out.p + n + r0 : nullptr, nullptr, s);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(stream_sync(ctx, s));          // (the next batch overwrites the scratch)
+            r0 = r1;
+        }
+        if (outside) std::fill(outside, outside + n, (uint64_t)0);
+    } else {
     launch_pile_row_digests(ctx->d_pile.p, ctx->d_pile_off.p, ctx->d_read_len.p, d_be.p, d_be.p + n, d_al.p, (uint32_t)n,
                             fnv ? d_out.p : nullptr, inside ? d_out.p + n : nullptr, outside ? d_out.p + 2 * n : nullptr, s);
     HIPCHECK(hipGetLastError());
     HIPCHECK(stream_sync(ctx, s));
+    }
     if (fnv) HIPCHECK(hipMemcpy(fnv, d_out.p, n * 8, hipMemcpyDeviceToHost));
     if (inside) HIPCHECK(hipMemcpy(inside, d_out.p + n, n * 8, hipMemcpyDeviceToHost));
-    if (outside) HIPCHECK(hipMemcpy(outside, d_out.p + 2 * n, n * 8, hipMemcpyDeviceToHost));
+    if (outside && !ctx->rowless) HIPCHECK(hipMemcpy(outside, d_out.p + 2 * n, n * 8, hipMemcpyDeviceToHost));
+    return RALA_HIP_OK;
+}
+
+int rala_hip::pile_row_to_host(rala_hip_ctx* ctx, uint64_t read, uint16_t* data) {
+    const uint32_t n = ctx->h_read_len[read];
+    if (!ctx->rowless) {
+        HIPCHECK(ctx->d_pile.copy_to_host(data, ctx->h_pile_off[read], n));
+        return RALA_HIP_OK;
+    }
+    const int rc = materialize_rows(ctx, nullptr, (uint32_t)read, 1, ctx->sens_csr_ready, ctx->stream);
+    if (rc != RALA_HIP_OK) return rc;
+    if (n) HIPCHECK(hipMemcpy(data, ctx->d_rows_scratch.p, (size_t)n * 2, hipMemcpyDeviceToHost));
     return RALA_HIP_OK;
 }
 
@@ -2214,6 +2321,8 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "gzip_on_device")) { ctx->gzip_on_device = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "gzip_chunk_bytes")) { ctx->gzip_chunk_bytes = value > 0 ? value : 64 << 10; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_gzip_false_sync")) { ctx->debug_gzip_false_sync = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
+    if (!strcmp(key, "pile_rows")) { ctx->pile_rows = value ? 1u : 0u; return RALA_HIP_OK; }
+    if (!strcmp(key, "pile_rows_scratch_mb")) { ctx->pile_rows_scratch_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
     if (!strcmp(key, "pile_chunk_mb")) { ctx->pile_chunk_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_ev_events")) { ctx->debug_ev_events = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_count_window")) { ctx->debug_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
@@ -2415,7 +2524,16 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     ctx->initialized = ctx->constructed = ctx->ev_ready = false;
     ctx->tail_on_device = ctx->host_stale = ctx->marks_on_device = false;
 
-    {
+    ctx->rowless = ctx->pile_rows == 0;
+    ctx->sens_csr_ready = false;
+    ctx->rows_materialised = 0;
+    if (ctx->rowless && ctx->debug_pile_stop_after != 99) {
+        return fail(ctx, RALA_HIP_EINVAL, "debug_pile_stop_after is a diagnostic of the kernels that store rows: not with pile_rows = 0");
+    }
+    if (ctx->rowless) {
+        // option pile_rows = 0: no row is resident (what an earlier call allocated is given back); the kernels below store none
+        ctx->d_pile.release();
+    } else {
         // The rows as physical chunks of 1 GB mapped side by side into one range (round 6).  Where the rows lie physically decides
         // whether the first pile kernel takes 3.8 or 4.3 ms at C3 (five placements inside one process: 3.84 / 4.20 / 4.12 / 4.27 /
         // 3.81) - its stores, a wavefront per row, 7 000 rows open at a time, are the only access pattern of the path that feels it.
@@ -2611,7 +2729,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     }
 
     PileArgs a;
-    a.read_len = ctx->d_read_len.p; a.pile_off = ctx->d_pile_off.p; a.pile = ctx->d_pile.p;
+    a.read_len = ctx->d_read_len.p; a.pile_off = ctx->d_pile_off.p; a.pile = ctx->rowless ? nullptr : ctx->d_pile.p;
     a.ev_off = ctx->d_ev_off.p; a.ev = fixed ? ctx->d_ev_fixed.p : ctx->d_ev.p;
     a.ev_cnt = fixed ? ctx->d_cursor.p : nullptr; a.ev_stride = slot;
     ctx->ev_shift = ev_shift;
@@ -3066,6 +3184,9 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
     if (rc != RALA_HIP_OK) return rc;
     const bool with_sens = sens != nullptr && n_sens != 0;
     if (with_sens && !ctx->piles_resident) return fail(ctx, RALA_HIP_EINVAL, "the sensitive pass needs the piles on this context");
+    if (with_sens && ctx->rowless && ctx->sens_csr_ready) {
+        return fail(ctx, RALA_HIP_EINVAL, "pile_rows = 0: one sensitive construct per rala_hip_initialize (its bounds are what the rows are rebuilt from)");
+    }
     HIPCHECK(hipSetDevice(ctx->device));
     rc = flush_upload(ctx);
     if (rc != RALA_HIP_OK) return rc;
@@ -3299,7 +3420,7 @@ int rala_hip_get_pile_data(rala_hip_ctx* ctx, uint64_t read, uint16_t* data) {
     HIPCHECK(hipSetDevice(ctx->device));
     { const int rcm = materialize_host(ctx); if (rcm != RALA_HIP_OK) return rcm; }
     const uint32_t n = ctx->h_read_len[read];
-    HIPCHECK(ctx->d_pile.copy_to_host(data, ctx->h_pile_off[read], n));
+    { const int rcr = pile_row_to_host(ctx, read, data); if (rcr != RALA_HIP_OK) return rcr; }
     // Pile::shrink zeroes outside the current valid region (pile.cpp:311-318); the
     // host tail narrows regions after the pile was written
     if (ctx->h_alive[read]) {
@@ -3307,6 +3428,13 @@ int rala_hip_get_pile_data(rala_hip_ctx* ctx, uint64_t read, uint16_t* data) {
         for (uint32_t j = 0; j < B && j < n; ++j) data[j] = 0;
         for (uint32_t j = E; j < n; ++j) data[j] = 0;
     }
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_pile_rows_info(rala_hip_ctx* ctx, uint64_t* resident_bytes, uint64_t* rows_materialised) {
+    if (!ctx) return RALA_HIP_EINVAL;
+    if (resident_bytes) *resident_bytes = ctx->d_pile.p ? (uint64_t)ctx->d_pile.n * sizeof(uint16_t) : 0;
+    if (rows_materialised) *rows_materialised = ctx->rows_materialised;
     return RALA_HIP_OK;
 }
 

@@ -755,7 +755,8 @@ int rala_hip_mg_get_pile_data(rala_hip_mg* mg, uint64_t read, uint16_t* data) {
     const uint64_t j = read / mg->world;
     rala_hip_ctx* cl = mg->cl;
     const uint32_t n = cl->h_read_len[j];
-    MGCHECK(hipMemcpy(data, cl->d_pile.p + cl->h_pile_off[j], (size_t)n * 2, hipMemcpyDeviceToHost));
+    // (chunk by chunk where the rows lie in mapped chunks - a row may straddle two; rebuilt from its events with pile_rows = 0)
+    { const int rcr = pile_row_to_host(cl, j, data); if (rcr != RALA_HIP_OK) return mg_fail(mg, rcr, rala_hip_last_error(cl)); }
     uint32_t be[2] = {0, 0};
     uint8_t alive = 0;
     MGCHECK(hipMemcpy(&be[0], mg->cs->d_begin.p + read, 4, hipMemcpyDeviceToHost));

@@ -56,6 +56,10 @@ int paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t lo, uint64_
 int pile_row_digests(rala_hip_ctx* cl, const uint32_t* begin, const uint32_t* end, const uint8_t* alive, uint64_t* fnv, uint64_t* inside,
                      uint64_t* outside);
 
+// the stored values of one row of cl to the host (nothing zeroed): copied from the resident rows, or - option pile_rows = 0 -
+// rebuilt from the read's events (pile_rows_kernel.hip)
+int pile_row_to_host(rala_hip_ctx* cl, uint64_t read, uint16_t* data);
+
 hipError_t stream_sync(rala_hip_ctx* ctx, hipStream_t s);
 hipError_t d2h_small(rala_hip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 int flush_upload(rala_hip_ctx* ctx);       // (pipeline.hip) RALA_HIP_MEM_HOST_ASYNC columns not uploaded yet: now

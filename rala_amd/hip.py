@@ -23,7 +23,7 @@ SYMBOLS = (
     "rala_hip_create", "rala_hip_destroy", "rala_hip_last_error", "rala_hip_set_option", "rala_hip_stream",
     "rala_hip_set_reads", "rala_hip_set_overlaps", "rala_hip_initialize", "rala_hip_construct",
     "rala_hip_remove_transitive_edges", "rala_hip_tr_mark", "rala_hip_get_valid", "rala_hip_get_piles",
-    "rala_hip_get_pile_data", "rala_hip_get_pile_row_digests", "rala_hip_get_intervals", "rala_hip_get_overlaps", "rala_hip_get_graph_size",
+    "rala_hip_get_pile_data", "rala_hip_get_pile_row_digests", "rala_hip_get_pile_rows_info", "rala_hip_get_intervals", "rala_hip_get_overlaps", "rala_hip_get_graph_size",
     "rala_hip_get_graph", "rala_hip_get_timings", "rala_hip_get_num_prefiltered",
     "rala_hip_dedupe", "rala_hip_emit_bound_tuples", "rala_hip_set_bound_tuples", "rala_hip_import_state",
     "rala_hip_emit_bound_tuples_bucketed", "rala_hip_get_device_state", "rala_hip_import_state_device",
@@ -125,6 +125,7 @@ def lib(build=True):
         L.rala_hip_get_piles.argtypes = [vp, vp, vp, vp, vp, vp]
         L.rala_hip_get_pile_data.argtypes = [vp, u64, vp]
         L.rala_hip_get_pile_row_digests.argtypes = [vp, vp, vp, vp]
+        L.rala_hip_get_pile_rows_info.argtypes = [vp, vp, vp]
         L.rala_hip_get_intervals.argtypes = [vp, i32, vp, vp, vp]
         L.rala_hip_get_overlaps.argtypes = [vp, i32, ctypes.POINTER(u64), vp, vp, vp, vp, vp, vp, vp]
         L.rala_hip_get_graph_size.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
@@ -468,6 +469,13 @@ class Context:
         out = [np.zeros(self.n_reads, dtype=np.uint64) for _ in range(3)]
         self._check(self.L.rala_hip_get_pile_row_digests(self.h, *[a.ctypes.data for a in out]))
         return tuple(out)
+
+    def pile_rows_info(self):
+        """(resident_bytes, rows_materialised): the size of the rows' allocation (0 with option pile_rows = 0) and the rows
+        rebuilt from their events since initialize()"""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self.L.rala_hip_get_pile_rows_info(self.h, ctypes.addressof(out), ctypes.addressof(out) + 8))
+        return int(out[0]), int(out[1])
 
     def intervals(self, kind):
         """(offsets[n+1] uint64, pairs[k,2] uint32, aux[k] uint32)"""

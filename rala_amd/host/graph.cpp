@@ -82,6 +82,7 @@ void Graph::open_devices() {
             fprintf(stderr, "[rala::Graph::Graph] error: no usable HIP device!\n");
             exit(1);
         }
+        if (!io::pile_rows_wanted()) check(ctx_, rala_hip_set_option(ctx_, "pile_rows", 0), "Graph");
         return;
     }
     if (n_gpus > 64) {
@@ -125,6 +126,11 @@ void Graph::open_devices() {
         if (rc[k] != RALA_HIP_OK) {
             fprintf(stderr, "[rala::Graph::Graph] error: device %d (rank %u of %u) is not usable!\n", device[k], k, n_gpus);
             exit(1);
+        }
+        // (the rows live on the owner contexts)
+        if (!io::pile_rows_wanted()) {
+            rala_hip_ctx* owner = rala_hip_mg_owner_context(ranks_[k]);
+            check(owner, rala_hip_set_option(owner, "pile_rows", 0), "Graph");
         }
     }
     // joining a communicator is collective: one host thread per rank.  A join that does not come back cannot be

@@ -38,6 +38,11 @@ bool has_suffix(const std::string& src, const std::string& suffix);
  * says so, read where the file is opened; without it: no - see README.md, "Compressed overlap files", for what was measured */
 bool device_gzip_wanted();
 
+/*! @brief are the piles' coverage rows resident on the device (rala_hip option "pile_rows")?  RALA_PILE_ROWS=0 says no - a row is
+ * then rebuilt from the read's overlap bounds when Pile::data() or the -d output asks for it, and the device holds 2 bytes per base
+ * less; read where the devices are opened; without it: yes - see README.md, "Piles without resident rows" */
+bool pile_rows_wanted();
+
 /*! @brief is the read file indexed on the device (rala_hip_index_sequences) and its second pass cut out of the file with that
  * index?  RALA_DEVICE_SEQUENCES=1 / =0 says so, read where the file is opened; without it: no - see README.md, "Compressed
  * overlap files", for what was measured */
