@@ -188,7 +188,10 @@ typedef struct rala_hip_inflate_timings {
     uint64_t members;           /* gzip members with text */
 } rala_hip_inflate_timings;
 int rala_hip_get_inflate_timings(rala_hip_ctx* ctx, rala_hip_inflate_timings* out);
-/* The speculative inflater of the last rala_hip_set_overlaps_from_paf / _mhap call (zeros when it did not run). */
+/* The speculative inflater of the last rala_hip_set_overlaps_from_paf / _mhap call (zeros when it did not run), or of the last
+ * rala_hip_index_sequences of a single-member gzip file.  rala_hip_slice_sequences of such a file overwrites them with its own
+ * walk: it takes the index's chain over, so find_ms, chunks, chunks_with_candidate and chunks_refuted are 0 then, and decode_ms
+ * is the writing pass alone. */
 typedef struct rala_hip_gzip_timings {
     float find_ms;                  /* block starts searched in every chunk */
     float decode_ms;                /* the counting pass and the writing pass */
@@ -240,6 +243,40 @@ int rala_hip_get_sequence_index(rala_hip_ctx* ctx, uint64_t* name_off, uint32_t*
 /* ship_ms: the file (BGZF: its compressed bytes) to the device; tokenize_ms: the kernels (BGZF: the inflater among them);
  * bytes: the text's; lines: the records (the "loaded sequences" stage of src/graph.cpp:246-266) */
 int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out);
+/* With the option "gzip_on_device" set, rala_hip_index_sequences takes a gzip file of ONE member that is not BGZF as well (what
+ * gzip, pigz and basecallers write).  The compressed bytes stay in device memory while the file is indexed - the only buffer
+ * whose size depends on the file's; block starts are found and the chain from chunk 0 is followed as for the overlaps (see
+ * rala_hip_set_overlaps_from_paf), and the text is then written and resolved WINDOW by window: a window is a run of true
+ * chunks whose text fits it (a quarter of the free memory over three bytes per text byte; option "debug_sequence_window";
+ * never less than the largest chunk's text - RALA_HIP_ENOMEM where that does not fit), the last 32 768 bytes of a window are
+ * carried in front of the next one's symbols, the windows' CRC registers are chained.  CRC32, ISIZE and the final block ending
+ * at the trailer prove the text; anything else - several members included - is *irregular = 8.  The index equals that of the
+ * uncompressed file.  rala_hip_get_gzip_timings then speaks of this call.
+ *
+ * The second pass: the bases of the reads `wanted` (ascending record numbers of the current index, n_wanted of them) are cut
+ * out of the file on the device and written packed to `bases` (host memory): read wanted[k]'s at bases + base_off[k], where
+ * base_off (n_wanted + 1 entries) is the exclusive scan of the wanted reads' lengths.  The call walks the text in the windows
+ * of the index pass - a plain file's bytes, a BGZF file's members, a gzip member's chunks again (the chain is the context's;
+ * the compressed bytes are shipped once more) - and gathers every window's share with one kernel; the output leaves the device
+ * window by window.  *irregular != 0: refused, `bases` holds nothing of use, take the host reader - 64 there is no index or the
+ * file's size is not what the index saw, 8 the inflater refused or the gzip text's CRC32 / ISIZE are no longer the index's,
+ * 32 the text does not fit the index in another way. */
+int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t* wanted, uint64_t n_wanted, const uint64_t* base_off,
+                             uint8_t* bases, uint32_t threads, int* irregular);
+/* The last rala_hip_slice_sequences. */
+typedef struct rala_hip_sequence_slice_info {
+    uint64_t windows;               /* windows of text walked */
+    uint64_t max_window_text_bytes; /* the most text one window held (the look-ahead behind it included) */
+    uint64_t bases;                 /* bases written */
+    float ship_ms;                  /* the file's bytes (compressed ones where it is compressed) to the device */
+    float kernel_ms;                /* everything on the device: inflate, count, gather, the output's way back */
+    float gather_ms;                /* of those: the gather kernel */
+    float copy_ms;                  /* of those: the packed bases device -> host */
+} rala_hip_sequence_slice_info;
+int rala_hip_get_sequence_slice_info(rala_hip_ctx* ctx, rala_hip_sequence_slice_info* out);
+/* The CRC32 of n pieces laid end to end (no context, no device), from every piece's CRC REGISTER - started from zero, no final
+ * inversion: zlib's crc32(piece) ^ crc32(as many zero bytes) - and its length: how the windowed inflater chains its windows. */
+uint32_t rala_hip_crc32_chain(const uint32_t* reg, const uint64_t* len, uint64_t n);
 /* The sensitive overlaps (rala -s; Graph::preprocess, src/graph.cpp:901-939) of an uncompressed PAF file the same way, without
  * the length check (Overlap::transmute_ has none, src/overlap.cpp:84-114): the lines that start in bytes [lo, hi) of the file
  * (hi = ~0: to its end; a rank of a sharded run takes a share - any split of the sensitive set will do).  *out receives DEVICE

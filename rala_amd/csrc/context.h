@@ -265,6 +265,18 @@ struct rala_hip_ctx {
     uint64_t n_seq_records = 0, n_seq_name_bytes = 0;
     bool seq_index_valid = false;
     rala_hip_ingest_timings seq_tm = {};
+    // what the second pass (ingest.hip: rala_hip_slice_sequences) needs of the index: what it was made from (0 a plain file,
+    // 1 BGZF, 2 a single gzip member - then the chain of its true chunks, text offsets from the text's start, and its CRC32),
+    // the file's and the text's size, the stripped bytes of the whole text
+    int seq_source = 0;
+    bool seq_fastq = false;
+    uint64_t seq_file_n = 0, seq_text_n = 0, seq_n_stripped = 0;
+    std::vector<rala_hip::GzipJob> seq_gzip_chain;
+    uint32_t seq_gzip_crc = 0;
+    rala_hip::DevBuf<uint16_t> d_gzip_carry;
+    rala_hip::DevBuf<uint8_t> d_gzip_hold, d_slice_out;
+    rala_hip::DevBuf<uint64_t> d_slice_w[3];
+    rala_hip_sequence_slice_info slice_info = {};
 
     // overlaps
     uint64_t n_ovl = 0;

@@ -821,7 +821,7 @@ __global__ __launch_bounds__(kWave) void gzip_write_kernel(const uint8_t* __rest
     __shared__ __align__(16) uint16_t ring[kRing];
     __shared__ Lds T;
     const GzipJob job = jobs[blockIdx.x];
-    const GzipSpan o = inflate_span<true>(T, ring, comp, end, job.start_bit, blockIdx.x == 0, nullptr, 0, 0, job.stop_bit, job.text_n,
+    const GzipSpan o = inflate_span<true>(T, ring, comp, end, job.start_bit, job.first != 0, nullptr, 0, 0, job.stop_bit, job.text_n,
                                           sym + job.text_off);
     const bool ok = o.text == job.text_n && o.status == (job.stop_bit == kNoStart ? 1u : 0u);
     if (!ok && lane_id() == 0) atomicOr(flags, 8u);
@@ -849,7 +849,8 @@ __device__ __forceinline__ uint32_t through_window(const uint16_t* sym, const ui
 __global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const uint64_t* __restrict__ text_off, uint32_t n_true, uint32_t* flags) {
     bool wrong = false;
     for (uint32_t i = 1; i < n_true; ++i) {
-        const uint64_t hi = text_off[i], lo = hi > kRing ? hi - kRing : 0;
+        // (nothing in front of the first chunk is a symbol of this launch: a window's carry is bytes already)
+        const uint64_t hi = text_off[i], lo = max((uint64_t)(hi > kRing ? hi - kRing : 0), (uint64_t)text_off[0]);
         for (uint64_t p0 = (lo & ~7ull) + 8ull * threadIdx.x; p0 < hi; p0 += 8 * 1024) {
             const uint4 q = *(const uint4*)(sym + p0);
             uint32_t w[4] = {q.x, q.y, q.z, q.w};
@@ -879,7 +880,8 @@ __global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const
 // kSeg bytes of text per workgroup: symbols in (8 per thread and load), markers through their chunk's window, the bytes
 // staged in LDS, their CRC register (from zero, no final inversion: the host chains the segments') and out in whole 16 bytes.
 __global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_t* __restrict__ sym, const uint64_t* __restrict__ text_off, uint32_t n_true,
-                                                                    uint64_t text_n, uint8_t* __restrict__ text, uint32_t* __restrict__ seg_crc, uint32_t* flags) {
+                                                                    uint64_t text_n, uint8_t* __restrict__ text, uint32_t* __restrict__ seg_crc, uint32_t* flags,
+                                                                    uint64_t front) {
     __shared__ __align__(16) uint8_t out[kSeg];
     __shared__ uint32_t crc_table[256];
     __shared__ uint32_t wave_part[kSegThreads / kWave];
@@ -894,14 +896,14 @@ __global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_
     }
     bool wrong = false;
     for (uint32_t k = 8 * tid; k < n; k += 8 * kSegThreads) {
-        const uint4 q = *(const uint4*)(sym + base + k);            // (the buffer is readable behind text_n)
+        const uint4 q = *(const uint4*)(sym + front + base + k);    // (the buffer is readable behind text_n)
         const uint32_t w[4] = {q.x, q.y, q.z, q.w};
         uint32_t b[2] = {0, 0};
 #pragma unroll
         for (uint32_t e = 0; e < 8; ++e) {
             uint32_t s = (w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
             if (k + e < n && (s & 0x8000u)) {
-                s = through_window(sym, text_off, n_true, base + k + e, s);
+                s = through_window(sym, text_off, n_true, front + base + k + e, s);
                 wrong = wrong || (s & 0x8000u);
             }
             b[e >> 2] |= (s & 0xFFu) << (8 * (e & 3));
@@ -930,6 +932,15 @@ __global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_
         for (uint32_t k = 0; k < kSegThreads / kWave; ++k) total ^= wave_part[k];
         seg_crc[blockIdx.x] = total;
     }
+}
+
+// out[i] = symbol n + i of (the kRing symbols at sym, then the n bytes at text)
+__global__ __launch_bounds__(256) void gzip_carry_kernel(const uint16_t* __restrict__ sym, const uint8_t* __restrict__ text, uint64_t n,
+                                                          uint16_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kRing) return;
+    const uint64_t p = n + i;
+    out[i] = p < kRing ? sym[p] : (uint16_t)text[p - kRing];
 }
 
 constexpr X2n kX2nHost = make_x2n();
@@ -971,11 +982,34 @@ void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, u
 }
 
 void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
-                         uint32_t* flags, hipStream_t s) {
+                         uint32_t* flags, hipStream_t s, uint64_t front) {
     if (text_n == 0) return;
     if (n_true > 1) hipLaunchKernelGGL(gzip_windows_kernel, dim3(1), dim3(1024), 0, s, sym, text_off, n_true, flags);
     const uint64_t n_seg = (text_n + kSeg - 1) / kSeg;
-    hipLaunchKernelGGL(gzip_resolve_kernel, dim3((uint32_t)n_seg), dim3(kSegThreads), 0, s, sym, text_off, n_true, text_n, text, seg_crc, flags);
+    hipLaunchKernelGGL(gzip_resolve_kernel, dim3((uint32_t)n_seg), dim3(kSegThreads), 0, s, sym, text_off, n_true, text_n, text, seg_crc, flags, front);
+}
+
+uint32_t gzip_ring_symbols() { return kRing; }
+
+void launch_gzip_carry(uint16_t* sym, const uint8_t* text, uint64_t text_n, uint16_t* tmp, hipStream_t s) {
+    hipLaunchKernelGGL(gzip_carry_kernel, dim3(kRing / 256), dim3(256), 0, s, sym, text, text_n, tmp);
+    (void)hipMemcpyAsync(sym, tmp, kRing * sizeof(uint16_t), hipMemcpyDeviceToDevice, s);
+}
+
+uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n) {
+    uint32_t acc = 0;
+    for (uint64_t b = 0, k = 0; b < text_n; b += kSeg, ++k) acc = crc_shift(acc, std::min<uint64_t>(kSeg, text_n - b)) ^ seg_crc[k];
+    return acc;
+}
+
+uint32_t gzip_crc_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
+    uint32_t acc = 0;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        acc = crc_shift(acc, len[i]) ^ reg[i];
+        total += len[i];
+    }
+    return ~(acc ^ crc_shift(0xFFFFFFFFu, total));
 }
 
 uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n) {

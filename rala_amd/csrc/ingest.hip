@@ -624,6 +624,8 @@ int gzip_inflate(rala_hip_ctx* ctx, const char* path, uint32_t threads, GzipFile
         j.stop_bit = sp.status == 0 ? starts[sp.next] : kGzipNoStart;
         j.text_off = text_n;
         j.text_n = sp.text;
+        j.first = jobs.empty() ? 1u : 0u;
+        j.pad = 0;
         jobs.push_back(j);
         text_off.push_back(text_n);
         text_n += sp.text;
@@ -775,6 +777,340 @@ int index_window(rala_hip_ctx* ctx, SequenceRun& R, const uint8_t* text, uint64_
     R.name_bytes += bytes;
     R.last_is_newline = last == '\n';
     return RALA_HIP_OK;
+}
+
+// ---- a single-member gzip read file, inflated WINDOW by window (the driver of gzip_inflate's kernels for a text that does
+// not fit): find, count and the chain run over the whole compressed file, which stays resident - the only buffer whose size
+// depends on the file's; write, windows and resolve then run per window, a run of consecutive true chunks whose text fits
+// it.  The symbols of a window lie behind a CARRY of gzip_ring_symbols(): the last 32 768 bytes in front of it (0x8000 where
+// the file's text has not begun), so the markers of its first chunks point into bytes, and every text offset the kernels see
+// counts from the carry's first symbol.
+struct GzipWalk {
+    std::vector<GzipJob> chain;             // the true chunks, text offsets from the text's start
+    uint64_t file_n = 0, end = 0, text_n = 0;
+    uint32_t crc = 0;                       // the trailer's
+    uint64_t window = 0;                    // text bytes a window holds at most (at least the largest chunk's)
+    size_t next_job = 0;
+    std::vector<uint32_t> reg;              // the windows' CRC registers and lengths
+    std::vector<uint64_t> len;
+    float ship_ms = 0;
+    uint32_t n_readers = 0;
+    rala_hip_gzip_timings tm = {};
+};
+
+// The file to the device and (chain == null) its chain built there, or the chain of an earlier walk taken over; the buffers
+// of a window made: `front` bytes of room in front of the window's text in ctx->d_gzip_text and `behind` bytes behind it.
+// want_window 0: what a quarter of the free memory holds at three bytes per text byte.  *valid = false: not a stream this can prove.
+int gzip_walk_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, uint64_t want_window, uint64_t front, uint64_t behind,
+                   const std::vector<GzipJob>* chain, GzipWalk& g, bool* valid) {
+    *valid = false;
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    const uint64_t file_n = g.file_n = (uint64_t)st.st_size;
+    std::vector<uint8_t> head((size_t)std::min(file_n, kGzipHeadReach));
+    uint8_t trailer[8];
+    if (file_n < 18 || pread(fd, head.data(), head.size(), 0) != (ssize_t)head.size() || pread(fd, trailer, 8, (off_t)(file_n - 8)) != 8) return RALA_HIP_OK;
+    uint64_t deflate_off = 0;
+    if (!gzip_head(head.data(), head.size(), &deflate_off) || deflate_off + 8 >= file_n) return RALA_HIP_OK;
+    const uint64_t end = g.end = file_n - 8;
+    g.crc = le32(trailer);
+    hipStream_t s = ctx->stream;
+    const double t0 = now_ms();
+    if (ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess || ctx->d_bgzf_flag.ensure(1) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    }
+    const uint8_t* comp = ctx->d_bgzf_comp.p;
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+    if (ship_file(fd, 0, file_n, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, []() { return true; }, &g.n_readers)) {
+        return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    }
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    g.ship_ms = (float)(t1 - t0);
+    rala_hip_gzip_timings& tm = g.tm;
+    tm.compressed_bytes = file_n;
+    if (chain) {
+        g.chain = *chain;
+        for (const GzipJob& j : g.chain) {
+            g.text_n += j.text_n;
+            tm.max_wave_text_bytes = std::max<uint64_t>(tm.max_wave_text_bytes, j.text_n);
+        }
+        tm.chunks_confirmed = g.chain.size() - 1;
+        if (g.chain.empty() || (uint32_t)g.text_n != le32(trailer + 4)) return RALA_HIP_OK;
+    } else {
+        const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, ctx->gzip_chunk_bytes);
+        const uint64_t n_chunks = (end - deflate_off + chunk - 1) / chunk;
+        if (n_chunks >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+        if (ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess || ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess) {
+            return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        }
+        launch_gzip_find(comp, end, (file_n + 56) / 8, deflate_off, chunk, (uint32_t)n_chunks, ctx->debug_gzip_false_sync, ctx->d_gzip_starts.p, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipStreamSynchronize(s));
+        const double t2 = now_ms();
+        launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s);
+        INGEST_CHECK(hipGetLastError());
+        std::vector<uint64_t> starts(n_chunks);
+        std::vector<GzipSpan> spans(n_chunks);
+        INGEST_CHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipStreamSynchronize(s));
+        const double t3 = now_ms();
+        ctx->d_gzip_starts.release();
+        ctx->d_gzip_spans.release();
+        tm.chunks = n_chunks;
+        tm.find_ms = (float)(t2 - t1);
+        tm.decode_ms = (float)(t3 - t2);
+        for (uint64_t c = 1; c < n_chunks; ++c) tm.chunks_with_candidate += starts[c] != kGzipNoStart;
+        // the chain from chunk 0: the true chunks, their text offsets
+        uint64_t text_n = 0, end_bit = 0;
+        for (uint64_t c = 0;;) {
+            const GzipSpan& sp = spans[c];
+            if (sp.status > 1 || (sp.status == 0 && (sp.next <= c || sp.next >= n_chunks))) return RALA_HIP_OK;
+            GzipJob j;
+            j.start_bit = starts[c];
+            j.stop_bit = sp.status == 0 ? starts[sp.next] : kGzipNoStart;
+            j.text_off = text_n;
+            j.text_n = sp.text;
+            j.first = g.chain.empty() ? 1u : 0u;
+            j.pad = 0;
+            g.chain.push_back(j);
+            text_n += sp.text;
+            tm.chunks_refuted += sp.refuted;
+            tm.max_wave_text_bytes = std::max<uint64_t>(tm.max_wave_text_bytes, sp.text);
+            if (sp.status == 1) { end_bit = sp.end_bit; break; }
+            c = sp.next;
+        }
+        tm.chunks_confirmed = g.chain.size() - 1;
+        // the final block ends in the byte in front of the trailer; ISIZE
+        if ((end_bit + 7) / 8 != end || (uint32_t)text_n != le32(trailer + 4)) return RALA_HIP_OK;
+        g.text_n = text_n;
+    }
+    tm.text_bytes = g.text_n;
+    // the window: symbols (2 bytes) and text (1 byte) of it inside the quarter of what is free now
+    uint64_t window = want_window;
+    if (window == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        window = std::max<uint64_t>(64ull << 20, free_b / 12);
+    }
+    window = std::max<uint64_t>(std::min<uint64_t>(window, 1ull << 31), tm.max_wave_text_bytes);
+    if (window > (1ull << 31)) return ingest_fail(ctx, RALA_HIP_ENOMEM, "a chunk of the gzip file gives more text than a window holds");
+    window = std::min(window, std::max<uint64_t>(g.text_n, 1));
+    g.window = window;
+    const uint64_t ring = gzip_ring_symbols();
+    if (ctx->d_gzip_sym.ensure(ring + window + 64) != hipSuccess || ctx->d_gzip_text.ensure(front + window + behind) != hipSuccess ||
+        ctx->d_gzip_crc.ensure(window / gzip_segment_bytes() + 2) != hipSuccess || ctx->d_gzip_carry.ensure(ring) != hipSuccess ||
+        ctx->d_gzip_hold.ensure(front + 16) != hipSuccess) {
+        ctx->d_gzip_sym.release();
+        ctx->d_gzip_text.release();
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
+    }
+    // nothing lies in front of the first window: a marker that points there is no byte
+    INGEST_CHECK(hipMemsetD16Async((hipDeviceptr_t)ctx->d_gzip_sym.p, (unsigned short)0x8000u, ring, s));
+    *valid = true;
+    return RALA_HIP_OK;
+}
+
+// The next window's text [*lo, *lo + *n) to `text` (16-byte aligned, in ctx->d_gzip_text).  *flag != 0: the inflater refused.
+int gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* text, uint64_t* lo, uint64_t* n, uint32_t* flag) {
+    hipStream_t s = ctx->stream;
+    const uint64_t ring = gzip_ring_symbols();
+    const size_t j0 = g.next_job;
+    size_t j1 = j0;
+    uint64_t n_w = 0;
+    while (j1 < g.chain.size() && (j1 == j0 || n_w + g.chain[j1].text_n <= g.window)) n_w += g.chain[j1++].text_n;
+    const uint64_t a = g.chain[j0].text_off;
+    std::vector<GzipJob> jobs(g.chain.begin() + j0, g.chain.begin() + j1);
+    std::vector<uint64_t> text_off(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - a);
+    if (n_w > g.window) return ingest_fail(ctx, RALA_HIP_EDEVICE, "a chunk larger than the window");
+    *lo = a;
+    *n = n_w;
+    *flag = 0;
+    g.next_job = j1;
+    if (ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's chunks");
+    }
+    const double t0 = now_ms();
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    const uint64_t n_seg = (n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)jobs.size(), n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s, ring);
+    INGEST_CHECK(hipGetLastError());
+    std::vector<uint32_t> seg_crc(n_seg);
+    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    if (j1 < g.chain.size()) launch_gzip_carry(ctx->d_gzip_sym.p, text, n_w, ctx->d_gzip_carry.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    g.tm.decode_ms += (float)(t1 - t0);
+    g.tm.resolve_ms += (float)(now_ms() - t1);
+    g.reg.push_back(gzip_crc_register(seg_crc.data(), n_w));
+    g.len.push_back(n_w);
+    return RALA_HIP_OK;
+}
+
+// behind the last window: is the text the trailer's?
+bool gzip_walk_proven(const GzipWalk& g) {
+    return g.next_job == g.chain.size() && gzip_crc_chain(g.reg.data(), g.len.data(), g.reg.size()) == g.crc;
+}
+
+// ---- the text of a read file window by window: a plain file's bytes, a BGZF file's members, a gzip member's chunks ------
+// Both passes walk it: rala_hip_index_sequences and rala_hip_slice_sequences.  A window is the n bytes at text position lo
+// that are this step's, and behind them what of the next sequence_halo_bytes() the text still has (n_avail); zeros behind
+// those up to the next multiple of the tile + the halo + 64.  The gzip source inflates whole chunks: it holds the tail of
+// every inflated window back and puts it in front of the next one.
+struct TextWindow {
+    const uint8_t* text = nullptr;
+    uint64_t lo = 0, n = 0, n_avail = 0;
+    double t_kernels = 0;                   // from here on the device works on the window (what was before: the ship)
+};
+struct TextSource {
+    int kind = 0;                           // 0 plain, 1 BGZF, 2 gzip
+    int fd = -1;
+    std::string path;
+    uint32_t threads = 1;
+    uint64_t window = 0, file_n = 0, text_n = 0;
+    std::unique_ptr<BgzfFile> bg;
+    std::unique_ptr<GzipWalk> gz;
+    uint64_t lo = 0, hold = 0, front = 0;
+    double ship_ms = 0;
+    uint32_t flag = 0;                      // 8: an inflater refused
+    uint64_t windows = 0, max_window = 0;
+};
+
+uint64_t sequence_window_bytes(rala_hip_ctx* ctx) {
+    uint64_t window = (uint64_t)ctx->debug_sequence_window;
+    if (window == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        window = std::max<uint64_t>(256ull << 20, free_b / 4);
+    }
+    return std::min<uint64_t>(window, 1ull << 31);
+}
+
+// *valid = false: a gzip file this does not take (not BGZF and gzip_ok false, or one the inflaters cannot prove)
+int source_open(rala_hip_ctx* ctx, TextSource& S, bool gzip_ok, const std::vector<GzipJob>* chain, bool* valid) {
+    *valid = true;
+    S.text_n = S.file_n;
+    S.window = sequence_window_bytes(ctx);
+    uint8_t head[18] = {0};
+    const ssize_t got = pread(S.fd, head, sizeof(head), 0);
+    if (!(got >= 2 && head[0] == 0x1f && head[1] == 0x8b)) return RALA_HIP_OK;
+    *valid = bgzf_head(head, (uint64_t)got);
+    if (*valid) {
+        S.kind = 1;
+        S.bg.reset(new BgzfFile);
+        const int rc = bgzf_open(ctx, S.path.c_str(), S.threads, S.window, *S.bg, valid);
+        if (rc != RALA_HIP_OK) return rc;
+        S.text_n = S.bg->text_n;
+        S.ship_ms = S.bg->ship_ms;
+    } else if (gzip_ok) {
+        S.kind = 2;
+        S.gz.reset(new GzipWalk);
+        const uint64_t tile = sequence_tile_bytes(), halo = sequence_halo_bytes();
+        S.front = (halo + 15) / 16 * 16;
+        const int rc = gzip_walk_open(ctx, S.fd, S.path.c_str(), S.threads, (uint64_t)ctx->debug_sequence_window, S.front, tile + halo + 64 + 16, chain,
+                                      *S.gz, valid);
+        if (rc != RALA_HIP_OK) return rc;
+        S.text_n = S.gz->text_n;
+        S.ship_ms = S.gz->ship_ms;
+    }
+    return RALA_HIP_OK;
+}
+
+int source_next(rala_hip_ctx* ctx, TextSource& S, TextWindow* w) {
+    hipStream_t s = ctx->stream;
+    const uint64_t tile = sequence_tile_bytes(), halo = sequence_halo_bytes();
+    const double t0 = now_ms();
+    w->lo = S.lo;
+    if (S.kind == 2) {
+        uint8_t* const at = ctx->d_gzip_text.p + S.front;
+        uint64_t a = 0, n_w = 0;
+        const int rc = gzip_walk_next(ctx, *S.gz, at, &a, &n_w, &S.flag);
+        if (rc != RALA_HIP_OK || S.flag) return rc;
+        if (a != S.lo + S.hold) return ingest_fail(ctx, RALA_HIP_EDEVICE, "the gzip windows do not follow each other");
+        uint8_t* text = at - S.hold;
+        w->n_avail = S.hold + n_w;
+        const bool last = a + n_w == S.text_n;
+        w->n = last ? w->n_avail : w->n_avail > halo ? w->n_avail - halo : 0;
+        const uint64_t cap = (w->n + tile - 1) / tile * tile + halo + 64;
+        // What is held back is the halo, a multiple of 16, unless the windows so far were no longer than it: then all of
+        // them is held back, any number of bytes, and the text in front of `at` does not begin at a multiple of 16, where
+        // the index's and the slicer's kernels load it 16 bytes at a time.  Such a window goes to a buffer of its own.
+        if (S.hold % 16) {
+            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
+            INGEST_CHECK(hipMemcpyAsync(ctx->d_paf_text.p, text, w->n_avail, hipMemcpyDeviceToDevice, s));
+            text = ctx->d_paf_text.p;
+        }
+        INGEST_CHECK(hipMemsetAsync(text + w->n_avail, 0, cap - w->n_avail, s));
+        INGEST_CHECK(hipStreamSynchronize(s));
+        w->text = text;
+        w->t_kernels = t0;
+    } else {
+        w->n = std::min(S.window, S.text_n - S.lo);
+        w->n_avail = std::min<uint64_t>(S.text_n - S.lo, w->n + halo);
+        const uint64_t cap = (w->n + tile - 1) / tile * tile + halo + 64;
+        // what lies behind the text reads as zeros: a carriage return in the text's last byte is a base, as on the host
+        if (S.kind == 1) {
+            BgzfText bt;
+            const int rc = bgzf_text_range(ctx, *S.bg, S.lo, w->n_avail, cap, 0, S.threads, []() { return true; }, "device memory", &bt);
+            if (rc != RALA_HIP_OK) return rc;
+            if (bt.flag) { S.flag = 8; return RALA_HIP_OK; }
+            w->text = bt.text;
+            w->t_kernels = bt.t1;
+            S.ship_ms += bt.t_ship - bt.t0;
+        } else {
+            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+            if (hipMemsetAsync(ctx->d_paf_text.p + w->n_avail, 0, cap - w->n_avail, s) != hipSuccess ||
+                ship_file(S.fd, S.lo, w->n_avail, ctx->d_paf_text.p, ctx->device, S.threads, nullptr, []() { return true; }, nullptr) ||
+                hipStreamSynchronize(s) != hipSuccess) {
+                return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying " + S.path + " failed");
+            }
+            w->text = ctx->d_paf_text.p;
+            w->t_kernels = now_ms();
+            S.ship_ms += w->t_kernels - t0;
+        }
+    }
+    ++S.windows;
+    S.max_window = std::max(S.max_window, w->n_avail);
+    return RALA_HIP_OK;
+}
+
+// the window is done with: on to the next one (gzip: what was held back goes in front of it)
+int source_advance(rala_hip_ctx* ctx, TextSource& S, const TextWindow& w) {
+    S.lo = w.lo + w.n;
+    if (S.kind != 2) return RALA_HIP_OK;
+    S.hold = w.n_avail - w.n;
+    if (S.hold && S.lo < S.text_n) {
+        hipStream_t s = ctx->stream;
+        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_hold.p, w.text + w.n, S.hold, hipMemcpyDeviceToDevice, s));
+        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_text.p + S.front - S.hold, ctx->d_gzip_hold.p, S.hold, hipMemcpyDeviceToDevice, s));
+        INGEST_CHECK(hipStreamSynchronize(s));
+    }
+    return RALA_HIP_OK;
+}
+
+void source_close(rala_hip_ctx* ctx) {
+    ctx->d_paf_text.release();                  // (a window of the file: not kept)
+    ctx->d_bgzf_comp.release();
+    ctx->d_gzip_sym.release();
+    ctx->d_gzip_text.release();
+}
+
+void trace_gzip_walk(const GzipWalk& g) {
+    const rala_hip_gzip_timings& t = g.tm;
+    fprintf(stderr, "[trace] device inflate: one gzip member in %lu windows of at most %.3f GB of text, %.3f GB compressed shipped in %.1f ms, %lu "
+            "chunks (%lu with a candidate, %lu confirmed, %lu refuted), %.3f GB of text (at most %.3f GB by one wave): find %.2f ms, decode %.2f ms, "
+            "resolve %.2f ms\n", (unsigned long)g.reg.size(), g.window / 1e9, t.compressed_bytes / 1e9, g.ship_ms, (unsigned long)t.chunks,
+            (unsigned long)t.chunks_with_candidate, (unsigned long)t.chunks_confirmed, (unsigned long)t.chunks_refuted, t.text_bytes / 1e9,
+            t.max_wave_text_bytes / 1e9, t.find_ms, t.decode_ms, t.resolve_ms);
 }
 
 }  // namespace
@@ -1015,72 +1351,48 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     struct stat st;
     if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
     const uint64_t file_n = (uint64_t)st.st_size;
-    // the window over the text: the overlap ingest's rule, and every count of a window in 32 bits
-    uint64_t window = (uint64_t)ctx->debug_sequence_window;
-    if (window == 0) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        window = std::max<uint64_t>(256ull << 20, free_b / 4);
-    }
-    window = std::min<uint64_t>(window, 1ull << 31);
-    // a gzip file: BGZF is inflated on the device, anything else is the host reader's - known from the first 18 bytes
-    std::unique_ptr<BgzfFile> bg;
-    uint8_t head[18] = {0};
-    const ssize_t got = pread(file.fd, head, sizeof(head), 0);
-    if (got >= 2 && head[0] == 0x1f && head[1] == 0x8b) {
-        bool valid = bgzf_head(head, (uint64_t)got);
-        if (valid) {
-            bg.reset(new BgzfFile);
-            const int rc = bgzf_open(ctx, path, threads, window, *bg, &valid);
-            if (rc != RALA_HIP_OK) { ctx->d_bgzf_comp.release(); return rc; }
-        }
-        if (!valid) {
-            ctx->d_bgzf_comp.release();
+    // the window over the text: the overlap ingest's rule, and every count of a window in 32 bits.  A gzip file: BGZF is
+    // inflated on the device, so is (option gzip_on_device) any other file of one member; what is left is the host reader's
+    TextSource S;
+    S.fd = file.fd;
+    S.path = path;
+    S.threads = threads;
+    S.file_n = file_n;
+    {
+        bool valid = true;
+        const int rc = source_open(ctx, S, ctx->gzip_on_device, nullptr, &valid);
+        if (S.gz) ctx->gzip_tm = S.gz->tm;
+        if (rc != RALA_HIP_OK || !valid) {
+            source_close(ctx);
+            if (rc != RALA_HIP_OK) return rc;
             *irregular = 8;
             return RALA_HIP_OK;
         }
     }
     SequenceRun R;
     R.fastq = format == 1;
-    R.text_n = bg ? bg->text_n : file_n;
+    R.text_n = S.text_n;
     hipStream_t s = ctx->stream;
-    const uint64_t tile = sequence_tile_bytes();
-    double ship_ms = bg ? bg->ship_ms : 0, kernel_ms = 0;
+    double kernel_ms = 0;
     uint32_t flags = 0;
     int rc = RALA_HIP_OK;
-    for (uint64_t lo = 0; lo < R.text_n && rc == RALA_HIP_OK && !flags; lo += window) {
-        const uint64_t n = std::min(window, R.text_n - lo);
-        const uint64_t n_avail = std::min<uint64_t>(R.text_n - lo, n + sequence_halo_bytes());
-        const uint64_t cap = (n + tile - 1) / tile * tile + sequence_halo_bytes() + 64;
-        const uint8_t* text = nullptr;
-        const double t0 = now_ms();
-        double t1 = t0;
-        // what lies behind the text reads as zeros: a carriage return in the text's last byte is a base, as on the host
-        if (bg) {
-            BgzfText bt;
-            rc = bgzf_text_range(ctx, *bg, lo, n_avail, cap, 0, threads, []() { return true; }, "device memory", &bt);
-            if (rc != RALA_HIP_OK) break;
-            if (bt.flag) { flags = 8; break; }
-            text = bt.text;
-            t1 = bt.t1;
-            ship_ms += bt.t_ship - bt.t0;
-        } else {
-            if (ctx->d_paf_text.ensure(cap) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text"); break; }
-            if (hipMemsetAsync(ctx->d_paf_text.p + n_avail, 0, cap - n_avail, s) != hipSuccess ||
-                ship_file(file.fd, lo, n_avail, ctx->d_paf_text.p, ctx->device, threads, nullptr, []() { return true; }, nullptr) ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                rc = ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
-                break;
-            }
-            text = ctx->d_paf_text.p;
-            t1 = now_ms();
-            ship_ms += t1 - t0;
-        }
-        rc = index_window(ctx, R, text, lo, n, n_avail, &flags);
-        kernel_ms += now_ms() - t1;
+    // (a gzip member is inflated to its end even where the index has given up: CRC32 and ISIZE say whether that was its text)
+    while (S.lo < R.text_n && rc == RALA_HIP_OK && !S.flag && (!flags || S.gz)) {
+        TextWindow w;
+        rc = source_next(ctx, S, &w);
+        if (rc != RALA_HIP_OK || S.flag) break;
+        if (!flags) rc = index_window(ctx, R, w.text, w.lo, w.n, w.n_avail, &flags);
+        if (rc == RALA_HIP_OK) rc = source_advance(ctx, S, w);
+        kernel_ms += now_ms() - w.t_kernels;
     }
-    ctx->d_paf_text.release();                  // (a window of the file: not kept)
-    ctx->d_bgzf_comp.release();
+    if (S.gz) {
+        ctx->gzip_tm = S.gz->tm;
+        if (rc == RALA_HIP_OK && !S.flag && !gzip_walk_proven(*S.gz)) S.flag = 8;
+        if (getenv("RALA_HIP_TRACE")) trace_gzip_walk(*S.gz);
+    }
+    if (S.flag) flags = 8;
+    const double ship_ms = S.ship_ms;
+    source_close(ctx);
     if (rc != RALA_HIP_OK) return rc;
     if (!flags && R.fastq && (R.n_events & 3u) != 0) flags = kSeqNotFourLines;       // a record cut after 1, 2 or 3 lines
     const double tf = now_ms();
@@ -1120,6 +1432,16 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     ctx->n_seq_records = R.n_records;
     ctx->n_seq_name_bytes = R.name_bytes;
     ctx->seq_index_valid = true;
+    ctx->seq_source = S.kind;
+    ctx->seq_fastq = R.fastq;
+    ctx->seq_file_n = file_n;
+    ctx->seq_text_n = R.text_n;
+    ctx->seq_n_stripped = R.n_stripped;
+    ctx->seq_gzip_chain.clear();
+    if (S.gz) {
+        ctx->seq_gzip_chain.swap(S.gz->chain);
+        ctx->seq_gzip_crc = S.gz->crc;
+    }
     *n_records = R.n_records;
     *name_bytes = R.name_bytes;
     return RALA_HIP_OK;
@@ -1144,6 +1466,168 @@ int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* ou
     if (!ctx || !out) return RALA_HIP_EINVAL;
     *out = ctx->seq_tm;
     return RALA_HIP_OK;
+}
+
+int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t* wanted, uint64_t n_wanted, const uint64_t* base_off,
+                             uint8_t* bases, uint32_t threads, int* irregular) {
+    if (!ctx || !path || !irregular || !base_off || (n_wanted && !wanted) || (!bases && base_off[n_wanted])) return RALA_HIP_EINVAL;
+    *irregular = 0;
+    ctx->slice_info = rala_hip_sequence_slice_info();
+    if (!ctx->seq_index_valid) { *irregular = 64; return RALA_HIP_OK; }
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t n_rec = ctx->n_seq_records;
+    // what the index holds of the wanted reads (none of them empty): where their text lies, where their bases go
+    std::vector<uint64_t> data_off(n_rec), span(n_rec), data_stripped(n_rec);
+    std::vector<uint32_t> length(n_rec);
+    if (n_rec) {
+        INGEST_CHECK(hipMemcpy(data_off.data(), ctx->d_seq_data_off.p, n_rec * 8, hipMemcpyDeviceToHost));
+        INGEST_CHECK(hipMemcpy(span.data(), ctx->d_seq_span.p, n_rec * 8, hipMemcpyDeviceToHost));
+        INGEST_CHECK(hipMemcpy(data_stripped.data(), ctx->d_seq_data_stripped.p, n_rec * 8, hipMemcpyDeviceToHost));
+        INGEST_CHECK(hipMemcpy(length.data(), ctx->d_seq_length.p, n_rec * 4, hipMemcpyDeviceToHost));
+    }
+    std::vector<uint64_t> w_off, w_end, w_adj, w_base;
+    if (base_off[0] != 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "base_off does not begin at 0");
+    for (uint64_t k = 0; k < n_wanted; ++k) {
+        const uint64_t r = wanted[k];
+        if (r >= n_rec || (k && r <= wanted[k - 1])) return ingest_fail(ctx, RALA_HIP_EINVAL, "wanted reads not ascending records of the index");
+        if (base_off[k + 1] - base_off[k] != length[r]) return ingest_fail(ctx, RALA_HIP_EINVAL, "base_off is not the scan of the wanted reads' lengths");
+        if (!length[r]) continue;
+        w_off.push_back(data_off[r]);
+        w_end.push_back(data_off[r] + span[r]);
+        w_adj.push_back(base_off[k] - data_off[r] + data_stripped[r]);
+        w_base.push_back(base_off[k]);
+    }
+    const uint64_t n_w = w_off.size(), n_bases = base_off[n_wanted];
+    Fd file;
+    file.fd = open(path, O_RDONLY);
+    struct stat st;
+    if (file.fd < 0 || fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode) || (uint64_t)st.st_size != ctx->seq_file_n) { *irregular = 64; return RALA_HIP_OK; }
+    if (!n_w) return RALA_HIP_OK;
+    // whatever way this call ends, the wanted reads, a window's bases and the source's buffers do not stay the context's
+    struct Release {
+        rala_hip_ctx* ctx;
+        ~Release() {
+            source_close(ctx);
+            ctx->d_slice_out.release();
+            for (int k = 0; k < 3; ++k) ctx->d_slice_w[k].release();
+        }
+    } release{ctx};
+    for (int k = 0; k < 3; ++k) INGEST_CHECK(ctx->d_slice_w[k].ensure(n_w));
+    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[0].p, w_off.data(), n_w * 8, hipMemcpyHostToDevice));
+    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[1].p, w_end.data(), n_w * 8, hipMemcpyHostToDevice));
+    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[2].p, w_adj.data(), n_w * 8, hipMemcpyHostToDevice));
+    TextSource S;
+    S.fd = file.fd;
+    S.path = path;
+    S.threads = threads;
+    S.file_n = (uint64_t)st.st_size;
+    {
+        bool valid = true;
+        const int rc = source_open(ctx, S, ctx->seq_source == 2, ctx->seq_source == 2 ? &ctx->seq_gzip_chain : nullptr, &valid);
+        if (rc != RALA_HIP_OK || !valid || S.kind != ctx->seq_source || S.text_n != ctx->seq_text_n ||
+            (S.gz && (S.gz->crc != ctx->seq_gzip_crc || S.gz->chain.back().stop_bit != kGzipNoStart))) {
+            if (rc != RALA_HIP_OK) return rc;
+            *irregular = valid && S.kind == ctx->seq_source && !S.gz ? 64 : 8;
+            return RALA_HIP_OK;
+        }
+    }
+    const uint64_t tile = sequence_tile_bytes();
+    uint64_t n_stripped = 0, k_lo = 0;
+    bool last_is_newline = true;
+    double kernel_ms = 0, gather_ms = 0, copy_ms = 0;
+    uint32_t flags = 0;
+    int rc = RALA_HIP_OK;
+    INGEST_CHECK(ctx->d_seq_flags.ensure(1));
+    INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+    // (a gzip member is inflated to its end, wanted reads or not: a window's markers point into the one before, and CRC32
+    // and ISIZE say at the end whether this was the text the index saw)
+    while (S.lo < S.text_n && rc == RALA_HIP_OK && !S.flag && !flags && (k_lo < n_w || S.gz)) {
+        TextWindow w;
+        rc = source_next(ctx, S, &w);
+        if (rc != RALA_HIP_OK || S.flag) break;
+        const uint64_t n_tiles = (w.n + tile - 1) / tile;
+        if (n_tiles && k_lo < n_w) {
+            // the stripped bytes in front of every tile, as the index counted them
+            if (ctx->d_seq_tile[0].ensure(n_tiles + 2) != hipSuccess || ctx->d_seq_tile[1].ensure(n_tiles + 2) != hipSuccess ||
+                ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)) != hipSuccess) {
+                rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the tiles' counts");
+                break;
+            }
+            launch_sequence_count(w.text, w.n, last_is_newline, ctx->seq_fastq, ctx->d_seq_tile[0].p, ctx->d_seq_tile[1].p, s);
+            launch_exclusive_scan(ctx->d_seq_tile[1].p, ctx->d_seq_tile[1].p, n_tiles, ctx->d_scan_ws.p, s);
+            uint32_t stripped = 0;
+            uint8_t last = 0;
+            if (hipMemcpyAsync(&stripped, ctx->d_seq_tile[1].p + n_tiles, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(&last, w.text + w.n - 1, 1, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+                rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "counting a window's stripped bytes failed");
+                break;
+            }
+            // the wanted reads with text in [lo, hi), and the share of the output that is this window's
+            const uint64_t lo = w.lo, hi = w.lo + w.n;
+            while (k_lo < n_w && w_end[k_lo] <= lo) ++k_lo;
+            const uint64_t k_hi = std::lower_bound(w_off.begin() + k_lo, w_off.end(), hi) - w_off.begin();
+            if (k_lo < k_hi) {
+                const uint64_t out_lo = w_off[k_lo] >= lo ? w_base[k_lo] : lo - n_stripped + w_adj[k_lo];
+                const uint64_t out_hi = w_end[k_hi - 1] <= hi ? (k_hi < n_w ? w_base[k_hi] : n_bases) : hi - (n_stripped + stripped) + w_adj[k_hi - 1];
+                if (out_hi < out_lo || out_hi > n_bases || out_hi - out_lo > w.n) { flags = kSeqSliceMismatch; break; }
+                const uint64_t out_n = out_hi - out_lo;
+                if (out_n) {
+                    if (ctx->d_slice_out.ensure(out_n) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's bases"); break; }
+                    SequenceGather G;
+                    G.text = w.text; G.n = w.n; G.text_off = lo;
+                    G.tile_stripped0 = ctx->d_seq_tile[1].p; G.stripped0 = n_stripped;
+                    G.w_off = ctx->d_slice_w[0].p; G.w_end = ctx->d_slice_w[1].p; G.w_adj = ctx->d_slice_w[2].p;
+                    G.k_lo = k_lo; G.k_hi = k_hi;
+                    G.out_lo = out_lo; G.out_n = out_n; G.out = ctx->d_slice_out.p; G.flags = ctx->d_seq_flags.p;
+                    const double tg = now_ms();
+                    launch_sequence_gather(G, s);
+                    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "the gather kernel failed"); break; }
+                    const double tc = now_ms();
+                    if (hipMemcpyAsync(bases + out_lo, ctx->d_slice_out.p, out_n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+                        rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "copying a window's bases failed");
+                        break;
+                    }
+                    gather_ms += tc - tg;
+                    copy_ms += now_ms() - tc;
+                    ctx->slice_info.bases += out_n;
+                }
+            }
+            n_stripped += stripped;
+            last_is_newline = last == '\n';
+        }
+        if (rc == RALA_HIP_OK) rc = source_advance(ctx, S, w);
+        kernel_ms += now_ms() - w.t_kernels;
+    }
+    if (S.gz && rc == RALA_HIP_OK && !S.flag && !flags && !gzip_walk_proven(*S.gz)) S.flag = 8;
+    if (S.gz) ctx->gzip_tm = S.gz->tm;
+    if (rc != RALA_HIP_OK) return rc;
+    if (!S.flag && !flags && ctx->slice_info.bases != n_bases) flags = kSeqSliceMismatch;
+    ctx->slice_info.windows = S.windows;
+    ctx->slice_info.max_window_text_bytes = S.max_window;
+    ctx->slice_info.ship_ms = (float)S.ship_ms;
+    ctx->slice_info.kernel_ms = (float)kernel_ms;
+    ctx->slice_info.gather_ms = (float)gather_ms;
+    ctx->slice_info.copy_ms = (float)copy_ms;
+    if (getenv("RALA_HIP_TRACE")) {
+        fprintf(stderr, "[trace] device sequence slice: %lu windows of at most %.3f GB of text, %lu bases of %lu reads, ship %.1f ms, device %.2f ms "
+                "(gather %.2f ms, bases to the host %.2f ms) (flags %u)\n", (unsigned long)S.windows, S.max_window / 1e9,
+                (unsigned long)ctx->slice_info.bases, (unsigned long)n_wanted, S.ship_ms, kernel_ms, gather_ms, copy_ms, S.flag | flags);
+    }
+    if (S.flag || flags) *irregular = (int)(S.flag | flags);
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_sequence_slice_info(rala_hip_ctx* ctx, rala_hip_sequence_slice_info* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->slice_info;
+    return RALA_HIP_OK;
+}
+
+uint32_t rala_hip_crc32_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
+    if (n && (!reg || !len)) return 0;
+    return gzip_crc_chain(reg, len, n);
 }
 
 int rala_hip_get_ingest_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out) {

@@ -559,6 +559,25 @@ void launch_sequence_names(const uint8_t* text, uint64_t text_off, const uint64_
 // flags: kSeqNotFourLines (a quality line of another length than its bases), kSeqTooLong
 void launch_sequence_finish(uint64_t n_records, uint64_t n_events, uint64_t text_n, uint64_t stripped_n, bool fastq, const SequenceColumns& c,
                             uint64_t* data_span, uint32_t* length, uint32_t* flags, hipStream_t s);
+// The second pass: the bases of the wanted reads out of one window of the text (launch_sequence_count's layout: n bytes at
+// text, byte 0 at text_off of the whole text; tile_stripped0 the exclusive scan of its counts, stripped0 the stripped bytes of
+// the windows in front).  Wanted read k (ascending, none empty) holds the text [w_off[k], w_end[k]); a byte at text position p
+// that is not stripped, with s stripped bytes in front of it, goes to out[p - s + w_adj[k] - out_lo] (w_adj = where the
+// read's bases begin in the packed output - data_off + data_stripped; out: the out_n bytes of this window's share).  Only
+// reads k_lo <= k < k_hi are looked at.  flags |= kSeqSliceMismatch: a byte fell outside out - the text is not the index's.
+constexpr uint32_t kSeqSliceMismatch = 32;
+struct SequenceGather {
+    const uint8_t* text;
+    uint64_t n, text_off;
+    const uint32_t* tile_stripped0;
+    uint64_t stripped0;
+    const uint64_t *w_off, *w_end, *w_adj;
+    uint64_t k_lo, k_hi;
+    uint64_t out_lo, out_n;
+    uint8_t* out;
+    uint32_t* flags;
+};
+void launch_sequence_gather(const SequenceGather& G, hipStream_t s);
 
 // ---- BGZF members -> text (inflate_kernels.hip) ---------------------------------------------
 // one gzip member of a BGZF file: its raw-deflate bytes at comp + comp_off (deflate_len of them, then CRC32 and ISIZE), its
@@ -583,9 +602,10 @@ struct GzipSpan {
     uint32_t next, status, refuted, pad;
 };
 // one true chunk for the writing pass: decoded from start_bit to the block boundary stop_bit (kGzipNoStart: to the final block's
-// end), its text_n symbols to sym + text_off; job 0 is the stream's first chunk
+// end), its text_n symbols to sym + text_off; first != 0: the stream's first chunk (nothing lies in front of its text)
 struct GzipJob {
     uint64_t start_bit, stop_bit, text_off, text_n;
+    uint32_t first, pad;
 };
 // starts[c], c < n_chunks: where chunk c's first candidate block begins (chunk 0: 8 * deflate_off), kGzipNoStart = none;
 // false_sync n != 0 (tests): every n-th chunk is given its first bit as its start
@@ -596,10 +616,22 @@ void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts
 void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, uint32_t n_jobs, uint16_t* sym, uint32_t* flags, hipStream_t s);
 // text_off[j] = job j's text offset; sym (readable 64 symbols behind text_n) -> text, and the CRC register of every
 // gzip_segment_bytes() of it in seg_crc; flags |= 8: a symbol that points in front of the text
+// A WINDOW of the text (the jobs of a run of consecutive true chunks): front = gzip_ring_symbols() symbols in front of the
+// window's first one hold the bytes in front of the window (the carry; 0x8000: no such byte, the file's text begins behind
+// it), text_off[] counts from the buffer's start (the first job's is `front`) and text_n is the window's; front = 0: the
+// whole text at once.
 void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
-                         uint32_t* flags, hipStream_t s);
+                         uint32_t* flags, hipStream_t s, uint64_t front = 0);
 uint32_t gzip_segment_bytes();
+uint32_t gzip_ring_symbols();
 uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n);        // (host) the text's CRC32
+// the carry of the next window: the last gzip_ring_symbols() of (the carry in front of sym, then the window's text_n bytes at
+// text) as symbols, through tmp (that many symbols) to the front of sym
+void launch_gzip_carry(uint16_t* sym, const uint8_t* text, uint64_t text_n, uint16_t* tmp, hipStream_t s);
+// (host) the CRC register (from zero, no final inversion) of text_n bytes from launch_gzip_resolve's segment registers
+uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n);
+// (host) the CRC32 of pieces laid end to end from each piece's register (from zero, no final inversion) and length
+uint32_t gzip_crc_chain(const uint32_t* reg, const uint64_t* len, uint64_t n);
 
 // ---- scans (scan_kernels.hip) --------------------------------------------------
 // exclusive prefix sum of n uint32 values; out may alias in; out[n] receives the total

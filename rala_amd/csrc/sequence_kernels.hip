@@ -193,6 +193,132 @@ __global__ __launch_bounds__(kBlock) void seq_finish_kernel(uint64_t n_records, 
     length[r] = (uint32_t)len;
 }
 
+// ---- the second pass: the wanted reads' bases out of a window of the text ------------------------------------------------
+// One workgroup per tile of 16 KB, 64 bytes per thread in 16-byte loads.  Where a byte goes is a function of what the index
+// holds: its position, the stripped bytes in front of it (the tile's count behind a scan, as the record pass has them) and
+// its read's data_off / data_stripped (G.w_adj) - a read that lies over many tiles or windows needs no carry.  The tile's
+// wanted reads are found by binary search; their kept bytes are compacted into LDS behind a block scan, every read's share
+// of the tile a RUN (first rank, first output index), and go out rank by rank: neighbouring lanes, neighbouring bytes.  A
+// tile with more than kMaxRuns wanted reads (reads of a few bytes) stores straight from the registers instead.
+constexpr uint32_t kMaxRuns = 256;
+
+// bits [a, b) of a 64-bit mask, 0 <= a < b <= 64
+__device__ __forceinline__ uint64_t bit_range(uint32_t a, uint32_t b) {
+    return (b >= 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull);
+}
+
+__global__ __launch_bounds__(kBlock) void seq_gather_kernel(SequenceGather G) {
+    __shared__ __align__(16) uint8_t stage[kTile];
+    __shared__ uint32_t run_rank[kMaxRuns], run_out[kMaxRuns];
+    __shared__ uint32_t tmp[kBlock / 64 + 1];
+    __shared__ uint64_t k_range[2];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
+    const uint64_t t1 = t0 + kTile < G.n ? t0 + kTile : G.n;
+    const uint64_t T0 = G.text_off + t0, T1 = G.text_off + t1;
+    // the wanted reads with text in this tile: [first whose end lies behind T0, first that starts at or behind T1)
+    if (tid < 2) {
+        uint64_t lo = G.k_lo, hi = G.k_hi;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            const bool left = tid == 0 ? G.w_end[mid] <= T0 : G.w_off[mid] < T1;
+            if (left) lo = mid + 1; else hi = mid;
+        }
+        k_range[tid] = lo;
+    }
+    __syncthreads();
+    const uint64_t ka = k_range[0], kb = k_range[1];
+    if (ka >= kb) return;                                           // (the whole workgroup: no wanted read here)
+    const bool direct = kb - ka > kMaxRuns;
+    const uint64_t j0 = t0 + tid * kSeg;
+    const uint64_t P0 = G.text_off + j0, P1 = P0 + kSeg;
+    uint32_t w[16];
+    uint64_t stripped = 0, valid = 0;
+    if (j0 < t1) {
+        const uint4* p = (const uint4*)(G.text + j0);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint4 v = p[k];
+            w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+        }
+        const uint64_t nl = byte_mask(w, 0x0A0A0A0Au), cr = byte_mask(w, 0x0D0D0D0Du);
+        valid = j0 + kSeg > t1 ? (1ull << (t1 - j0)) - 1ull : ~0ull;
+        const uint64_t next_nl = G.text[j0 + kSeg] == '\n' ? 1ull << 63 : 0ull;
+        stripped = (nl | (cr & ((nl >> 1) | next_nl))) & valid;
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 16; ++k) w[k] = 0;
+    }
+    // the thread's first read, and the bytes of its 64 that lie in a wanted read
+    uint64_t k0 = kb;
+    if (j0 < t1) {
+        uint64_t lo = ka, hi = kb;
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (G.w_end[mid] <= P0) lo = mid + 1; else hi = mid;
+        }
+        k0 = lo;
+    }
+    uint64_t sel = 0;
+    for (uint64_t k = k0; k < kb; ++k) {
+        const uint64_t off = G.w_off[k], end = G.w_end[k];
+        if (off >= P1) break;
+        sel |= bit_range((uint32_t)((off > P0 ? off : P0) - P0), (uint32_t)((end < P1 ? end : P1) - P0));
+        if (end >= P1) break;
+    }
+    sel &= valid & ~stripped;
+    // (both counts of a tile are at most 16384: they ride in one word)
+    uint32_t total;
+    const uint32_t before = block_scan_excl<(int)kBlock>(((uint32_t)__popcll(stripped) << 16) | (uint32_t)__popcll(sel), OpAdd(), 0u, tmp, total);
+    const uint64_t s0 = G.stripped0 + G.tile_stripped0[blockIdx.x] + (before >> 16);
+    const uint32_t rank0 = before & 0xFFFFu, n_sel = total & 0xFFFFu;
+    bool outside = false;
+    for (uint64_t k = k0; k < kb; ++k) {
+        const uint64_t off = G.w_off[k], end = G.w_end[k];
+        if (off >= P1) break;
+        const uint64_t adj = G.w_adj[k] - G.out_lo;
+        if (direct) {
+            const uint64_t mine = sel & bit_range((uint32_t)((off > P0 ? off : P0) - P0), (uint32_t)((end < P1 ? end : P1) - P0));
+#pragma unroll
+            for (uint32_t b = 0; b < 64; ++b) {
+                if ((mine >> b) & 1ull) {
+                    const uint64_t o = P0 + b - (s0 + (uint64_t)__popcll(stripped & ((1ull << b) - 1ull))) + adj;
+                    if (o < G.out_n) G.out[o] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+                    else outside = true;
+                }
+            }
+        } else if (off >= P0 || tid == 0) {
+            // the read's first byte in this tile is among this thread's: its run
+            const uint32_t a = (uint32_t)((off > P0 ? off : P0) - P0);
+            const uint64_t below = (1ull << a) - 1ull;
+            const uint64_t o = P0 + a - (s0 + (uint64_t)__popcll(stripped & below)) + adj;
+            run_rank[k - ka] = rank0 + (uint32_t)__popcll(sel & below);
+            run_out[k - ka] = o < G.out_n ? (uint32_t)o : 0xFFFFFFFFu;
+        }
+        if (end >= P1) break;
+    }
+    if (!direct) {
+        uint32_t r = rank0;
+#pragma unroll
+        for (uint32_t b = 0; b < 64; ++b) {
+            if ((sel >> b) & 1ull) stage[r++] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+        }
+        __syncthreads();
+        const uint32_t n_runs = (uint32_t)(kb - ka);
+        for (uint32_t c = tid; c < n_sel; c += kBlock) {
+            uint32_t lo = 0, hi = n_runs;                           // the last run that begins at or in front of rank c
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (run_rank[mid] <= c) lo = mid; else hi = mid;
+            }
+            const uint64_t o = (uint64_t)run_out[lo] + (c - run_rank[lo]);
+            if (o < G.out_n) G.out[o] = stage[c];
+            else outside = true;
+        }
+    }
+    if (outside) atomicOr(G.flags, kSeqSliceMismatch);
+}
+
 }  // namespace
 
 uint32_t sequence_tile_bytes() { return kTile; }
@@ -227,6 +353,12 @@ void launch_sequence_finish(uint64_t n_records, uint64_t n_events, uint64_t text
     const dim3 grid((uint32_t)((n_records + kBlock - 1) / kBlock));
     if (fastq) hipLaunchKernelGGL(seq_finish_kernel<true>, grid, dim3(kBlock), 0, s, n_records, n_events, text_n, stripped_n, c, data_span, length, flags);
     else hipLaunchKernelGGL(seq_finish_kernel<false>, grid, dim3(kBlock), 0, s, n_records, n_events, text_n, stripped_n, c, data_span, length, flags);
+}
+
+void launch_sequence_gather(const SequenceGather& G, hipStream_t s) {
+    const uint32_t tiles = (uint32_t)((G.n + kTile - 1) / kTile);
+    if (!tiles || G.k_lo >= G.k_hi) return;
+    hipLaunchKernelGGL(seq_gather_kernel, dim3(tiles), dim3(kBlock), 0, s, G);
 }
 
 }  // namespace rala_hip

@@ -34,6 +34,7 @@ SYMBOLS = (
     "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
+    "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",
     "rala_hip_mg_destroy", "rala_hip_mg_last_error", "rala_hip_mg_set_reads", "rala_hip_mg_slice_cuts",
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
     "rala_hip_mg_owner_context",
@@ -86,6 +87,15 @@ class GzipTimings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("find_ms", "decode_ms", "resolve_ms")] + [(n, ctypes.c_uint64) for n in (
         "compressed_bytes", "text_bytes", "chunks", "chunks_with_candidate", "chunks_confirmed", "chunks_refuted",
         "max_wave_text_bytes")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SequenceSliceInfo(ctypes.Structure):
+    """rala_hip_sequence_slice_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("windows", "max_window_text_bytes", "bases")] + [(n, ctypes.c_float) for n in (
+        "ship_ms", "kernel_ms", "gather_ms", "copy_ms")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -170,6 +180,10 @@ def lib(build=True):
         L.rala_hip_index_sequences.argtypes = [vp, ctypes.c_char_p, i32, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32)]
         L.rala_hip_get_sequence_index.argtypes = [vp] + [vp] * 6
         L.rala_hip_get_sequence_timings.argtypes = [vp, ctypes.POINTER(IngestTimings)]
+        L.rala_hip_slice_sequences.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, vp, u32, ctypes.POINTER(i32)]
+        L.rala_hip_get_sequence_slice_info.argtypes = [vp, ctypes.POINTER(SequenceSliceInfo)]
+        L.rala_hip_crc32_chain.argtypes = [vp, vp, u64]
+        L.rala_hip_crc32_chain.restype = u32
         _lib = L
     return _lib
 
@@ -326,6 +340,31 @@ class Context:
         names = [raw[int(o):int(o) + int(k)] for o, k in zip(name_off, name_len)]
         self.n_reads = n.value
         return 0, {"names": names, "name_off": name_off, "length": length, "data_off": data_off, "data_span": data_span}
+
+    def slice_sequences(self, path, wanted, length, threads=4):
+        """rala_hip_slice_sequences: the bases of the reads `wanted` (ascending records of the current index; length = the
+        index's lengths) cut out of the file on the device -> (irregular, bases, base_off); bases (None when refused) is one
+        uint8 array, read wanted[k]'s bases are bases[base_off[k]:base_off[k + 1]]"""
+        wanted = np.ascontiguousarray(wanted, dtype=np.uint64)
+        base_off = np.zeros(len(wanted) + 1, dtype=np.uint64)
+        np.cumsum(np.asarray(length, dtype=np.uint64)[wanted.astype(np.int64)], out=base_off[1:])
+        bases = np.zeros(max(int(base_off[-1]), 1), dtype=np.uint8)
+        irregular = ctypes.c_int(0)
+        self._check(self.L.rala_hip_slice_sequences(self.h, os.fsencode(path), wanted.ctypes.data, len(wanted), base_off.ctypes.data,
+                                                    bases.ctypes.data, threads, ctypes.byref(irregular)))
+        if irregular.value:
+            return irregular.value, None, base_off
+        return 0, bases[:int(base_off[-1])], base_off
+
+    def sequence_slice_info(self):
+        t = SequenceSliceInfo()
+        self._check(self.L.rala_hip_get_sequence_slice_info(self.h, ctypes.byref(t)))
+        return t.as_dict()
+
+    def gzip_timings(self):
+        t = GzipTimings()
+        self._check(self.L.rala_hip_get_gzip_timings(self.h, ctypes.byref(t)))
+        return t.as_dict()
 
     def sequence_timings(self):
         t = IngestTimings()
@@ -694,3 +733,12 @@ def run_ranks(ranks, sens_slices=None):
         msgs = [L.rala_hip_mg_last_error(r.h).decode() for r in ranks]
         raise RalaHipError(rc, " | ".join(m for m in msgs if m))
     return int(pairs.value)
+
+
+def crc32_chain(reg, length):
+    """rala_hip_crc32_chain (no device): the CRC32 of pieces laid end to end from every piece's register (from zero, no final
+    inversion) and length"""
+    reg = np.ascontiguousarray(reg, dtype=np.uint32)
+    length = np.ascontiguousarray(length, dtype=np.uint64)
+    assert len(reg) == len(length)
+    return int(lib().rala_hip_crc32_chain(reg.ctypes.data, length.ctypes.data, len(reg)))

@@ -264,6 +264,11 @@ bool Graph::index_sequences() {
                        io::has_suffix(sequences_path_, ".fastq.gz") || io::has_suffix(sequences_path_, ".fq.gz");
     uint64_t n = 0, name_bytes = 0;
     int irregular = 0;
+    // a .gz file that is not BGZF - one member, what gzip, pigz and basecallers write - is taken only where
+    // io::device_gzip_wanted() (the windowed speculative inflater).  The option is only ever raised here, as the overlap ingest
+    // raises it for itself where the same switch is on: whoever set it on this context keeps it
+    const bool gzip_wanted = io::has_suffix(sequences_path_, ".gz") && io::device_gzip_wanted();
+    if (gzip_wanted) check(ctx_, rala_hip_set_option(ctx_, "gzip_on_device", 1), "initialize");
     // (several GPUs: the main context indexes the file; rala_hip_mg_set_reads receives the lengths as always)
     const int rc = rala_hip_index_sequences(ctx_, sequences_path_.c_str(), fastq ? 1 : 0, std::max(1u, num_threads_), &n, &name_bytes, &irregular);
     if (rc != RALA_HIP_OK || irregular) return false;
@@ -296,7 +301,10 @@ bool Graph::index_sequences() {
             }
         }
         if (fd >= 0) close(fd);
-        if (!ok) { sequence_index_ = io::SequenceIndex(); return false; }
+        // no BGZF members: the index was made from a single gzip member (gzip_wanted, or the device had said irregular) -
+        // the second pass is the device's as well (rala_hip_slice_sequences), the host slicer cannot seek in such a file
+        sequence_index_gzip_ = !ok && gzip_wanted;
+        if (!ok && !gzip_wanted) { sequence_index_ = io::SequenceIndex(); return false; }
     }
     names_.reserve(n);
     read_len_ = ix.length;
@@ -626,9 +634,23 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         // the device indexed the file: the bases of the reads the graph keeps are cut out of it, nothing is parsed again
         std::vector<uint64_t> wanted;
         for (uint64_t i = 0; i < n; ++i) if (read_to_node[i] >= 0) wanted.push_back(i);
-        std::vector<std::string> bases;
-        sliced = io::slice_sequences(sequences_path_, sequence_index_, wanted, std::max(1u, num_threads_), bases);
-        for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], names_[wanted[w]], bases[w]);
+        if (sequence_index_gzip_) {
+            // a single gzip member: inflated again and cut on the device; any refusal (the file changed, no room) is the host reader's
+            std::vector<uint64_t> base_off(wanted.size() + 1, 0);
+            for (size_t w = 0; w < wanted.size(); ++w) base_off[w + 1] = base_off[w] + sequence_index_.length[wanted[w]];
+            std::vector<uint8_t> packed(base_off.back() + 1);
+            int irregular = 0;
+            sliced = rala_hip_slice_sequences(ctx_, sequences_path_.c_str(), wanted.data(), wanted.size(), base_off.data(), packed.data(),
+                                              std::max(1u, num_threads_), &irregular) == RALA_HIP_OK && !irregular;
+            // (read by read out of the packed buffer: no second copy of all the kept bases)
+            for (size_t w = 0; sliced && w < wanted.size(); ++w) {
+                keep(wanted[w], names_[wanted[w]], std::string((const char*)packed.data() + base_off[w], base_off[w + 1] - base_off[w]));
+            }
+        } else {
+            std::vector<std::string> bases;
+            sliced = io::slice_sequences(sequences_path_, sequence_index_, wanted, std::max(1u, num_threads_), bases);
+            for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], names_[wanted[w]], bases[w]);
+        }
     }
     uint64_t seq_id = 0;
     if (!sliced) read_sequences(sequences_path_, [&](const std::string& name, const std::string& data) {

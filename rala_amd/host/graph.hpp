@@ -88,6 +88,7 @@ private:
     io::NameTable name_table_;
     io::OverlapColumns overlaps_;       // parsed once
     io::SequenceIndex sequence_index_;  // where the reads' bases lie in the file (the device indexed it; empty: the host reader did)
+    bool sequence_index_gzip_ = false;  // ... of a single gzip member's text: the second pass is rala_hip_slice_sequences
     bool index_sequences();
 
     AssemblyGraph graph_;
