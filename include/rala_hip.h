@@ -209,6 +209,19 @@ int rala_hip_get_gzip_timings(rala_hip_ctx* ctx, rala_hip_gzip_timings* out);
  * it: ID1 ID2, CM = 8, FLG with FEXTRA / FNAME / FCOMMENT / FHCRC and its reserved bits clear.  *valid = 1: the deflate
  * bytes begin at *deflate_off; 0: not such a header, or it does not end within the n bytes. */
 int rala_hip_gzip_head(const uint8_t* bytes, uint64_t n, uint64_t* deflate_off, int* valid);
+/* The chain of true chunks of a single-member gzip stream (no context, no device), as the device ingest builds it from what
+ * the device found and counted in each of n_chunks chunks - starts[c]: the bit chunk c's first candidate block begins at
+ * (~0: none); status[c]: 0 decoding from there ended at the start of chunk next[c], 1 the final block ended at bit end_bit[c],
+ * 2 invalid, 3 no start; text[c]: the bytes it gives; refuted[c]: later starts it passed - followed from chunk 0.  end: the
+ * trailer's first byte; isize: the trailer's ISIZE.  *valid = 0, refused: a chunk on the chain with status > 1, a next that
+ * does not lead forward to a chunk there is, a final block that does not end in the byte in front of `end`, a text whose size
+ * is not isize modulo 2^32.  *n_jobs: the chain's chunks; when cap >= *n_jobs, each one's first bit, the bit it stops at (~0:
+ * the final block's end), its text offset and text size are written to the arrays given (any may be null).  stats (may be
+ * null): chunks, chunks_with_candidate, chunks_confirmed, chunks_refuted, max_wave_text_bytes and text_bytes of the walk. */
+int rala_hip_gzip_chain(const uint64_t* starts, const uint64_t* end_bit, const uint64_t* text, const uint32_t* next,
+                        const uint32_t* status, const uint32_t* refuted, uint64_t n_chunks, uint64_t end, uint32_t isize, uint64_t cap,
+                        uint64_t* n_jobs, uint64_t* start_bit, uint64_t* stop_bit, uint64_t* text_off, uint64_t* text_n,
+                        rala_hip_gzip_timings* stats, int* valid);
 /* The member index of a BGZF file held in memory (no context, no device): the chain of gzip members from byte 0, as the
  * device ingest builds it - the bytes scanned for member headers in blocks of block_bytes (0: the ingest's 32 MB), then
  * walked from offset 0.  *valid = 0: not a BGZF file the host reader would take (first 18 bytes not a BGZF header, a cut

@@ -243,11 +243,11 @@ struct rala_hip_ctx {
     int64_t ingest_window_bytes = 0;    // option: the tokeniser's window over the file's text (0: a quarter of the free device memory)
     rala_hip::DevBuf<unsigned long long> d_paf_bad;
     rala_hip_ingest_timings ingest_tm = {};
-    // BGZF overlap files (ingest.hip, inflate_kernels.hip): the compressed bytes, the members' jobs, the inflater's flag
+    // BGZF files (ingest_bgzf.hip, inflate_kernels.hip): the compressed bytes, the members' jobs, the inflater's flag
     rala_hip::DevBuf<uint8_t> d_bgzf_comp, d_bgzf_jobs;
     rala_hip::DevBuf<uint32_t> d_bgzf_flag;
     rala_hip_inflate_timings inflate_tm = {};
-    // single-member gzip files (option gzip_on_device; ingest.hip: gzip_inflate): the chunks' starts and spans, the true
+    // single-member gzip files (option gzip_on_device; ingest_gzip.hip): the chunks' starts and spans, the true
     // chunks' jobs and text offsets, the 16-bit symbols, the segments' CRCs, the resident text
     bool gzip_on_device = false;
     int64_t gzip_chunk_bytes = 64 << 10;        // option: compressed bytes per chunk
@@ -257,7 +257,7 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint16_t> d_gzip_sym;
     rala_hip::DevBuf<uint32_t> d_gzip_crc;
     rala_hip_gzip_timings gzip_tm = {};
-    // the sequence index (ingest.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
+    // the sequence index (ingest_sequences.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
     int64_t debug_sequence_window = 0;          // tests: the window over the read file's text (0: as the overlap ingest's, 2 GiB at most)
     rala_hip::DevBuf<uint64_t> d_seq_event[2], d_seq_name_pos, d_seq_data_off, d_seq_data_stripped, d_seq_name_off, d_seq_span;
     rala_hip::DevBuf<uint32_t> d_seq_name_len, d_seq_length, d_seq_tile[2], d_seq_name_at, d_seq_flags;
@@ -265,7 +265,7 @@ struct rala_hip_ctx {
     uint64_t n_seq_records = 0, n_seq_name_bytes = 0;
     bool seq_index_valid = false;
     rala_hip_ingest_timings seq_tm = {};
-    // what the second pass (ingest.hip: rala_hip_slice_sequences) needs of the index: what it was made from (0 a plain file,
+    // what the second pass (ingest_sequences.hip: rala_hip_slice_sequences) needs of the index: what it was made from (0 a plain file,
     // 1 BGZF, 2 a single gzip member - then the chain of its true chunks, text offsets from the text's start, and its CRC32),
     // the file's and the text's size, the stripped bytes of the whole text
     int seq_source = 0;

@@ -1,0 +1,132 @@
+// BGZF files on the device: the member index made while the file is read, the members that cover a range of the text
+// shipped and inflated (inflate_kernels.hip: launch_bgzf_inflate).
+#include <atomic>
+
+#include "ingest_common.h"
+
+using namespace rala_hip;
+using namespace rala_hip::ingest;
+
+int rala_hip::ingest::bgzf_open(rala_hip_ctx* ctx, int fd, uint64_t file_n, const char* path, uint32_t threads, uint64_t window, BgzfFile& f,
+                                bool* valid) {
+    *valid = false;
+    f.fd = fd;
+    f.file_n = file_n;
+    if (file_n < 18) return RALA_HIP_OK;
+    const double t0 = now_ms();
+    f.resident = file_n <= window;
+    if (f.resident && ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    const uint64_t n_blocks = (file_n + kBlockBytes - 1) / kBlockBytes;
+    std::vector<std::vector<BgzfCand>> cand(n_blocks);
+    std::atomic<int> edge_failed(0);
+    const BlockScan scan = [&](uint64_t b, const uint8_t* bytes, size_t n) {
+        // the block, the 8 bytes in front of it and what a header that starts in it may reach behind it
+        const uint64_t off = b * kBlockBytes;
+        uint8_t pre[8];
+        const uint64_t n_pre = std::min<uint64_t>(8, off);
+        std::vector<uint8_t> ext((size_t)std::min<uint64_t>(kHeaderReach, file_n - off - n));
+        if ((n_pre && pread(fd, pre, n_pre, (off_t)(off - n_pre)) != (ssize_t)n_pre) ||
+            (!ext.empty() && pread(fd, ext.data(), ext.size(), (off_t)(off + n)) != (ssize_t)ext.size())) {
+            edge_failed = 1;
+            return;
+        }
+        auto at = [&](uint64_t q) -> uint8_t {
+            if (q < off) return pre[n_pre - (off - q)];
+            if (q < off + n) return bytes[q - off];
+            return ext[q - off - n];
+        };
+        bgzf_scan(bytes, n, off, file_n, at, cand[b]);
+    };
+    const int shipped = ship_file(fd, 0, file_n, f.resident ? ctx->d_bgzf_comp.p : nullptr, ctx->device, threads, &scan,
+                                  []() { return true; }, &f.n_readers);
+    if (shipped || edge_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    uint8_t tail[4];
+    if (pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
+    std::vector<BgzfMember> members;
+    if (!bgzf_walk(cand, file_n, le32(tail), members)) return RALA_HIP_OK;
+    f.n_members = members.size();
+    for (const BgzfMember& m : members) {
+        if (m.isize) f.jobs.push_back(m);
+        f.text_n += m.isize;
+    }
+    f.shipped = f.resident ? file_n : 0;
+    f.ship_ms = (float)(now_ms() - t0);
+    *valid = true;
+    return RALA_HIP_OK;
+}
+
+int rala_hip::ingest::bgzf_text_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t n_avail, uint64_t cap, int pad, uint32_t threads,
+                                      const std::function<bool()>& meanwhile, const char* room, TextArrival* out) {
+    hipStream_t s = ctx->stream;
+    // the members that hold the text [lo - 1, lo + n_avail) (the byte in front of lo says whether lo starts a line)
+    const uint64_t need_lo = lo ? lo - 1 : 0, need_hi = lo + n_avail;
+    size_t j0 = 0, j1 = 0;
+    if (need_hi > need_lo) {
+        auto by_text = [](const BgzfMember& m, uint64_t t) { return m.text_off < t; };
+        j1 = std::lower_bound(f.jobs.begin(), f.jobs.end(), need_hi, by_text) - f.jobs.begin();
+        j0 = std::lower_bound(f.jobs.begin(), f.jobs.end(), need_lo + 1, by_text) - f.jobs.begin() - 1;
+    }
+    const uint64_t base = j1 > j0 ? f.jobs[j0].text_off : lo;
+    const uint64_t shift = lo - base;
+    const uint64_t extent = j1 > j0 ? f.jobs[j1 - 1].text_off + f.jobs[j1 - 1].isize - base : 0;
+    const uint64_t size = std::max(shift + cap, extent) + 64;
+    out->t0 = now_ms();
+    if (ctx->d_paf_text.ensure(size) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+    uint64_t comp_base = 0;
+    if (!f.resident && j1 > j0) {
+        comp_base = f.jobs[j0].off;
+        const uint64_t c_len = f.jobs[j1 - 1].off + f.jobs[j1 - 1].bsize - comp_base;
+        if (ctx->d_bgzf_comp.ensure(c_len + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        const int shipped = ship_file(f.fd, comp_base, c_len, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, meanwhile, &f.n_readers);
+        if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
+        if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying the compressed file failed");
+        f.shipped += c_len;
+    } else if (!meanwhile()) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
+    }
+    out->t_ship = now_ms();
+    std::vector<BgzfJob> jobs(j1 - j0);
+    for (size_t j = j0; j < j1; ++j) {
+        const BgzfMember& m = f.jobs[j];
+        BgzfJob& J = jobs[j - j0];
+        J.comp_off = m.off + m.hdr - comp_base;
+        J.text_off = m.text_off - base;
+        J.deflate_len = m.bsize - m.hdr - 8;
+        J.isize = m.isize;
+    }
+    uint32_t flag = 0;
+    if (!jobs.empty()) {
+        INGEST_CHECK(ctx->d_bgzf_jobs.ensure(jobs.size() * sizeof(BgzfJob)));
+        INGEST_CHECK(ctx->d_bgzf_flag.ensure(1));
+        INGEST_CHECK(hipMemcpyAsync(ctx->d_bgzf_jobs.p, jobs.data(), jobs.size() * sizeof(BgzfJob), hipMemcpyHostToDevice, s));
+        INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+        launch_bgzf_inflate(ctx->d_bgzf_comp.p, (const BgzfJob*)ctx->d_bgzf_jobs.p, (uint32_t)jobs.size(), ctx->d_paf_text.p, size, ctx->d_bgzf_flag.p, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    uint8_t* const text = ctx->d_paf_text.p + shift;
+    INGEST_CHECK(hipMemsetAsync(text + n_avail, pad, cap - n_avail, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    out->t1 = now_ms();
+    f.inflate_ms += (float)(out->t1 - out->t_ship);
+    if (flag) ctx->d_paf_text.release();
+    out->text = text;
+    out->flag = flag;
+    return RALA_HIP_OK;
+}
+
+extern "C" int rala_hip_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, uint64_t cap, uint64_t* n_members, uint64_t* file_off,
+                        uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* text_off, int* valid) {
+    if ((!bytes && n) || !n_members || !valid) return RALA_HIP_EINVAL;
+    std::vector<BgzfMember> m;
+    *valid = bgzf_index_bytes(bytes, n, block_bytes ? block_bytes : kBlockBytes, m) ? 1 : 0;
+    *n_members = *valid ? m.size() : 0;
+    if (!*valid || cap < m.size()) return RALA_HIP_OK;
+    for (size_t i = 0; i < m.size(); ++i) {
+        if (file_off) file_off[i] = m[i].off;
+        if (comp_bytes) comp_bytes[i] = m[i].bsize;
+        if (text_bytes) text_bytes[i] = m[i].isize;
+        if (text_off) text_off[i] = m[i].text_off;
+    }
+    return RALA_HIP_OK;
+}

@@ -1,0 +1,181 @@
+// What the device ingest decides on the host from bytes it does not trust - a file's first bytes, the member headers of a
+// BGZF file, the header of a gzip member, the chain through the chunks the device counted: pure functions, no device header.
+#pragma once
+
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "gzip_types.h"
+#include "rala_hip.h"
+
+namespace rala_hip {
+namespace ingest {
+
+inline uint32_t le32(const uint8_t* p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// ---- BGZF: the member index -------------------------------------------------------------------
+constexpr uint64_t kHeaderReach = 12 + 65535;      // the bytes a member header may occupy (XLEN < 2^16)
+
+struct BgzfCand {
+    uint64_t pos;
+    uint32_t bsize;         // the member's bytes (BSIZE + 1); 0: no member header the host reader would take
+    uint32_t hdr;           // 12 + XLEN
+    uint32_t prev_isize;    // the 4 bytes in front of pos (the ISIZE of a member that ends here)
+};
+struct BgzfMember {
+    uint64_t off, text_off;
+    uint32_t bsize, hdr, isize;
+};
+
+// is_bgzf of the host reader (io.cpp, BgzfSource): the first 18 bytes
+inline bool bgzf_head(const uint8_t* h, uint64_t n) {
+    return n >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) != 0 && h[10] == 6 && h[11] == 0 && h[12] == 'B' &&
+           h[13] == 'C' && h[14] == 2 && h[15] == 0;
+}
+
+// What a file is by its first 18 bytes (n: those of them it has): BGZF, any other gzip file (the magic alone), or text.
+enum TextKind { kTextPlain = 0, kTextBgzf = 1, kTextGzip = 2 };
+inline TextKind sniff(const uint8_t* h, uint64_t n) {
+    if (n < 2 || h[0] != 0x1f || h[1] != 0x8b) return kTextPlain;
+    return bgzf_head(h, n) ? kTextBgzf : kTextGzip;
+}
+
+// The member-header candidates among the bytes [off, off + n) of a file of file_n bytes: at(q) gives byte q for q in
+// [off - min(off, 8), min(file_n, off + n + kHeaderReach)).  A candidate is every 0x1f 0x8b 0x08 with FEXTRA; its BSIZE
+// is read as read_block reads it (BgzfSource: any XLEN, the last "BC" subfield of length 2, bsize >= 12 + XLEN + 8).
+template <class At>
+void bgzf_scan(const uint8_t* bytes, uint64_t n, uint64_t off, uint64_t file_n, const At& at, std::vector<BgzfCand>& out) {
+    const uint8_t* const end = bytes + n;
+    for (const uint8_t* h = (const uint8_t*)memchr(bytes, 0x1f, n); h; h = (const uint8_t*)memchr(h + 1, 0x1f, (size_t)(end - h - 1))) {
+        const uint64_t q = off + (uint64_t)(h - bytes);
+        if (q + 12 > file_n) break;
+        if (at(q + 1) != 0x8b || at(q + 2) != 8 || !(at(q + 3) & 4)) {
+            if (h + 1 >= end) break;
+            continue;
+        }
+        BgzfCand c;
+        c.pos = q;
+        c.bsize = 0;
+        c.prev_isize = 0;
+        if (q >= 4) for (int k = 3; k >= 0; --k) c.prev_isize = (c.prev_isize << 8) | at(q - 4 + (uint64_t)k);
+        const uint32_t xlen = at(q + 10) | (uint32_t)at(q + 11) << 8;
+        c.hdr = 12 + xlen;
+        if (q + 12 + xlen <= file_n) {
+            uint32_t bsize = 0;
+            for (uint32_t k = 0; k + 4 <= xlen;) {
+                const uint64_t e = q + 12 + k;
+                const uint32_t slen = at(e + 2) | (uint32_t)at(e + 3) << 8;
+                if (at(e) == 'B' && at(e + 1) == 'C' && slen == 2 && k + 6 <= xlen) bsize = (at(e + 4) | (uint32_t)at(e + 5) << 8) + 1;
+                k += 4 + slen;
+            }
+            if (bsize >= 12 + xlen + 8) c.bsize = bsize;
+        }
+        out.push_back(c);
+        if (h + 1 >= end) break;
+    }
+}
+
+// The chain of members from offset 0 through the candidates (in file order); tail: the file's last 4 bytes (the last member's
+// ISIZE).  false: the chain breaks - a position with no member header, a member beyond the end, ISIZE > 65536.
+inline bool bgzf_walk(const std::vector<std::vector<BgzfCand>>& blocks, uint64_t file_n, uint32_t tail, std::vector<BgzfMember>& members) {
+    members.clear();
+    uint64_t o = 0;
+    size_t b = 0, i = 0;
+    while (o < file_n) {
+        while (b < blocks.size() && (i >= blocks[b].size() || blocks[b][i].pos < o)) {
+            if (i >= blocks[b].size()) { ++b; i = 0; } else { ++i; }
+        }
+        if (b >= blocks.size()) return false;
+        const BgzfCand& c = blocks[b][i];
+        if (c.pos != o || c.bsize == 0 || o + c.bsize > file_n) return false;
+        if (!members.empty()) members.back().isize = c.prev_isize;
+        BgzfMember m;
+        m.off = o; m.bsize = c.bsize; m.hdr = c.hdr; m.isize = 0; m.text_off = 0;
+        members.push_back(m);
+        o += c.bsize;
+    }
+    if (!members.empty()) members.back().isize = tail;
+    uint64_t t = 0;
+    for (BgzfMember& m : members) {
+        if (m.isize > 65536) return false;
+        m.text_off = t;
+        t += m.isize;
+    }
+    return true;
+}
+
+// the index of a file in memory, scanned in blocks of block_bytes (what the readers do with their staging blocks)
+inline bool bgzf_index_bytes(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, std::vector<BgzfMember>& members) {
+    if (!bgzf_head(bytes, n)) return false;
+    const uint64_t n_blocks = (n + block_bytes - 1) / block_bytes;
+    std::vector<std::vector<BgzfCand>> cand(n_blocks);
+    auto at = [&](uint64_t q) { return bytes[q]; };
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        const uint64_t off = b * block_bytes;
+        bgzf_scan(bytes + off, std::min(block_bytes, n - off), off, n, at, cand[b]);
+    }
+    return bgzf_walk(cand, n, le32(bytes + n - 4), members);
+}
+
+// ---- a single-member gzip file (gzip, pigz, Python's gzip) ---------------------------------------------------------
+// The header of a gzip member (RFC 1952 2.3) in the first n bytes of a file: where its deflate bytes begin.  false: not a
+// header inflate would take (magic, CM != 8, reserved flag bits) or one that does not end within the n bytes.
+inline bool gzip_head(const uint8_t* h, uint64_t n, uint64_t* deflate_off) {
+    if (n < 10 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xE0) != 0) return false;
+    const uint32_t flg = h[3];
+    uint64_t o = 10;
+    if (flg & 4) {                                                  // FEXTRA
+        if (o + 2 > n) return false;
+        o += 2 + (h[o] | (uint64_t)h[o + 1] << 8);
+        if (o > n) return false;
+    }
+    for (uint32_t bit = 8; bit <= 16; bit <<= 1) {                  // FNAME, FCOMMENT: zero-terminated
+        if (!(flg & bit)) continue;
+        const void* z = o < n ? memchr(h + o, 0, (size_t)(n - o)) : nullptr;
+        if (!z) return false;
+        o = (uint64_t)((const uint8_t*)z - h) + 1;
+    }
+    if (flg & 2) o += 2;                                            // FHCRC (not checked, as zlib's gzread does not)
+    if (o > n) return false;
+    *deflate_off = o;
+    return true;
+}
+
+// The chain of true chunks from chunk 0 through what the device found and counted (starts[c], spans[c], c < n_chunks:
+// launch_gzip_find / launch_gzip_count), their text offsets from the text's start, and the counters of `tm` that speak of
+// the chain.  The host's only defence against what the device made of an untrusted file - false, the stream cannot be
+// proven: a chunk on the chain that is invalid or has no start, a `next` that does not lead forward to a chunk there is,
+// a final block that does not end in the byte in front of the trailer (`end`), a text whose size is not ISIZE modulo 2^32.
+inline bool gzip_chain_from_spans(const uint64_t* starts, const GzipSpan* spans, uint64_t n_chunks, uint64_t end, uint32_t isize,
+                                  std::vector<GzipJob>& chain, rala_hip_gzip_timings* tm) {
+    chain.clear();
+    if (!n_chunks) return false;
+    for (uint64_t c = 1; c < n_chunks; ++c) tm->chunks_with_candidate += starts[c] != kGzipNoStart;
+    uint64_t text_n = 0, end_bit = 0;
+    for (uint64_t c = 0;;) {
+        const GzipSpan& sp = spans[c];
+        if (sp.status > 1 || (sp.status == 0 && (sp.next <= c || sp.next >= n_chunks))) return false;
+        GzipJob j;
+        j.start_bit = starts[c];
+        j.stop_bit = sp.status == 0 ? starts[sp.next] : kGzipNoStart;
+        j.text_off = text_n;
+        j.text_n = sp.text;
+        j.first = chain.empty() ? 1u : 0u;
+        j.pad = 0;
+        chain.push_back(j);
+        text_n += sp.text;
+        tm->chunks_refuted += sp.refuted;
+        tm->max_wave_text_bytes = std::max<uint64_t>(tm->max_wave_text_bytes, sp.text);
+        if (sp.status == 1) { end_bit = sp.end_bit; break; }
+        c = sp.next;
+    }
+    tm->chunks_confirmed = chain.size() - 1;
+    tm->text_bytes = text_n;
+    return end_bit / 8 + (end_bit % 8 != 0) == end && (uint32_t)text_n == isize;
+}
+
+}  // namespace ingest
+}  // namespace rala_hip

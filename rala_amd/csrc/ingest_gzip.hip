@@ -1,0 +1,258 @@
+// A single-member gzip file (gzip, pigz, Python's gzip) inflated on the device by speculative decoding (inflate_kernels.hip).
+// One front half - the file shipped, block starts found in every chunk, every chunk counted from its start, the chain from
+// chunk 0 built and proven on the host - and two back ends: the whole text at once (overlap files) or window by window
+// (read files).
+#include "ingest_common.h"
+
+using namespace rala_hip;
+using namespace rala_hip::ingest;
+
+namespace {
+
+constexpr uint64_t kGzipHeadReach = 1u << 20;       // a header (name, comment, extra field) longer than this is the host reader's
+
+// The file (g.file_n bytes) to ctx->d_bgzf_comp, where it stays, and its chain: found / counted on the device and built by
+// gzip_chain_from_spans, or (given != null) the chain of an earlier call taken over.  *valid = false: not a stream this can
+// prove - a header the parse refuses, what the chain builder refuses, a chain taken over that is not this file's (ISIZE).
+int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, const std::vector<GzipJob>* given, GzipStream& g, bool* valid) {
+    *valid = false;
+    const uint64_t file_n = g.file_n;
+    std::vector<uint8_t> head((size_t)std::min(file_n, kGzipHeadReach));
+    uint8_t trailer[8];
+    if (file_n < 18 || pread(fd, head.data(), head.size(), 0) != (ssize_t)head.size() || pread(fd, trailer, 8, (off_t)(file_n - 8)) != 8) return RALA_HIP_OK;
+    uint64_t deflate_off = 0;
+    if (!gzip_head(head.data(), head.size(), &deflate_off) || deflate_off + 8 >= file_n) return RALA_HIP_OK;
+    const uint64_t end = g.end = file_n - 8;
+    g.crc = le32(trailer);
+    const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, ctx->gzip_chunk_bytes);
+    const uint64_t n_chunks = (end - deflate_off + chunk - 1) / chunk;
+    if (!given && n_chunks >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    hipStream_t s = ctx->stream;
+    const double t0 = now_ms();
+    if (ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess || ctx->d_bgzf_flag.ensure(1) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    }
+    const uint8_t* comp = ctx->d_bgzf_comp.p;
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+    if (ship_file(fd, 0, file_n, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, []() { return true; }, &g.n_readers)) {
+        return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    }
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    g.ship_ms = (float)(t1 - t0);
+    rala_hip_gzip_timings& tm = g.tm;
+    tm.compressed_bytes = file_n;
+    if (given) {
+        g.chain = *given;
+        if (g.chain.empty()) return RALA_HIP_OK;
+        for (const GzipJob& j : g.chain) {
+            g.text_n += j.text_n;
+            tm.max_wave_text_bytes = std::max<uint64_t>(tm.max_wave_text_bytes, j.text_n);
+        }
+        tm.chunks_confirmed = g.chain.size() - 1;
+        tm.text_bytes = g.text_n;
+        *valid = (uint32_t)g.text_n == le32(trailer + 4);
+        return RALA_HIP_OK;
+    }
+    if (ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess || ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    }
+    launch_gzip_find(comp, end, (file_n + 56) / 8, deflate_off, chunk, (uint32_t)n_chunks, ctx->debug_gzip_false_sync, ctx->d_gzip_starts.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t2 = now_ms();
+    launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s);
+    INGEST_CHECK(hipGetLastError());
+    std::vector<uint64_t> starts(n_chunks);
+    std::vector<GzipSpan> spans(n_chunks);
+    INGEST_CHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t3 = now_ms();
+    ctx->d_gzip_starts.release();
+    ctx->d_gzip_spans.release();
+    tm.chunks = n_chunks;
+    tm.find_ms = (float)(t2 - t1);
+    tm.decode_ms = (float)(t3 - t2);
+    *valid = gzip_chain_from_spans(starts.data(), spans.data(), n_chunks, end, le32(trailer + 4), g.chain, &tm);
+    g.text_n = tm.text_bytes;
+    return RALA_HIP_OK;
+}
+
+}  // namespace
+
+// Written and resolved in one piece behind the front half (no window, so no 2^31 cap on the text), CRC32 checked.
+int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, GzipStream& g, bool* valid) {
+    const int rc = gzip_chain_open(ctx, fd, path, threads, nullptr, g, valid);
+    if (rc != RALA_HIP_OK || !*valid) return rc;
+    *valid = false;
+    hipStream_t s = ctx->stream;
+    const uint64_t text_n = g.text_n, n_jobs = g.chain.size();
+    std::vector<uint64_t> text_off(n_jobs);
+    for (size_t j = 0; j < n_jobs; ++j) text_off[j] = g.chain[j].text_off;
+    const uint64_t n_seg = (text_n + gzip_segment_bytes() - 1) / gzip_segment_bytes();
+    if (n_seg >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
+    if (ctx->d_gzip_sym.ensure(text_n + 64) != hipSuccess || ctx->d_gzip_text.ensure(text_n + paf_chunk_bytes() + 8192) != hipSuccess ||
+        ctx->d_gzip_jobs.ensure(n_jobs * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(n_jobs) != hipSuccess ||
+        ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the inflated text");
+    }
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, g.chain.data(), n_jobs * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t3 = now_ms();
+    launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)n_jobs, ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t4 = now_ms();
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)n_jobs, text_n, ctx->d_gzip_text.p, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    // what lies behind the text reads as newlines (as for the plain file)
+    INGEST_CHECK(hipMemsetAsync(ctx->d_gzip_text.p + text_n, '\n', paf_chunk_bytes() + 8192, s));
+    std::vector<uint32_t> seg_crc(n_seg);
+    uint32_t flag = 0;
+    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t5 = now_ms();
+    ctx->d_gzip_sym.release();
+    ctx->d_bgzf_comp.release();
+    g.tm.decode_ms += (float)(t4 - t3);                     // the counting pass and the writing pass
+    g.tm.resolve_ms = (float)(t5 - t4);
+    *valid = !flag && gzip_crc_of_segments(seg_crc.data(), text_n) == g.crc;
+    return RALA_HIP_OK;
+}
+
+// ---- WINDOW by window (the driver of the same kernels for a text that does not fit): the compressed file stays resident -
+// the only buffer whose size depends on the file's; write, windows and resolve run per window, a run of consecutive true
+// chunks whose text fits it.  The symbols of a window lie behind a CARRY of gzip_ring_symbols(): the last 32 768 bytes in
+// front of it (0x8000 where the file's text has not begun), so the markers of its first chunks point into bytes, and every
+// text offset the kernels see counts from the carry's first symbol.
+// The front half (chain != null: the chain of an earlier walk taken over), then the buffers of a window made: `front` bytes
+// of room in front of the window's text in ctx->d_gzip_text and `behind` bytes behind it.  want_window 0: what a quarter of
+// the free memory holds at three bytes per text byte.  *valid = false: not a stream this can prove.
+int rala_hip::ingest::gzip_walk_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, uint64_t want_window, uint64_t front,
+                                     uint64_t behind, const std::vector<GzipJob>* chain, GzipWalk& g, bool* valid) {
+    const int rc = gzip_chain_open(ctx, fd, path, threads, chain, g, valid);
+    if (rc != RALA_HIP_OK || !*valid) return rc;
+    *valid = false;
+    hipStream_t s = ctx->stream;
+    // the window: symbols (2 bytes) and text (1 byte) of it inside the quarter of what is free now
+    uint64_t window = want_window;
+    if (window == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        window = std::max<uint64_t>(64ull << 20, free_b / 12);
+    }
+    window = std::max<uint64_t>(std::min<uint64_t>(window, 1ull << 31), g.tm.max_wave_text_bytes);
+    if (window > (1ull << 31)) return ingest_fail(ctx, RALA_HIP_ENOMEM, "a chunk of the gzip file gives more text than a window holds");
+    window = std::min(window, std::max<uint64_t>(g.text_n, 1));
+    g.window = window;
+    const uint64_t ring = gzip_ring_symbols();
+    if (ctx->d_gzip_sym.ensure(ring + window + 64) != hipSuccess || ctx->d_gzip_text.ensure(front + window + behind) != hipSuccess ||
+        ctx->d_gzip_crc.ensure(window / gzip_segment_bytes() + 2) != hipSuccess || ctx->d_gzip_carry.ensure(ring) != hipSuccess ||
+        ctx->d_gzip_hold.ensure(front + 16) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
+    }
+    // nothing lies in front of the first window: a marker that points there is no byte
+    INGEST_CHECK(hipMemsetD16Async((hipDeviceptr_t)ctx->d_gzip_sym.p, (unsigned short)0x8000u, ring, s));
+    *valid = true;
+    return RALA_HIP_OK;
+}
+
+// The next window's text [*lo, *lo + *n) to `text` (16-byte aligned, in ctx->d_gzip_text).  *flag != 0: the inflater refused.
+int rala_hip::ingest::gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* text, uint64_t* lo, uint64_t* n, uint32_t* flag) {
+    hipStream_t s = ctx->stream;
+    const uint64_t ring = gzip_ring_symbols();
+    const size_t j0 = g.next_job;
+    size_t j1 = j0;
+    uint64_t n_w = 0;
+    while (j1 < g.chain.size() && (j1 == j0 || n_w + g.chain[j1].text_n <= g.window)) n_w += g.chain[j1++].text_n;
+    const uint64_t a = g.chain[j0].text_off;
+    std::vector<GzipJob> jobs(g.chain.begin() + j0, g.chain.begin() + j1);
+    std::vector<uint64_t> text_off(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - a);
+    if (n_w > g.window) return ingest_fail(ctx, RALA_HIP_EDEVICE, "a chunk larger than the window");
+    *lo = a;
+    *n = n_w;
+    *flag = 0;
+    g.next_job = j1;
+    if (ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's chunks");
+    }
+    const double t0 = now_ms();
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    const uint64_t n_seg = (n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)jobs.size(), n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s, ring);
+    INGEST_CHECK(hipGetLastError());
+    std::vector<uint32_t> seg_crc(n_seg);
+    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipMemcpyAsync(flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    if (j1 < g.chain.size()) launch_gzip_carry(ctx->d_gzip_sym.p, text, n_w, ctx->d_gzip_carry.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    g.tm.decode_ms += (float)(t1 - t0);
+    g.tm.resolve_ms += (float)(now_ms() - t1);
+    g.reg.push_back(gzip_crc_register(seg_crc.data(), n_w));
+    g.len.push_back(n_w);
+    return RALA_HIP_OK;
+}
+
+// behind the last window: is the text the trailer's?
+bool rala_hip::ingest::gzip_walk_proven(const GzipWalk& g) {
+    return g.next_job == g.chain.size() && gzip_crc_chain(g.reg.data(), g.len.data(), g.reg.size()) == g.crc;
+}
+
+void rala_hip::ingest::trace_gzip(const GzipStream& g, uint64_t windows, uint64_t window) {
+    const rala_hip_gzip_timings& t = g.tm;
+    char in[96] = "";
+    if (windows) snprintf(in, sizeof(in), " in %lu windows of at most %.3f GB of text", (unsigned long)windows, window / 1e9);
+    fprintf(stderr, "[trace] device inflate: one gzip member%s, %.3f GB compressed shipped in %.1f ms, %lu chunks (%lu with a candidate, %lu "
+            "confirmed, %lu refuted), %.3f GB of text (at most %.3f GB by one wave): find %.2f ms, decode %.2f ms, resolve %.2f ms\n", in,
+            t.compressed_bytes / 1e9, g.ship_ms, (unsigned long)t.chunks, (unsigned long)t.chunks_with_candidate, (unsigned long)t.chunks_confirmed,
+            (unsigned long)t.chunks_refuted, t.text_bytes / 1e9, t.max_wave_text_bytes / 1e9, t.find_ms, t.decode_ms, t.resolve_ms);
+}
+
+extern "C" {
+
+uint32_t rala_hip_crc32_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
+    if (n && (!reg || !len)) return 0;
+    return gzip_crc_chain(reg, len, n);
+}
+
+int rala_hip_gzip_head(const uint8_t* bytes, uint64_t n, uint64_t* deflate_off, int* valid) {
+    if ((!bytes && n) || !deflate_off || !valid) return RALA_HIP_EINVAL;
+    *deflate_off = 0;
+    *valid = gzip_head(bytes, n, deflate_off) ? 1 : 0;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_chain(const uint64_t* starts, const uint64_t* end_bit, const uint64_t* text, const uint32_t* next, const uint32_t* status,
+                        const uint32_t* refuted, uint64_t n_chunks, uint64_t end, uint32_t isize, uint64_t cap, uint64_t* n_jobs,
+                        uint64_t* start_bit, uint64_t* stop_bit, uint64_t* text_off, uint64_t* text_n, rala_hip_gzip_timings* stats, int* valid) {
+    if (!n_jobs || !valid || (n_chunks && (!starts || !end_bit || !text || !next || !status || !refuted))) return RALA_HIP_EINVAL;
+    std::vector<GzipSpan> spans(n_chunks);
+    for (uint64_t c = 0; c < n_chunks; ++c) spans[c] = GzipSpan{end_bit[c], text[c], next[c], status[c], refuted[c], 0};
+    std::vector<GzipJob> chain;
+    rala_hip_gzip_timings tm = {};
+    tm.chunks = n_chunks;
+    *valid = gzip_chain_from_spans(starts, spans.data(), n_chunks, end, isize, chain, &tm) ? 1 : 0;
+    if (stats) *stats = tm;
+    *n_jobs = *valid ? chain.size() : 0;
+    if (!*valid || cap < chain.size()) return RALA_HIP_OK;
+    for (size_t j = 0; j < chain.size(); ++j) {
+        if (start_bit) start_bit[j] = chain[j].start_bit;
+        if (stop_bit) stop_bit[j] = chain[j].stop_bit;
+        if (text_off) text_off[j] = chain[j].text_off;
+        if (text_n) text_n[j] = chain[j].text_n;
+    }
+    return RALA_HIP_OK;
+}
+
+}  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gzip_types.h"
+
 namespace rala_hip {
 
 // zero padding in front of a pile inside the LDS image (multiple of 8 so the
@@ -594,19 +596,8 @@ void launch_bgzf_inflate(const uint8_t* comp, const BgzfJob* jobs, uint32_t n_jo
 // ---- a single-member gzip stream -> text by speculative decoding (inflate_kernels.hip) -------------
 // Offsets are bytes / bits from the start of `comp`, which holds the whole file (aligned, 64 readable bytes behind it, n_words
 // = its 8-byte words); end = the trailer's first byte.
-constexpr uint64_t kGzipNoStart = ~0ull;
-// what the counting pass found from one chunk's start: status 0 = it ended at the start of chunk `next`, 1 = its final block
-// ended at bit end_bit, 2 = invalid, 3 = the chunk has no start; text = the bytes it gives; refuted = later starts it passed
-struct GzipSpan {
-    uint64_t end_bit, text;
-    uint32_t next, status, refuted, pad;
-};
-// one true chunk for the writing pass: decoded from start_bit to the block boundary stop_bit (kGzipNoStart: to the final block's
-// end), its text_n symbols to sym + text_off; first != 0: the stream's first chunk (nothing lies in front of its text)
-struct GzipJob {
-    uint64_t start_bit, stop_bit, text_off, text_n;
-    uint32_t first, pad;
-};
+// (kGzipNoStart, GzipSpan - what the counting pass found from one chunk's start - and GzipJob - one true chunk for the
+// writing pass: gzip_types.h)
 // starts[c], c < n_chunks: where chunk c's first candidate block begins (chunk 0: 8 * deflate_off), kGzipNoStart = none;
 // false_sync n != 0 (tests): every n-th chunk is given its first bit as its start
 void launch_gzip_find(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t n_chunks,

@@ -31,7 +31,7 @@ SYMBOLS = (
     "rala_hip_copy_device_state", "rala_hip_layout", "rala_hip_find_repetitive_hills",
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
-    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
     "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",
@@ -184,6 +184,7 @@ def lib(build=True):
         L.rala_hip_get_sequence_slice_info.argtypes = [vp, ctypes.POINTER(SequenceSliceInfo)]
         L.rala_hip_crc32_chain.argtypes = [vp, vp, u64]
         L.rala_hip_crc32_chain.restype = u32
+        L.rala_hip_gzip_chain.argtypes = [vp] * 6 + [u64, u64, u32, u64, ctypes.POINTER(u64)] + [vp] * 4 + [ctypes.POINTER(GzipTimings), ctypes.POINTER(i32)]
         _lib = L
     return _lib
 
@@ -742,3 +743,19 @@ def crc32_chain(reg, length):
     length = np.ascontiguousarray(length, dtype=np.uint64)
     assert len(reg) == len(length)
     return int(lib().rala_hip_crc32_chain(reg.ctypes.data, length.ctypes.data, len(reg)))
+
+
+def gzip_chain(starts, end_bit, text, nxt, status, refuted, end, isize):
+    """rala_hip_gzip_chain (no device): the chain of true chunks from chunk 0 through what the device found and counted per
+    chunk -> (None when refused, else the jobs' start_bit, stop_bit, text_off, text_n), the walk's counters"""
+    u64a, u32a = (lambda a: np.ascontiguousarray(a, dtype=np.uint64)), (lambda a: np.ascontiguousarray(a, dtype=np.uint32))
+    starts, end_bit, text, nxt, status, refuted = u64a(starts), u64a(end_bit), u64a(text), u32a(nxt), u32a(status), u32a(refuted)
+    n = len(starts)
+    assert all(len(a) == n for a in (end_bit, text, nxt, status, refuted))
+    out = [np.zeros(n, dtype=np.uint64) for _ in range(4)]
+    n_jobs, valid, tm = ctypes.c_uint64(0), ctypes.c_int32(0), GzipTimings()
+    rc = lib().rala_hip_gzip_chain(starts.ctypes.data, end_bit.ctypes.data, text.ctypes.data, nxt.ctypes.data, status.ctypes.data,
+                                   refuted.ctypes.data, n, end, isize, n, ctypes.byref(n_jobs), *[a.ctypes.data for a in out],
+                                   ctypes.byref(tm), ctypes.byref(valid))
+    assert rc == 0
+    return (tuple(a[:n_jobs.value] for a in out) if valid.value else None), tm.as_dict()

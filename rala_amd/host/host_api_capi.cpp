@@ -134,10 +134,12 @@ struct PafOnDevice {
     std::vector<uint8_t> strand;
     rala_hip_ingest_timings tm = {};
     rala_hip_gzip_timings gz = {};
+    int before_irregular = 0;       // what the file ingested first on the same context gave (hp_text_device_after)
+    int64_t before_bad = -1;
 };
 
 static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap,
-                            const char* const* keys = nullptr, const int64_t* values = nullptr, uint32_t n_options = 0);
+                            const char* const* keys = nullptr, const int64_t* values = nullptr, uint32_t n_options = 0, const char* before = nullptr);
 void* hp_paf_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads) {
     return text_on_device(path, names, read_len, n_reads, check_lengths, threads, false);
 }
@@ -151,8 +153,18 @@ void* hp_text_device_with(const char* path, const char* names, const uint32_t* r
                           int mhap, const char* const* keys, const int64_t* values, uint32_t n_options) {
     return text_on_device(path, mhap ? "" : names, read_len, n_reads, check_lengths, threads, mhap != 0, keys, values, n_options);
 }
+// hp_text_device_with behind the file `before`, ingested on the same context first, whatever comes of it (before[0], [1] =
+// its irregular flags and first length-check offender): does a call that gave up leave the context usable?
+void* hp_text_device_after(const char* before, const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths,
+                           uint32_t threads, int mhap, const char* const* keys, const int64_t* values, uint32_t n_options) {
+    return text_on_device(path, mhap ? "" : names, read_len, n_reads, check_lengths, threads, mhap != 0, keys, values, n_options, before);
+}
+void hp_paf_device_before(void* h, int64_t* before) {
+    before[0] = ((const PafOnDevice*)h)->before_irregular;
+    before[1] = ((const PafOnDevice*)h)->before_bad;
+}
 static void* text_on_device(const char* path, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths, uint32_t threads, bool mhap,
-                            const char* const* keys, const int64_t* values, uint32_t n_options) {
+                            const char* const* keys, const int64_t* values, uint32_t n_options, const char* before) {
     std::vector<std::string> nm;
     const char* p = names;
     for (uint64_t i = 0; i < n_reads && !mhap; ++i) {
@@ -169,6 +181,10 @@ static void* text_on_device(const char* path, const char* names, const uint32_t*
     for (uint32_t k = 0; k < n_options && out->rc == RALA_HIP_OK; ++k) out->rc = rala_hip_set_option(ctx, keys[k], values[k]);
     if (out->rc == RALA_HIP_OK) out->rc = rala_hip_set_reads(ctx, read_len, n_reads);
     if (out->rc == RALA_HIP_OK && !mhap) out->rc = rala_hip_set_name_table(ctx, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
+    if (out->rc == RALA_HIP_OK && before) {
+        out->rc = mhap ? rala_hip_set_overlaps_from_mhap(ctx, before, check_lengths, threads, &out->before_bad, &out->before_irregular)
+                       : rala_hip_set_overlaps_from_paf(ctx, before, check_lengths, threads, &out->before_bad, &out->before_irregular);
+    }
     if (out->rc == RALA_HIP_OK) {
         out->rc = mhap ? rala_hip_set_overlaps_from_mhap(ctx, path, check_lengths, threads, &out->bad, &out->irregular)
                        : rala_hip_set_overlaps_from_paf(ctx, path, check_lengths, threads, &out->bad, &out->irregular);

@@ -1,4 +1,4 @@
-"""CPU: the member index of a BGZF file (rala_hip_bgzf_index, rala_amd/csrc/ingest.hip) - the scan for member headers block by
+"""CPU: the member index of a BGZF file (rala_hip_bgzf_index, rala_amd/csrc/ingest_formats.h) - the scan for member headers block by
 block and the walk of the chain from offset 0 that the device ingest builds before it ships and inflates - against a walk in
 Python, and what it refuses: exactly what the host reader's BgzfSource (rala_amd/host/io.cpp) refuses."""
 import ctypes

@@ -306,6 +306,55 @@ def test_length_check_first_offender_and_tiny_windows(tmp_path):
                 same(got[0], w[0])
 
 
+def test_a_call_that_gives_up_in_a_window_leaves_the_context_usable(tmp_path):
+    """a gzip PAF with check_lengths on, a tiny window and the first offender in the second of three windows is refused; the
+    context stays usable: a plain file ingested on it afterwards gives the host reader's columns"""
+    ds = Dataset(500, 20_000, 6)
+    names = ["r%d" % i for i in range(ds.n_reads)]
+    paf = str(tmp_path / "ovl.paf")
+    ds.write_paf(paf)
+    lines = open(paf, "rb").read().splitlines(keepends=True)[:600]
+    assert len(lines) >= 300
+    good_paf, bad_paf = str(tmp_path / "good.paf"), str(tmp_path / "bad.paf")
+    open(good_paf, "wb").write(b"".join(lines))
+    window = sum(map(len, lines)) // 3 + 1
+    k = next(i for i in range(len(lines)) if sum(map(len, lines[:i])) >= window + 100)
+    assert sum(map(len, lines[:k + 1])) < 2 * window
+    f = lines[k].split(b"\t")
+    f[1] = b"%d" % (int(f[1]) + 1)                # (the query's length is no longer its read's)
+    open(bad_paf, "wb").write(b"".join(lines[:k] + [b"\t".join(f)] + lines[k + 1:]))
+    write_gz(bad_paf, bad_paf + ".gz", level=6)
+    want_bad = gi.device_parse(bad_paf, names, ds.read_len)
+    assert want_bad[0] is None and want_bad[2] >= 0
+    want, e0 = host.parse(good_paf, names, ds.read_len, 2, True)
+    assert e0 == -1
+    L = _lib()
+    L.hp_text_device_after.restype = ctypes.c_void_p
+    L.hp_text_device_after.argtypes = [ctypes.c_char_p] + list(L.hp_text_device_with.argtypes)
+    L.hp_paf_device_before.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    options = dict(gzip_on_device=1, gzip_chunk_bytes=4096, ingest_window_bytes=window)
+    keys = (ctypes.c_char_p * len(options))(*[o.encode() for o in options])
+    values = np.array(list(options.values()), dtype=np.int64)
+    rl = np.ascontiguousarray(ds.read_len, dtype=np.uint32)
+    h = L.hp_text_device_after((bad_paf + ".gz").encode(), good_paf.encode(), "\n".join(names).encode(), rl.ctypes.data, len(rl), 1, 3, 0,
+                               ctypes.cast(keys, ctypes.c_void_p), values.ctypes.data, len(options))
+    try:
+        info, before, g = np.zeros(6, dtype=np.int64), np.zeros(2, dtype=np.int64), np.zeros(10, dtype=np.int64)
+        L.hp_paf_device_info(h, info.ctypes.data)
+        L.hp_paf_device_before(h, before.ctypes.data)
+        L.hp_paf_device_gzip_info(h, g.ctypes.data)
+        assert info[0] == 0, info
+        assert (int(before[0]), int(before[1])) == want_bad[1:], before
+        assert info[1] == 0 and info[2] == -1 and info[3] == len(lines), info
+        assert g[5] == 0, g                     # (the second file met no inflater)
+        cols = {f: np.zeros(len(lines), dtype=np.uint32) for f in FIELDS}
+        cols["strand"] = np.zeros(len(lines), dtype=np.uint8)
+        L.hp_paf_device_copy(h, *[cols[f].ctypes.data for f in FIELDS], cols["strand"].ctypes.data)
+        same(cols, want)
+    finally:
+        L.hp_paf_device_free(h)
+
+
 def _mhap_graph(path, read_len, options=()):
     ctx = hip.Context(0)
     try:
