@@ -119,6 +119,8 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * "debug_dedupe_list_cap" (tests: the list of the runs duplicate removal's counting pass marks holds this many marks, 0 = the
  * default 2^20; a list that does not hold them all is given up and the pass over all overlaps does the work),
  * "gzip_on_device" (default 0; 1: rala_hip_set_overlaps_from_paf / _mhap inflate a single-member gzip file on the device, see there),
+ * "gzip_members" (default 0; with "gzip_on_device" 1: a gzip file of SEVERAL members that is not BGZF - cat a.gz b.gz, pigz -i,
+ * a .gz file that was appended to - is walked member by member on the device instead of refused, see rala_hip_gzip_chain_members),
  * "gzip_chunk_bytes" (default 65536: the compressed bytes one wave of that inflater starts in; at least 1024),
  * "debug_gzip_false_sync" (tests: every n-th of those chunks is given a bogus block start at its first bit; 0, the default: none),
  * "debug_sequence_window" (tests: rala_hip_index_sequences takes the read file's text through windows of this many bytes; 0, the
@@ -162,8 +164,8 @@ int rala_hip_set_overlaps(rala_hip_ctx* ctx, const rala_hip_overlaps* ovl, uint6
  * symbols (a byte, or "byte k of the window in front of this chunk"); the chain of chunks that ended at each other's starts
  * from chunk 0 is the stream, the rest is dropped; windows and symbols are resolved in text order, and the result is
  * proved: CRC32, ISIZE mod 2^32, the final block ending exactly at the 8 trailer bytes.  Anything else - a header RFC 1952
- * does not allow, an invalid block, a cut stream, a second member or other bytes behind the trailer - gives *irregular & 8
- * and sets nothing.  The compressed bytes, two bytes per byte of text and the text must fit in device memory together
+ * does not allow, an invalid block, a cut stream, a second member (unless the option "gzip_members" is set, see
+ * rala_hip_gzip_chain_members) or other bytes behind the trailer - gives *irregular & 8 and sets nothing.  The compressed bytes, two bytes per byte of text and the text must fit in device memory together
  * (RALA_HIP_ENOMEM otherwise; the caller takes the host reader).  rala_hip_get_gzip_timings: the passes. */
 typedef struct rala_hip_ingest_timings {
     float ship_ms;          /* file -> device memory (reads and copies overlapped) */
@@ -222,6 +224,42 @@ int rala_hip_gzip_chain(const uint64_t* starts, const uint64_t* end_bit, const u
                         const uint32_t* status, const uint32_t* refuted, uint64_t n_chunks, uint64_t end, uint32_t isize, uint64_t cap,
                         uint64_t* n_jobs, uint64_t* start_bit, uint64_t* stop_bit, uint64_t* text_off, uint64_t* text_n,
                         rala_hip_gzip_timings* stats, int* valid);
+/* ---- gzip files of several members (option "gzip_members" beside "gzip_on_device") -----------------------------------------
+ * The reference reads `cat a.fastq.gz b.fastq.gz` and `cat part*.paf.gz` transparently: bioparser's gzread walks from member to
+ * member (src/graph.cpp:190-224, 249-264, 328-352).  With both options set, rala_hip_set_overlaps_from_paf / _mhap,
+ * rala_hip_index_sequences and rala_hip_slice_sequences do the same on the device: a kernel finds every byte offset at which a
+ * member header begins (rala_hip_gzip_head's parse; a magic inside deflate bytes is found too and never reached), the counting
+ * pass also decodes from every such header's first block as from a stream's first chunk, and the host walks the chain: where a
+ * final block ends, the next 8 bytes are the member's trailer - its ISIZE must be the member's text size modulo 2^32 - and
+ * either the file ends behind them or a found header begins there.  Every member is proven separately: a back reference that
+ * reaches in front of its member's first byte is refused (zlib refuses it), and every member's CRC32 is compared with its own
+ * trailer.  Anything else - bytes between or behind members that are no header, a cut member, a wrong inner CRC32 or ISIZE -
+ * gives *irregular & 8 and sets nothing.  With "gzip_members" 0 a second member is refused as before.
+ *
+ * The chain of such a file (no context, no device), in the style of rala_hip_gzip_chain: besides the chunks' arrays, n_cands
+ * member candidates in ascending order - cand_header_off[k]: the header's first byte, cand_deflate_bit[k]: the bit its deflate
+ * bytes begin at, cand_prev_crc / cand_prev_isize[k]: the 8 bytes in front of the header, cand_end_bit / cand_text / cand_next /
+ * cand_status[k]: what decoding from cand_deflate_bit[k] as a first chunk gave.  file_n: the file's size; last_crc, last_isize:
+ * its last 8 bytes.  *valid = 0, refused: what rala_hip_gzip_chain refuses, a trailer behind which neither the file ends nor
+ * a candidate begins, a member whose text size is not its ISIZE, a member cut by the file's end, an end_bit or a next that
+ * does not lead forward.  Jobs as rala_hip_gzip_chain gives them, and first[j] = 1 on every member's first job; members
+ * (when member_cap >= *n_members): each one's text offset, text size and the CRC32 its trailer names, empty members included. */
+int rala_hip_gzip_chain_members(const uint64_t* starts, const uint64_t* end_bit, const uint64_t* text, const uint32_t* next,
+                                const uint32_t* status, const uint32_t* refuted, uint64_t n_chunks, const uint64_t* cand_header_off,
+                                const uint64_t* cand_deflate_bit, const uint32_t* cand_prev_crc, const uint32_t* cand_prev_isize,
+                                const uint64_t* cand_end_bit, const uint64_t* cand_text, const uint32_t* cand_next,
+                                const uint32_t* cand_status, uint64_t n_cands, uint64_t file_n, uint32_t last_crc, uint32_t last_isize,
+                                uint64_t cap, uint64_t* n_jobs, uint64_t* start_bit, uint64_t* stop_bit, uint64_t* text_off,
+                                uint64_t* text_n, uint32_t* first, uint64_t member_cap, uint64_t* n_members, uint64_t* member_text_off,
+                                uint64_t* member_text_n, uint32_t* member_crc32, rala_hip_gzip_timings* stats, int* valid);
+/* The member find alone (tests): the n bytes are shipped to the device and every offset at which rala_hip_gzip_head takes the
+ * bytes from there on (at most 2^20 of them) is returned in ascending order - *n_found of them; when cap >= *n_found, each
+ * header's offset and where its deflate bytes begin. */
+int rala_hip_gzip_find_members(rala_hip_ctx* ctx, const uint8_t* bytes, uint64_t n, uint64_t cap, uint64_t* n_found, uint64_t* header_off,
+                               uint64_t* deflate_off);
+/* The members of the gzip file the last rala_hip_set_overlaps_from_paf / _mhap or rala_hip_index_sequences inflated on the
+ * device (none: it inflated none, or refused): *n of them; when cap >= *n, each one's text offset, text size and CRC32. */
+int rala_hip_get_gzip_members(rala_hip_ctx* ctx, uint64_t* n, uint64_t cap, uint64_t* text_off, uint64_t* text_n, uint32_t* crc32);
 /* The member index of a BGZF file held in memory (no context, no device): the chain of gzip members from byte 0, as the
  * device ingest builds it - the bytes scanned for member headers in blocks of block_bytes (0: the ingest's 32 MB), then
  * walked from offset 0.  *valid = 0: not a BGZF file the host reader would take (first 18 bytes not a BGZF header, a cut
@@ -263,7 +301,8 @@ int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* ou
  * chunks whose text fits it (a quarter of the free memory over three bytes per text byte; option "debug_sequence_window";
  * never less than the largest chunk's text - RALA_HIP_ENOMEM where that does not fit), the last 32 768 bytes of a window are
  * carried in front of the next one's symbols, the windows' CRC registers are chained.  CRC32, ISIZE and the final block ending
- * at the trailer prove the text; anything else - several members included - is *irregular = 8.  The index equals that of the
+ * at the trailer prove the text; anything else - several members included, unless the option "gzip_members" is set: then every
+ * member is proven so, any number of member boundaries in a window - is *irregular = 8.  The index equals that of the
  * uncompressed file.  rala_hip_get_gzip_timings then speaks of this call.
  *
  * The second pass: the bases of the reads `wanted` (ascending record numbers of the current index, n_wanted of them) are cut

@@ -250,12 +250,18 @@ struct rala_hip_ctx {
     // single-member gzip files (option gzip_on_device; ingest_gzip.hip): the chunks' starts and spans, the true
     // chunks' jobs and text offsets, the 16-bit symbols, the segments' CRCs, the resident text
     bool gzip_on_device = false;
+    bool gzip_members = false;                  // option: a file of several members is walked member by member (with gzip_on_device)
     int64_t gzip_chunk_bytes = 64 << 10;        // option: compressed bytes per chunk
     uint32_t debug_gzip_false_sync = 0;         // tests: every n-th chunk is given a bogus start at its first bit
-    rala_hip::DevBuf<uint64_t> d_gzip_starts, d_gzip_off;
+    rala_hip::DevBuf<uint64_t> d_gzip_starts, d_gzip_off, d_gzip_floor;
     rala_hip::DevBuf<uint8_t> d_gzip_spans, d_gzip_jobs, d_gzip_text;
     rala_hip::DevBuf<uint16_t> d_gzip_sym;
     rala_hip::DevBuf<uint32_t> d_gzip_crc;
+    // ... and of a file of several members (option gzip_members): the member find's tile counts, its candidates and their spans,
+    // the pieces of the text cut at member ends and their CRC registers; the members of the last call (rala_hip_get_gzip_members)
+    rala_hip::DevBuf<uint32_t> d_gzip_tile, d_gzip_piece_crc;
+    rala_hip::DevBuf<uint8_t> d_gzip_cands, d_gzip_mspans, d_gzip_pieces;
+    std::vector<rala_hip::GzipMember> gzip_members_last;
     rala_hip_gzip_timings gzip_tm = {};
     // the sequence index (ingest_sequences.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
     int64_t debug_sequence_window = 0;          // tests: the window over the read file's text (0: as the overlap ingest's, 2 GiB at most)
@@ -272,6 +278,7 @@ struct rala_hip_ctx {
     bool seq_fastq = false;
     uint64_t seq_file_n = 0, seq_text_n = 0, seq_n_stripped = 0;
     std::vector<rala_hip::GzipJob> seq_gzip_chain;
+    std::vector<rala_hip::GzipMember> seq_gzip_members;     // (every member's text range, trailer offset and CRC32)
     uint32_t seq_gzip_crc = 0;
     rala_hip::DevBuf<uint16_t> d_gzip_carry;
     rala_hip::DevBuf<uint8_t> d_gzip_hold, d_slice_out;

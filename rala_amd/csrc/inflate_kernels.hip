@@ -24,7 +24,8 @@
 // The contract is tested (tests/test_gpu_inflate_crafted.py, both inflaters) against the case list of tests/deflate_craft.py -
 // handmade streams that zlib's compressor never writes, valid and invalid - with zlib's inflate and the host reader as the verdict.
 //
-// Below the BGZF kernel: a single-member gzip stream by speculative decoding over chunks of the compressed bytes (its own header comment).
+// Below the BGZF kernel: a single-member gzip stream by speculative decoding over chunks of the compressed bytes (its own header
+// comment), and behind it what a file of several such members adds: the member find, the members' spans, the pieces' CRC.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -422,6 +423,10 @@ __global__ __launch_bounds__(kWave) void bgzf_inflate_kernel(const uint8_t* __re
 //            chunk j points into the window in front of chunk j, which is bytes already);
 //   resolve  one streaming pass: every symbol to its byte in the text buffer, the CRC32 of every 16 KB of it on the way.
 // Whatever this cannot prove - CRC32, ISIZE, the final block ending exactly at the trailer - is flag 8 for the caller.
+// A file of several members (cat a.gz b.gz; option gzip_members) is the same stream entered anew behind every trailer: the
+// member headers are found by gzip_member_find_kernel, counted from by gzip_count_kernel beside the chunks, chained by the host
+// (ingest_formats.h: gzip_chain_members), and every member is proven alone - `first` on its first chunk, its floor beside
+// every later chunk's text offset (windows, resolve), its CRC32 from the segments' registers and gzip_piece_crc_kernel's.
 constexpr uint64_t kNoStart = ~0ull;
 constexpr uint32_t kRing = 32768;           // deflate's window: the symbols a match can reach
 constexpr uint32_t kProbe = 64;             // symbols a candidate block must decode to (fewer where its end-of-block comes first)
@@ -805,15 +810,31 @@ __device__ __forceinline__ GzipSpan inflate_span(Lds& T, uint16_t* ring, const u
     return o;
 }
 
+// Block c < n_chunks: the span from chunk c's start.  Block n_chunks + k: the span from member candidate k's first block, decoded
+// as a stream's first chunk (nothing lies in front of a member; the block may be stored, fixed or dynamic, final or not); it
+// lands on the chunk starts behind it as a chunk's span does.  No span ever lands on a member candidate: a member is entered
+// through the trailer in front of it alone (ingest_formats.h: gzip_chain_members).
 __global__ __launch_bounds__(kWave) void gzip_count_kernel(const uint8_t* __restrict__ comp, uint64_t end, const uint64_t* __restrict__ starts,
-                                                            uint32_t n_chunks, GzipSpan* __restrict__ spans) {
+                                                            uint32_t n_chunks, GzipSpan* __restrict__ spans, const GzipMemberCand* __restrict__ cands,
+                                                            uint64_t deflate_off, uint64_t chunk_bytes, GzipSpan* __restrict__ mspans) {
     __shared__ Lds T;
     const uint32_t c = blockIdx.x;
-    const uint64_t s = starts[c];
+    const bool member = c >= n_chunks;
+    uint64_t s = member ? cands[c - n_chunks].deflate_bit : starts[c];
+    uint32_t chunk = c;
     GzipSpan o = {};
     o.status = 3;                                                   // no start: nothing decoded
-    if (s != kNoStart) o = inflate_span<false>(T, nullptr, comp, end, s, c == 0, starts, n_chunks, c, kNoStart, 0, nullptr);
-    if (lane_id() == 0) spans[c] = o;
+    if (member) {
+        // the first chunk whose start can lie behind s: the one that holds s, where its start does
+        uint32_t k = (uint32_t)min((s / 8 - min(s / 8, deflate_off)) / chunk_bytes, (uint64_t)n_chunks - 1);
+        const uint64_t sk = starts[k];
+        if (sk == kNoStart || sk <= s) ++k;
+        chunk = k - 1;
+        o.status = 2;                                               // (deflate bytes that begin in the last trailer or behind it)
+        if (s >= 8ull * end) s = kNoStart;
+    }
+    if (s != kNoStart) o = inflate_span<false>(T, nullptr, comp, end, s, member || c == 0, starts, n_chunks, chunk, kNoStart, 0, nullptr);
+    if (lane_id() == 0) (member ? mspans[c - n_chunks] : spans[c]) = o;
 }
 
 __global__ __launch_bounds__(kWave) void gzip_write_kernel(const uint8_t* __restrict__ comp, uint64_t end, const GzipJob* __restrict__ jobs,
@@ -838,15 +859,18 @@ __device__ __forceinline__ uint32_t owner_of(const uint64_t* text_off, uint32_t 
 }
 
 // symbol at p (a marker) -> the byte it stands for, read from the window in front of its chunk (bytes by now); 0x8000 set:
-// it points in front of the text, or at something that is no byte
-__device__ __forceinline__ uint32_t through_window(const uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t p, uint32_t s) {
-    const uint64_t src = text_off[owner_of(text_off, n_true, p)] + (s & 0x7FFFu);
-    return src < kRing ? 0x8000u : sym[src - kRing];
+// it points in front of its member's text (mfloor[j]: where the member of chunk j begins), or at something that is no byte
+__device__ __forceinline__ uint32_t through_window(const uint16_t* sym, const uint64_t* text_off, const uint64_t* mfloor, uint32_t n_true, uint64_t p,
+                                                   uint32_t s) {
+    const uint32_t j = owner_of(text_off, n_true, p);
+    const uint64_t src = text_off[j] + (s & 0x7FFFu);
+    return src < kRing + mfloor[j] ? 0x8000u : sym[src - kRing];
 }
 
 // The windows, one workgroup, in text order: the symbols [text_off[i] - 32 768, text_off[i]) become bytes in place - 8 symbols per
 // thread and load, a vector's markers looked up side by side (their chunk: i - 1, or a few steps further back where chunks are small).
-__global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const uint64_t* __restrict__ text_off, uint32_t n_true, uint32_t* flags) {
+__global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const uint64_t* __restrict__ text_off, const uint64_t* __restrict__ mfloor,
+                                                            uint32_t n_true, uint32_t* flags) {
     bool wrong = false;
     for (uint32_t i = 1; i < n_true; ++i) {
         // (nothing in front of the first chunk is a symbol of this launch: a window's carry is bytes already)
@@ -863,7 +887,7 @@ __global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const
                     uint32_t j = i - 1;
                     while (text_off[j] > p) --j;
                     const uint64_t src = text_off[j] + (s & 0x7FFFu);
-                    const uint32_t v = src < kRing ? 0x8000u : sym[src - kRing];
+                    const uint32_t v = src < kRing + mfloor[j] ? 0x8000u : sym[src - kRing];
                     wrong = wrong || (v & 0x8000u);
                     w[e >> 1] = (w[e >> 1] & ~(0xFFFFu << (16 * (e & 1)))) | (v & 0xFFu) << (16 * (e & 1));
                     any = true;
@@ -877,11 +901,23 @@ __global__ __launch_bounds__(1024) void gzip_windows_kernel(uint16_t* sym, const
     if (wrong) atomicOr(flags, 8u);
 }
 
+// the share of this thread's wave in the CRC register (from zero, no final inversion) of the n <= kSeg bytes staged in `out`:
+// every thread takes a slice of kSegSlice bytes and shifts its register over the bytes behind it, the wave's are summed
+__device__ __forceinline__ uint32_t staged_crc_part(const uint8_t* out, uint32_t n, const uint32_t* crc_table) {
+    const uint32_t s0 = min(threadIdx.x * kSegSlice, n), s1 = min(s0 + kSegSlice, n);
+    uint32_t r = 0;
+    for (uint32_t i = s0; i < s1; ++i) r = crc_table[(r ^ out[i]) & 0xFFu] ^ (r >> 8);
+    uint32_t part = s1 > s0 && n > s1 ? multmodp(x2nmodp(n - s1, 3), r) : r;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) part ^= (uint32_t)__shfl_xor((int)part, off, kWave);
+    return part;
+}
+
 // kSeg bytes of text per workgroup: symbols in (8 per thread and load), markers through their chunk's window, the bytes
 // staged in LDS, their CRC register (from zero, no final inversion: the host chains the segments') and out in whole 16 bytes.
-__global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_t* __restrict__ sym, const uint64_t* __restrict__ text_off, uint32_t n_true,
-                                                                    uint64_t text_n, uint8_t* __restrict__ text, uint32_t* __restrict__ seg_crc, uint32_t* flags,
-                                                                    uint64_t front) {
+__global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_t* __restrict__ sym, const uint64_t* __restrict__ text_off,
+                                                                    const uint64_t* __restrict__ mfloor, uint32_t n_true, uint64_t text_n,
+                                                                    uint8_t* __restrict__ text, uint32_t* __restrict__ seg_crc, uint32_t* flags, uint64_t front) {
     __shared__ __align__(16) uint8_t out[kSeg];
     __shared__ uint32_t crc_table[256];
     __shared__ uint32_t wave_part[kSegThreads / kWave];
@@ -903,7 +939,7 @@ __global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_
         for (uint32_t e = 0; e < 8; ++e) {
             uint32_t s = (w[e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
             if (k + e < n && (s & 0x8000u)) {
-                s = through_window(sym, text_off, n_true, front + base + k + e, s);
+                s = through_window(sym, text_off, mfloor, n_true, front + base + k + e, s);
                 wrong = wrong || (s & 0x8000u);
             }
             b[e >> 2] |= (s & 0xFFu) << (8 * (e & 3));
@@ -912,12 +948,7 @@ __global__ __launch_bounds__(kSegThreads) void gzip_resolve_kernel(const uint16_
     }
     if (wrong) atomicOr(flags, 8u);
     __syncthreads();
-    const uint32_t s0 = min(tid * kSegSlice, n), s1 = min(s0 + kSegSlice, n);
-    uint32_t r = 0;
-    for (uint32_t i = s0; i < s1; ++i) r = crc_table[(r ^ out[i]) & 0xFFu] ^ (r >> 8);
-    uint32_t part = s1 > s0 && n > s1 ? multmodp(x2nmodp(n - s1, 3), r) : r;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part ^= (uint32_t)__shfl_xor((int)part, off, kWave);
+    const uint32_t part = staged_crc_part(out, n, crc_table);
     if ((tid & (kWave - 1)) == 0) wave_part[tid / kWave] = part;
     for (uint32_t k = 16 * tid; k < n; k += 16 * kSegThreads) {
         if (k + 16 <= n) {
@@ -941,6 +972,132 @@ __global__ __launch_bounds__(256) void gzip_carry_kernel(const uint16_t* __restr
     if (i >= kRing) return;
     const uint64_t p = n + i;
     out[i] = p < kRing ? sym[p] : (uint16_t)text[p - kRing];
+}
+
+// ---- the members of a gzip file (cat a.gz b.gz, pigz -i) -----------------------------------------------------------------------
+constexpr uint32_t kHeadTile = 4096;        // bytes of the file per workgroup of the member find
+constexpr uint32_t kHeadThreads = 256;      // 16 bytes per thread
+
+// ingest_formats.h's gzip_head on the bytes [off, min(n, off + kGzipHeadReach)) of comp, behind the magic, CM and the reserved
+// flag bits (which the caller has seen): FEXTRA by XLEN, FNAME and FCOMMENT up to their zero byte, FHCRC skipped.  false: the
+// header does not end inside those bytes.
+__device__ __forceinline__ bool member_head(const uint8_t* comp, uint64_t n, uint64_t off, uint64_t* deflate_off) {
+    const uint64_t lim = min(n, off + kGzipHeadReach);
+    if (off + 10 > lim) return false;
+    const uint32_t flg = comp[off + 3];
+    uint64_t o = off + 10;
+    if (flg & 4u) {
+        if (o + 2 > lim) return false;
+        o += 2 + ((uint32_t)comp[o] | (uint32_t)comp[o + 1] << 8);
+        if (o > lim) return false;
+    }
+    for (uint32_t bit = 8; bit <= 16; bit <<= 1) {
+        if (!(flg & bit)) continue;
+        while (o < lim && comp[o] != 0) ++o;
+        if (o >= lim) return false;
+        ++o;
+    }
+    if (flg & 2u) o += 2;
+    if (o > lim) return false;
+    *deflate_off = o;
+    return true;
+}
+
+// Every byte offset of the n bytes at comp (16-byte aligned, 64 zero bytes behind them) at which a member header begins: one
+// lane per 16 offsets tests 1f 8b 08 and FLG & 0xE0 == 0, what passes is parsed by member_head.  kWrite false: tile_count[t] =
+// the headers that begin in tile t (the host scans them); true: tile t's headers to out[tile_first[t] ..] in ascending order,
+// each with the 8 bytes in front of it.  A header may end in any later tile; its first four bytes may straddle two.  A magic
+// inside deflate bytes is a candidate like any other: the chain never reaches it.
+template <bool kWrite>
+__global__ __launch_bounds__(kHeadThreads) void gzip_member_find_kernel(const uint8_t* __restrict__ comp, uint64_t n, uint32_t* __restrict__ tile_count,
+                                                                         const uint32_t* __restrict__ tile_first, GzipMemberCand* __restrict__ out) {
+    __shared__ uint32_t wave_total[kHeadThreads / kWave];
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const uint64_t b = (uint64_t)blockIdx.x * kHeadTile + 16ull * tid;
+    uint32_t w[5] = {0, 0, 0, 0, 0};
+    if (b < n) {                                                    // (b + 20 <= n + 64)
+        const uint4 q = *(const uint4*)(comp + b);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        w[4] = *(const uint32_t*)(comp + b + 16);
+    }
+    uint32_t magic = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t sh = 8u * (i & 3u);
+        const uint32_t v = sh ? (w[i >> 2] >> sh) | (w[(i >> 2) + 1] << (32u - sh)) : w[i >> 2];
+        if ((v & 0xE0FFFFFFu) == 0x00088B1Fu && b + i < n) magic |= 1u << i;
+    }
+    uint32_t heads = 0;
+    for (uint32_t m = magic; m;) {
+        const uint32_t i = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1;
+        uint64_t d;
+        if (member_head(comp, n, b + i, &d)) heads |= 1u << i;
+    }
+    uint32_t incl = (uint32_t)__popc(heads);
+#pragma unroll
+    for (uint32_t d = 1; d < kWave; d <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, kWave);
+        if (lane >= d) incl += t;
+    }
+    if (lane == kWave - 1) wave_total[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kHeadThreads / kWave; ++k) {
+        if (k < wave) before += wave_total[k];
+        total += wave_total[k];
+    }
+    if (!kWrite) {
+        if (tid == 0) tile_count[blockIdx.x] = total;
+        return;
+    }
+    uint64_t at = (uint64_t)tile_first[blockIdx.x] + before + incl - (uint32_t)__popc(heads);
+    for (uint32_t m = heads; m;) {
+        const uint32_t i = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1;
+        const uint64_t off = b + i;
+        uint64_t d = 0;
+        member_head(comp, n, off, &d);
+        GzipMemberCand c;
+        c.header_off = off;
+        c.deflate_bit = 8ull * d;
+        c.prev_crc = c.prev_isize = 0;
+        if (off >= 8) {
+            const uint8_t* t = comp + off - 8;
+            c.prev_crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            c.prev_isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+        }
+        out[at++] = c;
+    }
+}
+
+// One workgroup per piece of the text (at most kSeg bytes at text + off): its CRC register, from zero and without the final
+// inversion, as gzip_resolve_kernel gives one per segment - the pieces are the segments cut where a member ends.
+__global__ __launch_bounds__(kSegThreads) void gzip_piece_crc_kernel(const uint8_t* __restrict__ text, const GzipPiece* __restrict__ pieces,
+                                                                      uint32_t* __restrict__ reg) {
+    __shared__ __align__(16) uint8_t out[kSeg];
+    __shared__ uint32_t crc_table[256];
+    __shared__ uint32_t wave_part[kSegThreads / kWave];
+    const uint32_t tid = threadIdx.x;
+    const GzipPiece pc = pieces[blockIdx.x];
+    const uint32_t n = min(pc.n, kSeg);
+    {
+        uint32_t r = tid;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r = (r & 1u) ? (r >> 1) ^ kPoly : r >> 1;
+        crc_table[tid] = r;
+    }
+    for (uint32_t k = tid; k < n; k += kSegThreads) out[k] = text[pc.off + k];
+    __syncthreads();
+    const uint32_t part = staged_crc_part(out, n, crc_table);
+    if ((tid & (kWave - 1)) == 0) wave_part[tid / kWave] = part;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < kSegThreads / kWave; ++k) total ^= wave_part[k];
+        reg[blockIdx.x] = total;
+    }
 }
 
 constexpr X2n kX2nHost = make_x2n();
@@ -973,20 +1130,39 @@ void launch_gzip_find(const uint8_t* comp, uint64_t end, uint64_t n_words, uint6
     hipLaunchKernelGGL(gzip_find_kernel, dim3(n_chunks), dim3(kWave), 0, s, comp, end, n_words, deflate_off, chunk_bytes, false_sync, starts);
 }
 
-void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s) {
-    hipLaunchKernelGGL(gzip_count_kernel, dim3(n_chunks), dim3(kWave), 0, s, comp, end, starts, n_chunks, spans);
+void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s,
+                       const GzipMemberCand* cands, uint32_t n_cands, uint64_t deflate_off, uint64_t chunk_bytes, GzipSpan* mspans) {
+    hipLaunchKernelGGL(gzip_count_kernel, dim3(n_chunks + n_cands), dim3(kWave), 0, s, comp, end, starts, n_chunks, spans, cands, deflate_off,
+                       chunk_bytes, mspans);
+}
+
+uint32_t gzip_member_tile_bytes() { return kHeadTile; }
+
+void launch_gzip_member_count(const uint8_t* comp, uint64_t n, uint32_t* tile_count, hipStream_t s) {
+    const uint64_t n_tiles = (n + kHeadTile - 1) / kHeadTile;
+    if (n_tiles) hipLaunchKernelGGL(gzip_member_find_kernel<false>, dim3((uint32_t)n_tiles), dim3(kHeadThreads), 0, s, comp, n, tile_count, nullptr, nullptr);
+}
+
+void launch_gzip_member_write(const uint8_t* comp, uint64_t n, const uint32_t* tile_first, GzipMemberCand* out, hipStream_t s) {
+    const uint64_t n_tiles = (n + kHeadTile - 1) / kHeadTile;
+    if (n_tiles) hipLaunchKernelGGL(gzip_member_find_kernel<true>, dim3((uint32_t)n_tiles), dim3(kHeadThreads), 0, s, comp, n, nullptr, tile_first, out);
+}
+
+void launch_gzip_piece_crc(const uint8_t* text, const GzipPiece* pieces, uint32_t n_pieces, uint32_t* reg, hipStream_t s) {
+    if (n_pieces) hipLaunchKernelGGL(gzip_piece_crc_kernel, dim3(n_pieces), dim3(kSegThreads), 0, s, text, pieces, reg);
 }
 
 void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, uint32_t n_jobs, uint16_t* sym, uint32_t* flags, hipStream_t s) {
     if (n_jobs) hipLaunchKernelGGL(gzip_write_kernel, dim3(n_jobs), dim3(kWave), 0, s, comp, end, jobs, sym, flags);
 }
 
-void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
-                         uint32_t* flags, hipStream_t s, uint64_t front) {
+void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, const uint64_t* mfloor, uint32_t n_true, uint64_t text_n, uint8_t* text,
+                         uint32_t* seg_crc, uint32_t* flags, hipStream_t s, uint64_t front) {
     if (text_n == 0) return;
-    if (n_true > 1) hipLaunchKernelGGL(gzip_windows_kernel, dim3(1), dim3(1024), 0, s, sym, text_off, n_true, flags);
+    if (n_true > 1) hipLaunchKernelGGL(gzip_windows_kernel, dim3(1), dim3(1024), 0, s, sym, text_off, mfloor, n_true, flags);
     const uint64_t n_seg = (text_n + kSeg - 1) / kSeg;
-    hipLaunchKernelGGL(gzip_resolve_kernel, dim3((uint32_t)n_seg), dim3(kSegThreads), 0, s, sym, text_off, n_true, text_n, text, seg_crc, flags, front);
+    hipLaunchKernelGGL(gzip_resolve_kernel, dim3((uint32_t)n_seg), dim3(kSegThreads), 0, s, sym, text_off, mfloor, n_true, text_n, text, seg_crc, flags,
+                       front);
 }
 
 uint32_t gzip_ring_symbols() { return kRing; }
@@ -1002,14 +1178,16 @@ uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n) {
     return acc;
 }
 
-uint32_t gzip_crc_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
+uint32_t gzip_crc_register_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
     uint32_t acc = 0;
+    for (uint64_t i = 0; i < n; ++i) acc = crc_shift(acc, len[i]) ^ reg[i];
+    return acc;
+}
+
+uint32_t gzip_crc_chain(const uint32_t* reg, const uint64_t* len, uint64_t n) {
     uint64_t total = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        acc = crc_shift(acc, len[i]) ^ reg[i];
-        total += len[i];
-    }
-    return ~(acc ^ crc_shift(0xFFFFFFFFu, total));
+    for (uint64_t i = 0; i < n; ++i) total += len[i];
+    return ~(gzip_crc_register_chain(reg, len, n) ^ crc_shift(0xFFFFFFFFu, total));
 }
 
 uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n) {

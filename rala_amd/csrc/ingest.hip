@@ -225,6 +225,7 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
     window = text_window_bytes(window);
     ctx->inflate_tm = rala_hip_inflate_timings();
     ctx->gzip_tm = rala_hip_gzip_timings();
+    ctx->gzip_members_last.clear();
     // A gzip file: BGZF is inflated on the device (the windows then lie over its text), so is (option gzip_on_device) any
     // other file of one member - by speculative decoding, the whole text resident afterwards, the windows over it; what is
     // left is the host reader's - known from the first 18 bytes, before anything is shipped.  (A file that cannot be opened
@@ -257,6 +258,7 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         X.gz.file_n = X.file_n;
         rc = gzip_inflate(ctx, X.file.fd, path, threads, X.gz, &valid);
         ctx->gzip_tm = X.gz.tm;
+        if (rc == RALA_HIP_OK && valid) ctx->gzip_members_last = X.gz.members;
         X.text_n = X.gz.text_n;
     } else if (X.kind == kTextBgzf) {
         rc = bgzf_open(ctx, X.file.fd, X.file_n, path, threads, window, X.bg, &valid);

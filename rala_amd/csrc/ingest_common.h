@@ -101,11 +101,21 @@ int bgzf_text_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t lo, uint64_t n_avai
                     const std::function<bool()>& meanwhile, const char* room, TextArrival* out);
 
 // ---- ingest_gzip.hip -----------------------------------------------------------------------------------------------
-// A single-member gzip file whose compressed bytes lie in ctx->d_bgzf_comp, and the chain of its true chunks.
+// A gzip file (one member; with the option gzip_members any number of them) whose compressed bytes lie in ctx->d_bgzf_comp, the
+// chain of its true chunks and its members.
 struct GzipStream {
     std::vector<GzipJob> chain;             // the true chunks, text offsets from the text's start
+    std::vector<GzipMember> members;        // text range, trailer and CRC32 of every member (one: the whole text)
+    std::vector<uint64_t> job_floor;        // per job of the chain: where its member's text begins
     uint64_t file_n = 0, end = 0, text_n = 0;       // file_n: set by the caller
-    uint32_t crc = 0;                       // the trailer's
+    uint32_t crc = 0;                       // the last trailer's
+    // the proof per member: the registers and lengths of the pieces of members[proven]'s text seen so far, and the verdict
+    size_t proven = 0;
+    std::vector<uint32_t> reg;
+    std::vector<uint64_t> len;
+    bool crc_ok = true;
+    uint64_t n_cands = 0;                   // member headers the device found (false ones included)
+    float member_find_ms = 0;
     float ship_ms = 0;
     uint32_t n_readers = 0;
     rala_hip_gzip_timings tm = {};
@@ -116,11 +126,11 @@ int gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, 
 struct GzipWalk : GzipStream {
     uint64_t window = 0;                    // text bytes a window holds at most (at least the largest chunk's)
     size_t next_job = 0;
-    std::vector<uint32_t> reg;              // the windows' CRC registers and lengths
-    std::vector<uint64_t> len;
+    uint64_t windows = 0;
 };
+// chain, members: null, or those of an earlier walk taken over (refused where a member's trailer is no longer what it was)
 int gzip_walk_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, uint64_t want_window, uint64_t front, uint64_t behind,
-                   const std::vector<GzipJob>* chain, GzipWalk& g, bool* valid);
+                   const std::vector<GzipJob>* chain, const std::vector<GzipMember>* members, GzipWalk& g, bool* valid);
 int gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* text, uint64_t* lo, uint64_t* n, uint32_t* flag);
 bool gzip_walk_proven(const GzipWalk& g);
 // the trace line of either driver (windows = 0: the whole text at once)

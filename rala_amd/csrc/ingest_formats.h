@@ -177,5 +177,81 @@ inline bool gzip_chain_from_spans(const uint64_t* starts, const GzipSpan* spans,
     return end_bit / 8 + (end_bit % 8 != 0) == end && (uint32_t)text_n == isize;
 }
 
+// ---- a gzip file of several members (cat a.gz b.gz, pigz -i, appended files) ------------------------------------------------
+// The same walk through a file whose members follow each other as gzread walks them (reference src/graph.cpp:190-224): besides
+// the chunks, the member headers the device found (cands[k], ascending header_off: launch_gzip_member_find) and what it counted
+// from each one's first block (mspans[k], decoded as a stream's first chunk).  Where a final block ends, at bit e, the member's
+// trailer lies at t = ceil(e / 8): the member's text size must be the ISIZE at t + 4 modulo 2^32; with t + 8 the file's end
+// (last_crc, last_isize: the file's last 8 bytes) the walk is done, otherwise a candidate with header_off == t + 8 must exist -
+// the 8 bytes in front of it are that trailer - and the walk goes on at its span.  A member is entered in no other way, so a
+// candidate that is no header (a magic inside deflate bytes) is never looked at.  false: what gzip_chain_from_spans refuses,
+// bytes behind a trailer that are no header, a cut member, an end_bit or a candidate that does not lead forward.
+// chain: first = 1 on every member's first job; members: text range, trailer and CRC32 of each, empty ones included.
+inline bool gzip_chain_members(const uint64_t* starts, const GzipSpan* spans, uint64_t n_chunks, const GzipMemberCand* cands,
+                               const GzipSpan* mspans, uint64_t n_cands, uint64_t file_n, uint32_t last_crc, uint32_t last_isize,
+                               std::vector<GzipJob>& chain, std::vector<GzipMember>& members, rala_hip_gzip_timings* tm) {
+    chain.clear();
+    members.clear();
+    if (!n_chunks || file_n < 8) return false;
+    for (uint64_t c = 1; c < n_chunks; ++c) tm->chunks_with_candidate += starts[c] != kGzipNoStart;
+    uint64_t text_n = 0, member_off = 0, c = 0, start_bit = starts[0];
+    const GzipSpan* sp = &spans[0];
+    bool on_chunk = true, first = true;
+    for (;;) {
+        if (sp->status > 1) return false;
+        GzipJob j;
+        j.start_bit = start_bit;
+        j.stop_bit = kGzipNoStart;
+        j.text_off = text_n;
+        j.text_n = sp->text;
+        j.first = first ? 1u : 0u;
+        j.pad = 0;
+        text_n += sp->text;
+        tm->chunks_refuted += sp->refuted;
+        tm->max_wave_text_bytes = std::max<uint64_t>(tm->max_wave_text_bytes, sp->text);
+        if (sp->status == 0) {
+            const uint64_t nx = sp->next;
+            if (nx >= n_chunks || (on_chunk && nx <= c) || starts[nx] == kGzipNoStart || starts[nx] <= start_bit) return false;
+            j.stop_bit = starts[nx];
+            chain.push_back(j);
+            c = nx;
+            sp = &spans[nx];
+            start_bit = starts[nx];
+            on_chunk = true;
+            first = false;
+            continue;
+        }
+        chain.push_back(j);
+        const uint64_t e = sp->end_bit;
+        if (e <= start_bit) return false;
+        const uint64_t t = e / 8 + (e % 8 != 0);
+        if (t > file_n || file_n - t < 8) return false;                     // (a member that is cut)
+        GzipMember m;
+        m.text_off = member_off;
+        m.text_n = text_n - member_off;
+        m.trailer_off = t;
+        m.pad = 0;
+        if (t + 8 == file_n) {
+            if ((uint32_t)m.text_n != last_isize) return false;
+            m.crc = last_crc;
+            members.push_back(m);
+            break;
+        }
+        const GzipMemberCand* const k = std::lower_bound(cands, cands + n_cands, t + 8, [](const GzipMemberCand& a, uint64_t off) { return a.header_off < off; });
+        if (k == cands + n_cands || k->header_off != t + 8 || k->deflate_bit < 8 * (t + 8 + 10)) return false;
+        if ((uint32_t)m.text_n != k->prev_isize) return false;
+        m.crc = k->prev_crc;
+        members.push_back(m);
+        member_off = text_n;
+        sp = &mspans[k - cands];
+        start_bit = k->deflate_bit;
+        on_chunk = false;
+        first = true;
+    }
+    tm->chunks_confirmed = chain.size() - members.size();
+    tm->text_bytes = text_n;
+    return true;
+}
+
 }  // namespace ingest
 }  // namespace rala_hip

@@ -1,7 +1,9 @@
-// A single-member gzip file (gzip, pigz, Python's gzip) inflated on the device by speculative decoding (inflate_kernels.hip).
-// One front half - the file shipped, block starts found in every chunk, every chunk counted from its start, the chain from
-// chunk 0 built and proven on the host - and two back ends: the whole text at once (overlap files) or window by window
-// (read files).
+// A gzip file that is not BGZF (gzip, pigz, Python's gzip; with the option gzip_members any chain of such members: cat a.gz b.gz,
+// pigz -i) inflated on the device by speculative decoding (inflate_kernels.hip).
+// One front half - the file shipped, member headers and block starts found, every chunk and every member candidate counted from
+// its start, the chain from chunk 0 built and proven on the host - and two back ends: the whole text at once (overlap files)
+// or window by window (read files).  Either proves every member: its ISIZE in the chain, its CRC32 from the registers of the
+// 16 KB segments that lie inside it and of the pieces of those a member boundary cuts.
 #include "ingest_common.h"
 
 using namespace rala_hip;
@@ -9,12 +11,49 @@ using namespace rala_hip::ingest;
 
 namespace {
 
-constexpr uint64_t kGzipHeadReach = 1u << 20;       // a header (name, comment, extra field) longer than this is the host reader's
+// The member headers among the n bytes at comp (launch_gzip_member_count / _write): counted per tile, scanned, written - to
+// ctx->d_gzip_cands, *n_cands of them in ascending order.
+int gzip_member_find(rala_hip_ctx* ctx, const uint8_t* comp, uint64_t n, uint64_t* n_cands) {
+    hipStream_t s = ctx->stream;
+    *n_cands = 0;
+    const uint64_t n_tiles = (n + gzip_member_tile_bytes() - 1) / gzip_member_tile_bytes();
+    if (!n_tiles) return RALA_HIP_OK;
+    if (n_tiles >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit tile ids");
+    if (ctx->d_gzip_tile.ensure(n_tiles + 2) != hipSuccess || ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
+    }
+    launch_gzip_member_count(comp, n, ctx->d_gzip_tile.p, s);
+    launch_exclusive_scan(ctx->d_gzip_tile.p, ctx->d_gzip_tile.p, n_tiles, ctx->d_scan_ws.p, s);
+    INGEST_CHECK(hipGetLastError());
+    uint32_t total = 0;
+    INGEST_CHECK(hipMemcpyAsync(&total, ctx->d_gzip_tile.p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    INGEST_CHECK(hipStreamSynchronize(s));
+    if (ctx->d_gzip_cands.ensure(((size_t)total + 1) * sizeof(GzipMemberCand)) != hipSuccess) {
+        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
+    }
+    launch_gzip_member_write(comp, n, ctx->d_gzip_tile.p, (GzipMemberCand*)ctx->d_gzip_cands.p, s);
+    INGEST_CHECK(hipGetLastError());
+    INGEST_CHECK(hipStreamSynchronize(s));
+    *n_cands = total;
+    return RALA_HIP_OK;
+}
+
+// where the text of every job's member begins
+void job_floors(GzipStream& g) {
+    g.job_floor.resize(g.chain.size());
+    size_t m = 0;
+    for (size_t j = 0; j < g.chain.size(); ++j) {
+        if (j && g.chain[j].first && m + 1 < g.members.size()) ++m;
+        g.job_floor[j] = g.members[m].text_off;
+    }
+}
 
 // The file (g.file_n bytes) to ctx->d_bgzf_comp, where it stays, and its chain: found / counted on the device and built by
-// gzip_chain_from_spans, or (given != null) the chain of an earlier call taken over.  *valid = false: not a stream this can
-// prove - a header the parse refuses, what the chain builder refuses, a chain taken over that is not this file's (ISIZE).
-int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, const std::vector<GzipJob>* given, GzipStream& g, bool* valid) {
+// gzip_chain_from_spans (option gzip_members: gzip_chain_members), or (given != null) the chain and the members of an earlier
+// call taken over.  *valid = false: not a stream this can prove - a header the parse refuses, what the chain builder refuses,
+// a chain taken over that is not this file's (a member's ISIZE or CRC32 is no longer the one it was taken with).
+int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, const std::vector<GzipJob>* given,
+                    const std::vector<GzipMember>* given_members, GzipStream& g, bool* valid) {
     *valid = false;
     const uint64_t file_n = g.file_n;
     std::vector<uint8_t> head((size_t)std::min(file_n, kGzipHeadReach));
@@ -45,46 +84,141 @@ int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t thread
     tm.compressed_bytes = file_n;
     if (given) {
         g.chain = *given;
-        if (g.chain.empty()) return RALA_HIP_OK;
+        if (given_members) g.members = *given_members;
+        if (g.chain.empty() || g.members.empty()) return RALA_HIP_OK;
         for (const GzipJob& j : g.chain) {
             g.text_n += j.text_n;
             tm.max_wave_text_bytes = std::max<uint64_t>(tm.max_wave_text_bytes, j.text_n);
         }
-        tm.chunks_confirmed = g.chain.size() - 1;
+        tm.chunks_confirmed = g.chain.size() - g.members.size();
         tm.text_bytes = g.text_n;
-        *valid = (uint32_t)g.text_n == le32(trailer + 4);
+        // every member's trailer is still where it was and says what it said
+        bool same = g.members.back().trailer_off + 8 == file_n;
+        for (size_t m = 0; same && m < g.members.size(); ++m) {
+            const GzipMember& mem = g.members[m];
+            uint8_t t[8];
+            same = mem.trailer_off + 8 <= file_n && pread(fd, t, 8, (off_t)mem.trailer_off) == 8 && le32(t) == mem.crc && le32(t + 4) == (uint32_t)mem.text_n;
+        }
+        job_floors(g);
+        *valid = same;
         return RALA_HIP_OK;
     }
-    if (ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess || ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess) {
+    const bool members = ctx->gzip_members;
+    uint64_t n_cands = 0;
+    if (members) {
+        const int rc = gzip_member_find(ctx, comp, file_n, &n_cands);
+        if (rc != RALA_HIP_OK) return rc;
+        if (n_chunks + n_cands >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many member candidates for 32-bit span ids");
+    }
+    const double t1b = now_ms();
+    g.n_cands = n_cands;
+    g.member_find_ms = (float)(t1b - t1);
+    if (ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess || ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess ||
+        ctx->d_gzip_mspans.ensure((n_cands + 1) * sizeof(GzipSpan)) != hipSuccess) {
         return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
     }
     launch_gzip_find(comp, end, (file_n + 56) / 8, deflate_off, chunk, (uint32_t)n_chunks, ctx->debug_gzip_false_sync, ctx->d_gzip_starts.p, s);
     INGEST_CHECK(hipGetLastError());
     INGEST_CHECK(hipStreamSynchronize(s));
     const double t2 = now_ms();
-    launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s);
+    launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s, (const GzipMemberCand*)ctx->d_gzip_cands.p,
+                      (uint32_t)n_cands, deflate_off, chunk, (GzipSpan*)ctx->d_gzip_mspans.p);
     INGEST_CHECK(hipGetLastError());
     std::vector<uint64_t> starts(n_chunks);
-    std::vector<GzipSpan> spans(n_chunks);
+    std::vector<GzipSpan> spans(n_chunks), mspans(n_cands);
+    std::vector<GzipMemberCand> cands(n_cands);
     INGEST_CHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
     INGEST_CHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    if (n_cands) {
+        INGEST_CHECK(hipMemcpyAsync(cands.data(), ctx->d_gzip_cands.p, n_cands * sizeof(GzipMemberCand), hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipMemcpyAsync(mspans.data(), ctx->d_gzip_mspans.p, n_cands * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    }
     INGEST_CHECK(hipStreamSynchronize(s));
     const double t3 = now_ms();
     ctx->d_gzip_starts.release();
     ctx->d_gzip_spans.release();
+    ctx->d_gzip_mspans.release();
+    ctx->d_gzip_cands.release();
+    ctx->d_gzip_tile.release();
     tm.chunks = n_chunks;
-    tm.find_ms = (float)(t2 - t1);
+    tm.find_ms = (float)(t2 - t1);                          // (the member find included)
     tm.decode_ms = (float)(t3 - t2);
-    *valid = gzip_chain_from_spans(starts.data(), spans.data(), n_chunks, end, le32(trailer + 4), g.chain, &tm);
+    if (members) {
+        *valid = gzip_chain_members(starts.data(), spans.data(), n_chunks, cands.data(), mspans.data(), n_cands, file_n, le32(trailer), le32(trailer + 4),
+                                    g.chain, g.members, &tm);
+    } else {
+        *valid = gzip_chain_from_spans(starts.data(), spans.data(), n_chunks, end, le32(trailer + 4), g.chain, &tm);
+        g.members.assign(1, GzipMember{0, tm.text_bytes, end, g.crc, 0});
+    }
     g.text_n = tm.text_bytes;
+    if (*valid) job_floors(g);
+    return RALA_HIP_OK;
+}
+
+// The members' CRC32 behind a launch that left the text [lo, lo + n) at `text` and its segments' registers in seg_crc: the
+// members from g.proven on take the registers of the segments that lie inside them and those of the pieces a member boundary
+// cuts off a segment (gzip_piece_crc_kernel: at most two per boundary, one per member that lies inside one segment); a member
+// that ends here is compared with its trailer, one that goes on keeps one register for the next launch.
+int gzip_prove_members(rala_hip_ctx* ctx, GzipStream& g, const uint8_t* text, uint64_t lo, uint64_t n, const std::vector<uint32_t>& seg_crc) {
+    hipStream_t s = ctx->stream;
+    const uint64_t seg = gzip_segment_bytes();
+    struct Item { uint64_t idx, len; int kind; };                    // kind 0: segment idx, 1: piece idx, 2: the member ends
+    std::vector<Item> items;
+    std::vector<GzipPiece> pieces;
+    for (size_t m = g.proven; m < g.members.size(); ++m) {
+        const GzipMember& mem = g.members[m];
+        const uint64_t m_end = mem.text_off + mem.text_n, hi = std::min(m_end, lo + n);
+        for (uint64_t p = std::max(mem.text_off, lo); p < hi;) {
+            const uint64_t k = (p - lo) / seg, seg_lo = lo + k * seg, seg_hi = std::min(seg_lo + seg, lo + n), q = std::min(hi, seg_hi);
+            if (p == seg_lo && q == seg_hi) {
+                items.push_back(Item{k, q - p, 0});
+            } else {
+                items.push_back(Item{pieces.size(), q - p, 1});
+                pieces.push_back(GzipPiece{p - lo, (uint32_t)(q - p), 0});
+            }
+            p = q;
+        }
+        if (m_end > lo + n) break;
+        items.push_back(Item{m, 0, 2});
+    }
+    std::vector<uint32_t> piece_crc(pieces.size());
+    if (!pieces.empty()) {
+        if (pieces.size() >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many member boundaries in one window");
+        if (ctx->d_gzip_pieces.ensure(pieces.size() * sizeof(GzipPiece)) != hipSuccess || ctx->d_gzip_piece_crc.ensure(pieces.size()) != hipSuccess) {
+            return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the members' pieces");
+        }
+        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_pieces.p, pieces.data(), pieces.size() * sizeof(GzipPiece), hipMemcpyHostToDevice, s));
+        launch_gzip_piece_crc(text, (const GzipPiece*)ctx->d_gzip_pieces.p, (uint32_t)pieces.size(), ctx->d_gzip_piece_crc.p, s);
+        INGEST_CHECK(hipGetLastError());
+        INGEST_CHECK(hipMemcpyAsync(piece_crc.data(), ctx->d_gzip_piece_crc.p, pieces.size() * 4, hipMemcpyDeviceToHost, s));
+        INGEST_CHECK(hipStreamSynchronize(s));
+    }
+    for (const Item& it : items) {
+        if (it.kind == 2) {
+            if (gzip_crc_chain(g.reg.data(), g.len.data(), g.reg.size()) != g.members[it.idx].crc) g.crc_ok = false;
+            g.reg.clear();
+            g.len.clear();
+            g.proven = it.idx + 1;
+        } else {
+            g.reg.push_back(it.kind ? piece_crc[it.idx] : seg_crc[it.idx]);
+            g.len.push_back(it.len);
+        }
+    }
+    if (g.reg.size() > 1) {
+        uint64_t total = 0;
+        for (uint64_t l : g.len) total += l;
+        const uint32_t r = gzip_crc_register_chain(g.reg.data(), g.len.data(), g.reg.size());
+        g.reg.assign(1, r);
+        g.len.assign(1, total);
+    }
     return RALA_HIP_OK;
 }
 
 }  // namespace
 
-// Written and resolved in one piece behind the front half (no window, so no 2^31 cap on the text), CRC32 checked.
+// Written and resolved in one piece behind the front half (no window, so no 2^31 cap on the text), every member's CRC32 checked.
 int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, GzipStream& g, bool* valid) {
-    const int rc = gzip_chain_open(ctx, fd, path, threads, nullptr, g, valid);
+    const int rc = gzip_chain_open(ctx, fd, path, threads, nullptr, nullptr, g, valid);
     if (rc != RALA_HIP_OK || !*valid) return rc;
     *valid = false;
     hipStream_t s = ctx->stream;
@@ -95,18 +229,20 @@ int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, 
     if (n_seg >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
     if (ctx->d_gzip_sym.ensure(text_n + 64) != hipSuccess || ctx->d_gzip_text.ensure(text_n + paf_chunk_bytes() + 8192) != hipSuccess ||
         ctx->d_gzip_jobs.ensure(n_jobs * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(n_jobs) != hipSuccess ||
-        ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess) {
+        ctx->d_gzip_floor.ensure(n_jobs) != hipSuccess || ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess) {
         return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the inflated text");
     }
     INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, g.chain.data(), n_jobs * sizeof(GzipJob), hipMemcpyHostToDevice, s));
     INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, g.job_floor.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
     INGEST_CHECK(hipStreamSynchronize(s));
     const double t3 = now_ms();
     launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)n_jobs, ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
     INGEST_CHECK(hipGetLastError());
     INGEST_CHECK(hipStreamSynchronize(s));
     const double t4 = now_ms();
-    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)n_jobs, text_n, ctx->d_gzip_text.p, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s);
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, (uint32_t)n_jobs, text_n, ctx->d_gzip_text.p, ctx->d_gzip_crc.p,
+                        ctx->d_bgzf_flag.p, s);
     INGEST_CHECK(hipGetLastError());
     // what lies behind the text reads as newlines (as for the plain file)
     INGEST_CHECK(hipMemsetAsync(ctx->d_gzip_text.p + text_n, '\n', paf_chunk_bytes() + 8192, s));
@@ -115,12 +251,13 @@ int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, 
     if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
     INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
     INGEST_CHECK(hipStreamSynchronize(s));
+    if (!flag) { const int rcp = gzip_prove_members(ctx, g, ctx->d_gzip_text.p, 0, text_n, seg_crc); if (rcp != RALA_HIP_OK) return rcp; }
     const double t5 = now_ms();
     ctx->d_gzip_sym.release();
     ctx->d_bgzf_comp.release();
     g.tm.decode_ms += (float)(t4 - t3);                     // the counting pass and the writing pass
     g.tm.resolve_ms = (float)(t5 - t4);
-    *valid = !flag && gzip_crc_of_segments(seg_crc.data(), text_n) == g.crc;
+    *valid = !flag && g.crc_ok && g.proven == g.members.size();
     return RALA_HIP_OK;
 }
 
@@ -128,13 +265,16 @@ int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, 
 // the only buffer whose size depends on the file's; write, windows and resolve run per window, a run of consecutive true
 // chunks whose text fits it.  The symbols of a window lie behind a CARRY of gzip_ring_symbols(): the last 32 768 bytes in
 // front of it (0x8000 where the file's text has not begun), so the markers of its first chunks point into bytes, and every
-// text offset the kernels see counts from the carry's first symbol.
-// The front half (chain != null: the chain of an earlier walk taken over), then the buffers of a window made: `front` bytes
-// of room in front of the window's text in ctx->d_gzip_text and `behind` bytes behind it.  want_window 0: what a quarter of
-// the free memory holds at three bytes per text byte.  *valid = false: not a stream this can prove.
+// text offset the kernels see counts from the carry's first symbol.  A window may hold any number of member boundaries: a
+// member's first chunk emits no markers, so the carry needs no reset, and a marker of a later chunk that reaches below its
+// member's first byte - in the carry or not - is refused by the floor the kernels get beside every text offset.
+// The front half (chain != null: the chain and the members of an earlier walk taken over), then the buffers of a window made:
+// `front` bytes of room in front of the window's text in ctx->d_gzip_text and `behind` bytes behind it.  want_window 0: what a
+// quarter of the free memory holds at three bytes per text byte.  *valid = false: not a stream this can prove.
 int rala_hip::ingest::gzip_walk_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t threads, uint64_t want_window, uint64_t front,
-                                     uint64_t behind, const std::vector<GzipJob>* chain, GzipWalk& g, bool* valid) {
-    const int rc = gzip_chain_open(ctx, fd, path, threads, chain, g, valid);
+                                     uint64_t behind, const std::vector<GzipJob>* chain, const std::vector<GzipMember>* members, GzipWalk& g,
+                                     bool* valid) {
+    const int rc = gzip_chain_open(ctx, fd, path, threads, chain, members, g, valid);
     if (rc != RALA_HIP_OK || !*valid) return rc;
     *valid = false;
     hipStream_t s = ctx->stream;
@@ -171,25 +311,33 @@ int rala_hip::ingest::gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* te
     while (j1 < g.chain.size() && (j1 == j0 || n_w + g.chain[j1].text_n <= g.window)) n_w += g.chain[j1++].text_n;
     const uint64_t a = g.chain[j0].text_off;
     std::vector<GzipJob> jobs(g.chain.begin() + j0, g.chain.begin() + j1);
-    std::vector<uint64_t> text_off(jobs.size());
-    for (size_t j = 0; j < jobs.size(); ++j) text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - a);
+    std::vector<uint64_t> text_off(jobs.size()), floors(jobs.size());
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - a);
+        // the member's first text position in this launch's coordinates, the carry's first symbol at the least
+        const uint64_t f = g.job_floor[j0 + j];
+        floors[j] = f + ring >= a ? f + ring - a : 0;
+    }
     if (n_w > g.window) return ingest_fail(ctx, RALA_HIP_EDEVICE, "a chunk larger than the window");
     *lo = a;
     *n = n_w;
     *flag = 0;
     g.next_job = j1;
-    if (ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess) {
+    if (ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess ||
+        ctx->d_gzip_floor.ensure(jobs.size()) != hipSuccess) {
         return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's chunks");
     }
     const double t0 = now_ms();
     INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
     INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, floors.data(), floors.size() * 8, hipMemcpyHostToDevice, s));
     launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
     INGEST_CHECK(hipGetLastError());
     INGEST_CHECK(hipStreamSynchronize(s));
     const double t1 = now_ms();
     const uint64_t n_seg = (n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
-    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)jobs.size(), n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s, ring);
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, (uint32_t)jobs.size(), n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p,
+                        s, ring);
     INGEST_CHECK(hipGetLastError());
     std::vector<uint32_t> seg_crc(n_seg);
     if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
@@ -197,24 +345,28 @@ int rala_hip::ingest::gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* te
     if (j1 < g.chain.size()) launch_gzip_carry(ctx->d_gzip_sym.p, text, n_w, ctx->d_gzip_carry.p, s);
     INGEST_CHECK(hipGetLastError());
     INGEST_CHECK(hipStreamSynchronize(s));
+    if (!*flag) { const int rc = gzip_prove_members(ctx, g, text, a, n_w, seg_crc); if (rc != RALA_HIP_OK) return rc; }
     g.tm.decode_ms += (float)(t1 - t0);
     g.tm.resolve_ms += (float)(now_ms() - t1);
-    g.reg.push_back(gzip_crc_register(seg_crc.data(), n_w));
-    g.len.push_back(n_w);
+    ++g.windows;
     return RALA_HIP_OK;
 }
 
-// behind the last window: is the text the trailer's?
+// behind the last window: was every member's text its trailer's?
 bool rala_hip::ingest::gzip_walk_proven(const GzipWalk& g) {
-    return g.next_job == g.chain.size() && gzip_crc_chain(g.reg.data(), g.len.data(), g.reg.size()) == g.crc;
+    return g.next_job == g.chain.size() && g.proven == g.members.size() && g.crc_ok;
 }
 
 void rala_hip::ingest::trace_gzip(const GzipStream& g, uint64_t windows, uint64_t window) {
     const rala_hip_gzip_timings& t = g.tm;
-    char in[96] = "";
+    char in[96] = "", members[160] = "one gzip member";
     if (windows) snprintf(in, sizeof(in), " in %lu windows of at most %.3f GB of text", (unsigned long)windows, window / 1e9);
-    fprintf(stderr, "[trace] device inflate: one gzip member%s, %.3f GB compressed shipped in %.1f ms, %lu chunks (%lu with a candidate, %lu "
-            "confirmed, %lu refuted), %.3f GB of text (at most %.3f GB by one wave): find %.2f ms, decode %.2f ms, resolve %.2f ms\n", in,
+    if (g.members.size() > 1) {
+        snprintf(members, sizeof(members), "%lu gzip members (%lu header candidates found in %.2f ms)", (unsigned long)g.members.size(),
+                 (unsigned long)g.n_cands, g.member_find_ms);
+    }
+    fprintf(stderr, "[trace] device inflate: %s%s, %.3f GB compressed shipped in %.1f ms, %lu chunks (%lu with a candidate, %lu "
+            "confirmed, %lu refuted), %.3f GB of text (at most %.3f GB by one wave): find %.2f ms, decode %.2f ms, resolve %.2f ms\n", members, in,
             t.compressed_bytes / 1e9, g.ship_ms, (unsigned long)t.chunks, (unsigned long)t.chunks_with_candidate, (unsigned long)t.chunks_confirmed,
             (unsigned long)t.chunks_refuted, t.text_bytes / 1e9, t.max_wave_text_bytes / 1e9, t.find_ms, t.decode_ms, t.resolve_ms);
 }
@@ -251,6 +403,87 @@ int rala_hip_gzip_chain(const uint64_t* starts, const uint64_t* end_bit, const u
         if (stop_bit) stop_bit[j] = chain[j].stop_bit;
         if (text_off) text_off[j] = chain[j].text_off;
         if (text_n) text_n[j] = chain[j].text_n;
+    }
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_chain_members(const uint64_t* starts, const uint64_t* end_bit, const uint64_t* text, const uint32_t* next, const uint32_t* status,
+                                const uint32_t* refuted, uint64_t n_chunks, const uint64_t* cand_header_off, const uint64_t* cand_deflate_bit,
+                                const uint32_t* cand_prev_crc, const uint32_t* cand_prev_isize, const uint64_t* cand_end_bit, const uint64_t* cand_text,
+                                const uint32_t* cand_next, const uint32_t* cand_status, uint64_t n_cands, uint64_t file_n, uint32_t last_crc,
+                                uint32_t last_isize, uint64_t cap, uint64_t* n_jobs, uint64_t* start_bit, uint64_t* stop_bit, uint64_t* text_off,
+                                uint64_t* text_n, uint32_t* first, uint64_t member_cap, uint64_t* n_members, uint64_t* member_text_off,
+                                uint64_t* member_text_n, uint32_t* member_crc32, rala_hip_gzip_timings* stats, int* valid) {
+    if (!n_jobs || !n_members || !valid || (n_chunks && (!starts || !end_bit || !text || !next || !status || !refuted)) ||
+        (n_cands && (!cand_header_off || !cand_deflate_bit || !cand_prev_crc || !cand_prev_isize || !cand_end_bit || !cand_text || !cand_next || !cand_status))) {
+        return RALA_HIP_EINVAL;
+    }
+    std::vector<GzipSpan> spans(n_chunks), mspans(n_cands);
+    std::vector<GzipMemberCand> cands(n_cands);
+    for (uint64_t c = 0; c < n_chunks; ++c) spans[c] = GzipSpan{end_bit[c], text[c], next[c], status[c], refuted[c], 0};
+    for (uint64_t k = 0; k < n_cands; ++k) {
+        cands[k] = GzipMemberCand{cand_header_off[k], cand_deflate_bit[k], cand_prev_crc[k], cand_prev_isize[k]};
+        mspans[k] = GzipSpan{cand_end_bit[k], cand_text[k], cand_next[k], cand_status[k], 0, 0};
+    }
+    std::vector<GzipJob> chain;
+    std::vector<GzipMember> members;
+    rala_hip_gzip_timings tm = {};
+    tm.chunks = n_chunks;
+    *valid = gzip_chain_members(starts, spans.data(), n_chunks, cands.data(), mspans.data(), n_cands, file_n, last_crc, last_isize, chain, members, &tm) ? 1 : 0;
+    if (stats) *stats = tm;
+    *n_jobs = *valid ? chain.size() : 0;
+    *n_members = *valid ? members.size() : 0;
+    if (!*valid) return RALA_HIP_OK;
+    for (size_t j = 0; j < chain.size() && cap >= chain.size(); ++j) {
+        if (start_bit) start_bit[j] = chain[j].start_bit;
+        if (stop_bit) stop_bit[j] = chain[j].stop_bit;
+        if (text_off) text_off[j] = chain[j].text_off;
+        if (text_n) text_n[j] = chain[j].text_n;
+        if (first) first[j] = chain[j].first;
+    }
+    for (size_t m = 0; m < members.size() && member_cap >= members.size(); ++m) {
+        if (member_text_off) member_text_off[m] = members[m].text_off;
+        if (member_text_n) member_text_n[m] = members[m].text_n;
+        if (member_crc32) member_crc32[m] = members[m].crc;
+    }
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_find_members(rala_hip_ctx* ctx, const uint8_t* bytes, uint64_t n, uint64_t cap, uint64_t* n_found, uint64_t* header_off,
+                               uint64_t* deflate_off) {
+    if (!ctx || !n_found || (!bytes && n)) return RALA_HIP_EINVAL;
+    *n_found = 0;
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if (ctx->d_bgzf_comp.ensure(n + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the bytes");
+    struct Release {
+        rala_hip_ctx* ctx;
+        ~Release() { ctx->d_bgzf_comp.release(); ctx->d_gzip_cands.release(); ctx->d_gzip_tile.release(); }
+    } release{ctx};
+    if (n) INGEST_CHECK(hipMemcpyAsync(ctx->d_bgzf_comp.p, bytes, n, hipMemcpyHostToDevice, s));
+    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + n, 0, 64, s));
+    uint64_t found = 0;
+    const int rc = gzip_member_find(ctx, ctx->d_bgzf_comp.p, n, &found);
+    if (rc != RALA_HIP_OK) return rc;
+    *n_found = found;
+    if (!found || cap < found) return RALA_HIP_OK;
+    std::vector<GzipMemberCand> cands(found);
+    INGEST_CHECK(hipMemcpy(cands.data(), ctx->d_gzip_cands.p, found * sizeof(GzipMemberCand), hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < found; ++k) {
+        if (header_off) header_off[k] = cands[k].header_off;
+        if (deflate_off) deflate_off[k] = cands[k].deflate_bit / 8;
+    }
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_gzip_members(rala_hip_ctx* ctx, uint64_t* n, uint64_t cap, uint64_t* text_off, uint64_t* text_n, uint32_t* crc32) {
+    if (!ctx || !n) return RALA_HIP_EINVAL;
+    const std::vector<GzipMember>& m = ctx->gzip_members_last;
+    *n = m.size();
+    for (size_t k = 0; k < m.size() && cap >= m.size(); ++k) {
+        if (text_off) text_off[k] = m[k].text_off;
+        if (text_n) text_n[k] = m[k].text_n;
+        if (crc32) crc32[k] = m[k].crc;
     }
     return RALA_HIP_OK;
 }

@@ -111,7 +111,7 @@ struct TextSource {
 };
 
 // *valid = false: a gzip file this does not take (not BGZF and gzip_ok false, or one the inflaters cannot prove)
-int source_open(rala_hip_ctx* ctx, TextSource& S, bool gzip_ok, const std::vector<GzipJob>* chain, bool* valid) {
+int source_open(rala_hip_ctx* ctx, TextSource& S, bool gzip_ok, const std::vector<GzipJob>* chain, const std::vector<GzipMember>* members, bool* valid) {
     *valid = true;
     S.text_n = S.file_n;
     S.window = std::min<uint64_t>(text_window_bytes((uint64_t)ctx->debug_sequence_window), 1ull << 31);
@@ -134,7 +134,7 @@ int source_open(rala_hip_ctx* ctx, TextSource& S, bool gzip_ok, const std::vecto
         const uint64_t tile = sequence_tile_bytes(), halo = sequence_halo_bytes();
         S.front = (halo + 15) / 16 * 16;
         const int rc = gzip_walk_open(ctx, S.fd, S.path.c_str(), S.threads, (uint64_t)ctx->debug_sequence_window, S.front, tile + halo + 64 + 16, chain,
-                                      *S.gz, valid);
+                                      members, *S.gz, valid);
         if (rc != RALA_HIP_OK) return rc;
         S.text_n = S.gz->text_n;
         S.ship_ms = S.gz->ship_ms;
@@ -233,6 +233,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     ctx->seq_index_valid = false;
     ctx->n_seq_records = ctx->n_seq_name_bytes = 0;
     ctx->seq_tm = rala_hip_ingest_timings();
+    ctx->gzip_members_last.clear();
     INGEST_CHECK(hipSetDevice(ctx->device));
     Fd file;
     uint64_t file_n = 0;
@@ -246,7 +247,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     S.file_n = file_n;
     {
         bool valid = true;
-        const int rc = source_open(ctx, S, ctx->gzip_on_device, nullptr, &valid);
+        const int rc = source_open(ctx, S, ctx->gzip_on_device, nullptr, nullptr, &valid);
         if (S.gz) ctx->gzip_tm = S.gz->tm;
         if (rc != RALA_HIP_OK || !valid) {
             source_close(ctx);
@@ -274,7 +275,8 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     if (S.gz) {
         ctx->gzip_tm = S.gz->tm;
         if (rc == RALA_HIP_OK && !S.flag && !gzip_walk_proven(*S.gz)) S.flag = 8;
-        if (getenv("RALA_HIP_TRACE")) trace_gzip(*S.gz, S.gz->reg.size(), S.gz->window);
+        if (getenv("RALA_HIP_TRACE")) trace_gzip(*S.gz, S.gz->windows, S.gz->window);
+        if (rc == RALA_HIP_OK && !S.flag) ctx->gzip_members_last = S.gz->members;
     }
     if (S.flag) flags = 8;
     const double ship_ms = S.ship_ms;
@@ -324,8 +326,10 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     ctx->seq_text_n = R.text_n;
     ctx->seq_n_stripped = R.n_stripped;
     ctx->seq_gzip_chain.clear();
+    ctx->seq_gzip_members.clear();
     if (S.gz) {
         ctx->seq_gzip_chain.swap(S.gz->chain);
+        ctx->seq_gzip_members.swap(S.gz->members);
         ctx->seq_gzip_crc = S.gz->crc;
     }
     *n_records = R.n_records;
@@ -409,7 +413,8 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
     S.file_n = file_n;
     {
         bool valid = true;
-        const int rc = source_open(ctx, S, ctx->seq_source == kTextGzip, ctx->seq_source == kTextGzip ? &ctx->seq_gzip_chain : nullptr, &valid);
+        const bool gz = ctx->seq_source == kTextGzip;
+        const int rc = source_open(ctx, S, gz, gz ? &ctx->seq_gzip_chain : nullptr, gz ? &ctx->seq_gzip_members : nullptr, &valid);
         if (rc != RALA_HIP_OK || !valid || S.kind != ctx->seq_source || S.text_n != ctx->seq_text_n ||
             (S.gz && (S.gz->crc != ctx->seq_gzip_crc || S.gz->chain.back().stop_bit != kGzipNoStart))) {
             if (rc != RALA_HIP_OK) return rc;

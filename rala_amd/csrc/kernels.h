@@ -602,17 +602,32 @@ void launch_bgzf_inflate(const uint8_t* comp, const BgzfJob* jobs, uint32_t n_jo
 // false_sync n != 0 (tests): every n-th chunk is given its first bit as its start
 void launch_gzip_find(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t n_chunks,
                       uint32_t false_sync, uint64_t* starts, hipStream_t s);
-void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s);
+// spans[c]: what decoding from chunk c's start gives.  With member candidates (cands[k], k < n_cands: launch_gzip_member_write;
+// deflate_off, chunk_bytes: launch_gzip_find's) mspans[k] is the same from candidate k's first block, decoded as a stream's first
+// chunk; a span lands on chunk starts only, never on a candidate.
+void launch_gzip_count(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, GzipSpan* spans, hipStream_t s,
+                       const GzipMemberCand* cands = nullptr, uint32_t n_cands = 0, uint64_t deflate_off = 0, uint64_t chunk_bytes = 1,
+                       GzipSpan* mspans = nullptr);
+// The member headers (ingest_formats.h: gzip_head at every byte offset) among the n bytes at comp (16-byte aligned, 64 zero bytes
+// behind them): count - tile_count[t] = those that begin in tile t of gzip_member_tile_bytes(); the caller scans the counts
+// (launch_exclusive_scan) and write puts tile t's candidates to out[tile_first[t] ..], ascending, exact, no capacity.
+uint32_t gzip_member_tile_bytes();
+void launch_gzip_member_count(const uint8_t* comp, uint64_t n, uint32_t* tile_count, hipStream_t s);
+void launch_gzip_member_write(const uint8_t* comp, uint64_t n, const uint32_t* tile_first, GzipMemberCand* out, hipStream_t s);
+// reg[p] = the CRC register (from zero, no final inversion) of piece p of the text: pieces[p].n <= gzip_segment_bytes() bytes at
+// text + pieces[p].off - the segments of launch_gzip_resolve cut where a member of the file ends
+void launch_gzip_piece_crc(const uint8_t* text, const GzipPiece* pieces, uint32_t n_pieces, uint32_t* reg, hipStream_t s);
 // flags |= 8 where a job does not give what the counting pass said
 void launch_gzip_write(const uint8_t* comp, uint64_t end, const GzipJob* jobs, uint32_t n_jobs, uint16_t* sym, uint32_t* flags, hipStream_t s);
-// text_off[j] = job j's text offset; sym (readable 64 symbols behind text_n) -> text, and the CRC register of every
-// gzip_segment_bytes() of it in seg_crc; flags |= 8: a symbol that points in front of the text
+// text_off[j] = job j's text offset, mfloor[j] = where the text of job j's member begins (a member that began in front of the
+// buffer: 0); sym (readable 64 symbols behind text_n) -> text, and the CRC register of every gzip_segment_bytes() of it in
+// seg_crc; flags |= 8: a symbol that points in front of its member's text
 // A WINDOW of the text (the jobs of a run of consecutive true chunks): front = gzip_ring_symbols() symbols in front of the
 // window's first one hold the bytes in front of the window (the carry; 0x8000: no such byte, the file's text begins behind
 // it), text_off[] counts from the buffer's start (the first job's is `front`) and text_n is the window's; front = 0: the
 // whole text at once.
-void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, uint32_t n_true, uint64_t text_n, uint8_t* text, uint32_t* seg_crc,
-                         uint32_t* flags, hipStream_t s, uint64_t front = 0);
+void launch_gzip_resolve(uint16_t* sym, const uint64_t* text_off, const uint64_t* mfloor, uint32_t n_true, uint64_t text_n, uint8_t* text,
+                         uint32_t* seg_crc, uint32_t* flags, hipStream_t s, uint64_t front = 0);
 uint32_t gzip_segment_bytes();
 uint32_t gzip_ring_symbols();
 uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n);        // (host) the text's CRC32
@@ -623,6 +638,8 @@ void launch_gzip_carry(uint16_t* sym, const uint8_t* text, uint64_t text_n, uint
 uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n);
 // (host) the CRC32 of pieces laid end to end from each piece's register (from zero, no final inversion) and length
 uint32_t gzip_crc_chain(const uint32_t* reg, const uint64_t* len, uint64_t n);
+// (host) the register of those pieces laid end to end: one piece for a later chain
+uint32_t gzip_crc_register_chain(const uint32_t* reg, const uint64_t* len, uint64_t n);
 
 // ---- scans (scan_kernels.hip) --------------------------------------------------
 // exclusive prefix sum of n uint32 values; out may alias in; out[n] receives the total

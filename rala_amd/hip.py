@@ -31,7 +31,7 @@ SYMBOLS = (
     "rala_hip_copy_device_state", "rala_hip_layout", "rala_hip_find_repetitive_hills",
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
-    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
     "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",
@@ -185,6 +185,10 @@ def lib(build=True):
         L.rala_hip_crc32_chain.argtypes = [vp, vp, u64]
         L.rala_hip_crc32_chain.restype = u32
         L.rala_hip_gzip_chain.argtypes = [vp] * 6 + [u64, u64, u32, u64, ctypes.POINTER(u64)] + [vp] * 4 + [ctypes.POINTER(GzipTimings), ctypes.POINTER(i32)]
+        L.rala_hip_gzip_chain_members.argtypes = ([vp] * 6 + [u64] + [vp] * 8 + [u64, u64, u32, u32, u64, ctypes.POINTER(u64)] + [vp] * 5 +
+                                                  [u64, ctypes.POINTER(u64)] + [vp] * 3 + [ctypes.POINTER(GzipTimings), ctypes.POINTER(i32)])
+        L.rala_hip_gzip_find_members.argtypes = [vp, vp, u64, u64, ctypes.POINTER(u64), vp, vp]
+        L.rala_hip_get_gzip_members.argtypes = [vp, ctypes.POINTER(u64), u64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -366,6 +370,23 @@ class Context:
         t = GzipTimings()
         self._check(self.L.rala_hip_get_gzip_timings(self.h, ctypes.byref(t)))
         return t.as_dict()
+
+    def gzip_members(self):
+        """rala_hip_get_gzip_members: (text_off, text_n, crc32) of every member of the gzip file the last ingest inflated"""
+        n = ctypes.c_uint64(0)
+        self._check(self.L.rala_hip_get_gzip_members(self.h, ctypes.byref(n), 0, None, None, None))
+        off, size, crc = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+        self._check(self.L.rala_hip_get_gzip_members(self.h, ctypes.byref(n), n.value, off.ctypes.data, size.ctypes.data, crc.ctypes.data))
+        return [(int(a), int(b), int(c)) for a, b, c in zip(off, size, crc)]
+
+    def gzip_find_members(self, data):
+        """rala_hip_gzip_find_members: [(header offset, deflate offset)] of every member header among the bytes, found on the device"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        self._check(self.L.rala_hip_gzip_find_members(self.h, buf.ctypes.data, len(buf), 0, ctypes.byref(n), None, None))
+        head, deflate = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64)
+        self._check(self.L.rala_hip_gzip_find_members(self.h, buf.ctypes.data, len(buf), n.value, ctypes.byref(n), head.ctypes.data, deflate.ctypes.data))
+        return list(zip(head.tolist(), deflate.tolist()))
 
     def sequence_timings(self):
         t = IngestTimings()
@@ -759,3 +780,28 @@ def gzip_chain(starts, end_bit, text, nxt, status, refuted, end, isize):
                                    ctypes.byref(tm), ctypes.byref(valid))
     assert rc == 0
     return (tuple(a[:n_jobs.value] for a in out) if valid.value else None), tm.as_dict()
+
+
+def gzip_chain_members(chunks, cands, file_n, last_crc, last_isize):
+    """rala_hip_gzip_chain_members (no device): the chain through a gzip file of several members.  chunks: dict of the arrays
+    starts, end_bit, text, next, status, refuted; cands: dict of header_off, deflate_bit, prev_crc, prev_isize, end_bit, text, next,
+    status (ascending header_off) -> (None when refused, else (jobs: start_bit, stop_bit, text_off, text_n, first; members:
+    [(text_off, text_n, crc32)])), the walk's counters"""
+    u64a, u32a = (lambda a: np.ascontiguousarray(a, dtype=np.uint64)), (lambda a: np.ascontiguousarray(a, dtype=np.uint32))
+    c = [u64a(chunks["starts"]), u64a(chunks["end_bit"]), u64a(chunks["text"]), u32a(chunks["next"]), u32a(chunks["status"]), u32a(chunks["refuted"])]
+    k = [u64a(cands["header_off"]), u64a(cands["deflate_bit"]), u32a(cands["prev_crc"]), u32a(cands["prev_isize"]), u64a(cands["end_bit"]),
+         u64a(cands["text"]), u32a(cands["next"]), u32a(cands["status"])]
+    n, nk = len(c[0]), len(k[0])
+    assert all(len(a) == n for a in c) and all(len(a) == nk for a in k)
+    cap = n + nk + 1
+    jobs = [np.zeros(cap, dtype=np.uint64) for _ in range(4)] + [np.zeros(cap, dtype=np.uint32)]
+    mem = [np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)]
+    n_jobs, n_members, valid, tm = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int32(0), GzipTimings()
+    rc = lib().rala_hip_gzip_chain_members(*[a.ctypes.data for a in c], n, *[a.ctypes.data for a in k], nk, file_n, last_crc, last_isize, cap,
+                                           ctypes.byref(n_jobs), *[a.ctypes.data for a in jobs], cap, ctypes.byref(n_members),
+                                           *[a.ctypes.data for a in mem], ctypes.byref(tm), ctypes.byref(valid))
+    assert rc == 0
+    if not valid.value:
+        return None, tm.as_dict()
+    members = [(int(a), int(b), int(x)) for a, b, x in zip(*[m[:n_members.value] for m in mem])]
+    return (tuple(a[:n_jobs.value] for a in jobs), members), tm.as_dict()

@@ -4,7 +4,7 @@
 // writes).  Ingest: an uncompressed file's text goes to the device and is tokenised there
 // (rala_hip_set_overlaps_from_paf; ms_parse = ship + tokenise, ms_upload = the name table), a
 // BGZF file's members are inflated there first, a single-member gzip file too where
-// io::device_gzip_wanted(); a file the device tokeniser
+// io::device_gzip_wanted() (one of several members where io::device_gzip_members_wanted()); a file the device tokeniser
 // calls irregular, or device_ingest = 0: the host readers (multi-threaded parse, then the columns'
 // upload).
 #include <stdint.h>
@@ -48,6 +48,8 @@ extern "C" int rala_e2e_from_paf_with(const char* paf_path, const uint32_t* read
         t1 = clock::now();
         // (a single-member gzip file: inflated on the device where io::device_gzip_wanted() says so; no room for it there: the host reader)
         if (rc == RALA_HIP_OK && rala::io::has_suffix(path, ".gz") && rala::io::device_gzip_wanted()) rc = rala_hip_set_option(ctx, "gzip_on_device", 1);
+        // (several members, RALA_DEVICE_GZIP=2: io::device_gzip_members_wanted())
+        if (rc == RALA_HIP_OK && rala::io::has_suffix(path, ".gz") && rala::io::device_gzip_members_wanted()) rc = rala_hip_set_option(ctx, "gzip_members", 1);
         // (measurements, tools/e2e_bench.py: the chunk size of that inflater)
         if (rc == RALA_HIP_OK && getenv("RALA_E2E_GZIP_CHUNK")) rc = rala_hip_set_option(ctx, "gzip_chunk_bytes", atoll(getenv("RALA_E2E_GZIP_CHUNK")));
         if (rc == RALA_HIP_OK) rc = rala_hip_set_overlaps_from_paf(ctx, paf_path, 1, num_threads, &bad, &irregular);

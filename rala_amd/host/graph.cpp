@@ -269,6 +269,9 @@ bool Graph::index_sequences() {
     // raises it for itself where the same switch is on: whoever set it on this context keeps it
     const bool gzip_wanted = io::has_suffix(sequences_path_, ".gz") && io::device_gzip_wanted();
     if (gzip_wanted) check(ctx_, rala_hip_set_option(ctx_, "gzip_on_device", 1), "initialize");
+    // (RALA_DEVICE_GZIP=2: a file of several members - cat a.fastq.gz b.fastq.gz, what gzread walks transparently, reference
+    // src/graph.cpp:190-224 - as well)
+    if (gzip_wanted && io::device_gzip_members_wanted()) check(ctx_, rala_hip_set_option(ctx_, "gzip_members", 1), "initialize");
     // (several GPUs: the main context indexes the file; rala_hip_mg_set_reads receives the lengths as always)
     const int rc = rala_hip_index_sequences(ctx_, sequences_path_.c_str(), fastq ? 1 : 0, std::max(1u, num_threads_), &n, &name_bytes, &irregular);
     if (rc != RALA_HIP_OK || irregular) return false;
@@ -346,6 +349,7 @@ void Graph::initialize() {
     // any other irregular file, and the host reader below decides
     if (gz && ranks_.empty() && device_ingest && io::device_gzip_wanted()) {
         check(ctx_, rala_hip_set_option(ctx_, "gzip_on_device", 1), "initialize");
+        if (io::device_gzip_members_wanted()) check(ctx_, rala_hip_set_option(ctx_, "gzip_members", 1), "initialize");
     }
     auto falls_back = [](int rc) { return rc == RALA_HIP_ENOTAFILE || rc == RALA_HIP_ETOOLARGE || rc == RALA_HIP_ENOMEM; };
     auto length_error = [](int64_t bad) {

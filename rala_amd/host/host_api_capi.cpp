@@ -134,6 +134,8 @@ struct PafOnDevice {
     std::vector<uint8_t> strand;
     rala_hip_ingest_timings tm = {};
     rala_hip_gzip_timings gz = {};
+    std::vector<uint64_t> member_off, member_n;     // rala_hip_get_gzip_members of the call
+    std::vector<uint32_t> member_crc;
     int before_irregular = 0;       // what the file ingested first on the same context gave (hp_text_device_after)
     int64_t before_bad = -1;
 };
@@ -191,6 +193,12 @@ static void* text_on_device(const char* path, const char* names, const uint32_t*
     }
     if (out->rc == RALA_HIP_OK) rala_hip_get_ingest_timings(ctx, &out->tm);
     if (out->rc == RALA_HIP_OK) rala_hip_get_gzip_timings(ctx, &out->gz);
+    uint64_t n_members = 0;
+    if (out->rc == RALA_HIP_OK) out->rc = rala_hip_get_gzip_members(ctx, &n_members, 0, nullptr, nullptr, nullptr);
+    if (out->rc == RALA_HIP_OK && n_members) {
+        out->member_off.resize(n_members); out->member_n.resize(n_members); out->member_crc.resize(n_members);
+        out->rc = rala_hip_get_gzip_members(ctx, &n_members, n_members, out->member_off.data(), out->member_n.data(), out->member_crc.data());
+    }
     if (out->rc == RALA_HIP_OK && !out->irregular && out->bad < 0) {
         out->rc = rala_hip_get_overlap_columns(ctx, &out->n, nullptr, nullptr);
         uint32_t* cols[7];
@@ -303,6 +311,14 @@ void hp_paf_device_gzip_info(void* h, int64_t* info) {
     info[3] = (int64_t)g.compressed_bytes; info[4] = (int64_t)g.text_bytes; info[5] = (int64_t)g.chunks;
     info[6] = (int64_t)g.chunks_with_candidate; info[7] = (int64_t)g.chunks_confirmed; info[8] = (int64_t)g.chunks_refuted;
     info[9] = (int64_t)g.max_wave_text_bytes;
+}
+// the members rala_hip_get_gzip_members gave behind the call (tests/test_gpu_gzip_members.py): their number; with cap >= it, each
+// one's text offset, text size and CRC32
+uint64_t hp_paf_device_gzip_members(void* h, uint64_t cap, uint64_t* text_off, uint64_t* text_n, uint32_t* crc32) {
+    const auto* o = (const PafOnDevice*)h;
+    const uint64_t n = o->member_off.size();
+    for (uint64_t k = 0; k < n && cap >= n; ++k) { text_off[k] = o->member_off[k]; text_n[k] = o->member_n[k]; crc32[k] = o->member_crc[k]; }
+    return n;
 }
 void hp_paf_device_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uint32_t* a_end, uint32_t* b_begin, uint32_t* b_end,
                         uint32_t* length, uint8_t* strand) {

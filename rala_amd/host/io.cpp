@@ -72,6 +72,11 @@ bool device_gzip_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool device_gzip_members_wanted() {
+    const char* e = getenv("RALA_DEVICE_GZIP");
+    return e ? atoi(e) == 2 : false;
+}
+
 bool pile_rows_wanted() {
     const char* e = getenv("RALA_PILE_ROWS");
     return e ? atoi(e) != 0 : true;

@@ -37,6 +37,9 @@ bool has_suffix(const std::string& src, const std::string& suffix);
 /*! @brief is a single-member gzip overlap file inflated on the device (rala_hip option "gzip_on_device")?  RALA_DEVICE_GZIP=1 / =0
  * says so, read where the file is opened; without it: no - see README.md, "Compressed overlap files", for what was measured */
 bool device_gzip_wanted();
+/*! @brief ... and is a gzip file of several members that is not BGZF (cat a.gz b.gz, pigz -i) walked member by member there (rala_hip
+ * option "gzip_members") instead of handed to the host reader?  RALA_DEVICE_GZIP=2 says so (and says device_gzip_wanted() as well) */
+bool device_gzip_members_wanted();
 
 /*! @brief are the piles' coverage rows resident on the device (rala_hip option "pile_rows")?  RALA_PILE_ROWS=0 says no - a row is
  * then rebuilt from the read's overlap bounds when Pile::data() or the -d output asks for it, and the device holds 2 bytes per base
