@@ -268,6 +268,22 @@ int rala_hip_get_gzip_members(rala_hip_ctx* ctx, uint64_t* n, uint64_t cap, uint
  * exclusive scan of the text sizes) are written to the arrays given (any may be null). */
 int rala_hip_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t block_bytes, uint64_t cap, uint64_t* n_members, uint64_t* file_off,
                         uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* text_off, int* valid);
+/* A BGZF file in PIECES by compressed byte range (no context, no device; what a rank of a sharded run does with its share of
+ * the file, rala_hip_mg_set_overlaps_from_paf with the option "bgzf_in_pieces"): the piece [lo, hi) of the n bytes holds the
+ * members whose header BEGINS in it - found by the same scan over blocks of block_bytes (0: 32 MB) that start at lo, walked as
+ * a chain from the first candidate in the range until the chain reaches an offset >= hi, where a candidate or the file's end
+ * must stand; a member's ISIZE is read from the 4 bytes in front of the next header.  Nothing in front of lo is looked at
+ * (but the 8 bytes in front of a block).  *begin: the offset of the piece's first member; *end: the offset the chain
+ * reached; *empty: no header begins in the range.  *valid = 0: the chain broke (what rala_hip_bgzf_index refuses), or lo = 0
+ * and the first 18 bytes are no BGZF header.  A piece that is valid says nothing about the file: the caller joins the pieces
+ * with rala_hip_bgzf_pieces_chain.  When cap >= *n_members, each member's file offset, compressed size and text size. */
+int rala_hip_bgzf_index_range(const uint8_t* bytes, uint64_t n, uint64_t lo, uint64_t hi, uint64_t block_bytes, uint64_t cap,
+                              uint64_t* n_members, uint64_t* file_off, uint32_t* comp_bytes, uint32_t* text_bytes, uint64_t* begin,
+                              uint64_t* end, int* empty, int* valid);
+/* 1: the n_pieces pieces (in file order) are one chain of members from offset 0 to file_bytes - piece 0 is not empty and begins
+ * at 0, every piece that is not empty begins where the one in front of it ended, the last of them ends at file_bytes.  0: a
+ * gap, a false candidate that started a piece's chain, a cut file - the host reader decides (src/graph.cpp:190-224). */
+int rala_hip_bgzf_pieces_chain(const uint64_t* begin, const uint64_t* end, const int* empty, uint32_t n_pieces, uint64_t file_bytes);
 /* ---- the read file: names, lengths and offsets of every sequence, indexed on the device ---------------------------------
  * Replaces the first sequence pass of Graph::initialize (src/graph.cpp:249-264: bioparser's FASTA / FASTQ parser, a heap
  * Sequence per read of which the name and the length are kept) and lets the second one (src/graph.cpp:527-551) cut the
@@ -336,6 +352,16 @@ uint32_t rala_hip_crc32_chain(const uint32_t* reg, const uint64_t* len, uint64_t
  * option "sensitive_in_device_memory" set.  *irregular != 0: nothing was set, take the host reader. */
 int rala_hip_tokenise_sensitive_paf(rala_hip_ctx* ctx, const char* path, uint64_t lo, uint64_t hi, uint32_t threads,
                                     rala_hip_overlaps* out, uint64_t* n, int* irregular);
+/* The same for part `part` of `parts` of a sensitive file of any kind (src/graph.cpp:901-939), format 0: PAF, 1: MHAP (no name
+ * table needed), no length check in either.  The parts are byte ranges of the FILE, [F / P k + min(k, F % P), ...).  Plain text:
+ * the lines that start in the part's bytes.  BGZF: the part's piece (rala_hip_bgzf_index_range), inflated on the device; a
+ * line belongs to the piece that holds the byte in front of its first byte.  Any other gzip file: parts = 1 and the option
+ * "gzip_on_device" (and "gzip_members"), otherwise *irregular = 8.  piece[0 .. 2] = begin, end, empty of the part (plain text:
+ * its byte range): there is no collective here, the caller of several parts checks rala_hip_bgzf_pieces_chain behind them
+ * and takes the host reader where it fails.  The compressed bytes and the text are released before the call returns - the
+ * context holds piles by then; RALA_HIP_ENOMEM is an answer to fall back on. */
+int rala_hip_tokenise_sensitive(rala_hip_ctx* ctx, const char* path, int format, uint32_t part, uint32_t parts, uint32_t threads,
+                                rala_hip_overlaps* out, uint64_t* n, uint64_t piece[3], int* irregular);
 /* the context's overlap columns, wherever they came from, into host buffers (*n entries each; cols / strand may be NULL to
  * ask for the count alone): a_id, b_id, a_begin, a_end, b_begin, b_end, length */
 int rala_hip_get_overlap_columns(rala_hip_ctx* ctx, uint64_t* n, uint32_t* const cols[7], uint8_t* strand);
@@ -489,6 +515,14 @@ int rala_hip_mg_set_overlaps(rala_hip_mg* mg, const rala_hip_overlaps* slice, ui
  * *length_error_read, *irregular: as rala_hip_set_overlaps_from_paf (the same values on every rank). */
 int rala_hip_mg_set_overlaps_from_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
                                       int* irregular);
+/* An MHAP file the same way (src/graph.cpp:328-382; twelve numeric columns, no name table).
+ * Both take a BGZF file too when the option "bgzf_in_pieces" is set on rala_hip_mg_context(mg) (default 0: a compressed file
+ * is read as the text it is not, and is irregular): rank k takes the piece of its byte range (rala_hip_bgzf_index_range),
+ * begin, end and emptiness of the pieces travel with the ranks' exchange, and a file whose pieces are not one chain
+ * (rala_hip_bgzf_pieces_chain), a member the inflater refuses on any rank (CRC32, ISIZE) or a gzip file that is not BGZF is
+ * *irregular = 8 on every rank, nothing set. */
+int rala_hip_mg_set_overlaps_from_mhap(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
+                                       int* irregular);
 /* the rank's slice as it was set: file position of its record 0, records (the columns: rala_hip_get_overlap_columns on
  * rala_hip_mg_context(mg)) */
 int rala_hip_mg_get_slice(rala_hip_mg* mg, uint64_t* first, uint64_t* n);

@@ -251,6 +251,7 @@ struct rala_hip_ctx {
     // chunks' jobs and text offsets, the 16-bit symbols, the segments' CRCs, the resident text
     bool gzip_on_device = false;
     bool gzip_members = false;                  // option: a file of several members is walked member by member (with gzip_on_device)
+    bool bgzf_in_pieces = false;                // option: a rank of a sharded run takes its piece of a BGZF overlap file (rala_hip_mg_set_overlaps_from_*)
     int64_t gzip_chunk_bytes = 64 << 10;        // option: compressed bytes per chunk
     uint32_t debug_gzip_false_sync = 0;         // tests: every n-th chunk is given a bogus start at its first bit
     rala_hip::DevBuf<uint64_t> d_gzip_starts, d_gzip_off, d_gzip_floor;

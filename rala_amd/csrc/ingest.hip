@@ -189,6 +189,86 @@ int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t l
     return tokenise_range(ctx, X, lo, hi, check_lengths, threads, extra_rows, T, out);
 }
 
+int rala_hip::overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_t part, uint32_t parts, const PartKinds& take, bool check_lengths,
+                                    uint32_t threads, size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t piece[3], bool* bgzf) {
+    if (!ctx || !path || !out || !piece || !bgzf || parts == 0 || part >= parts) return RALA_HIP_EINVAL;
+    *out = PafRange();
+    *bgzf = false;
+    piece[0] = piece[1] = 0;
+    piece[2] = 1;
+    int rc = ingest_ready(ctx, T.mhap);
+    if (rc != RALA_HIP_OK) return rc;
+    INGEST_CHECK(hipSetDevice(ctx->device));
+    OverlapText X;
+    X.path = path;
+    rc = open_regular(ctx, path, X.file, &X.file_n);
+    if (rc != RALA_HIP_OK) return rc;
+    X.text_n = X.file_n;
+    uint8_t head[18] = {0};
+    const ssize_t got = pread(X.file.fd, head, sizeof(head), 0);
+    X.kind = sniff(head, (uint64_t)std::max<ssize_t>(got, 0));
+    const bool taken = (X.kind == kTextBgzf && take.bgzf_pieces) || (X.kind == kTextGzip && take.gzip_whole && parts == 1 && ctx->gzip_on_device);
+    if (X.kind != kTextPlain && !taken) {
+        if (take.refuse_other) { out->flags = 8; return RALA_HIP_OK; }
+        X.kind = kTextPlain;
+    }
+    const uint64_t F = X.file_n;
+    const uint64_t lo = F / parts * part + std::min<uint64_t>(part, F % parts), hi = F / parts * (part + 1) + std::min<uint64_t>(part + 1, F % parts);
+    if (X.kind == kTextPlain) {
+        piece[0] = lo; piece[1] = hi; piece[2] = 0;
+        return tokenise_range(ctx, X, lo, hi, check_lengths, threads, extra_rows, T, out);
+    }
+    // whatever way this ends, the compressed bytes and the inflated text do not stay the context's (it may hold piles by now)
+    struct Release {
+        rala_hip_ctx* ctx;
+        ~Release() {
+            ctx->d_bgzf_comp.release();
+            ctx->d_gzip_sym.release();
+            ctx->d_gzip_text.release();
+            ctx->d_paf_text.release();
+        }
+    } release{ctx};
+    bool valid = true;
+    ctx->inflate_tm = rala_hip_inflate_timings();
+    if (X.kind == kTextGzip) {
+        X.gz.file_n = F;
+        rc = gzip_inflate(ctx, X.file.fd, path, threads, X.gz, &valid);
+        ctx->gzip_tm = X.gz.tm;
+        if (rc != RALA_HIP_OK) return rc;
+        if (!valid) { out->flags = 8; return RALA_HIP_OK; }
+        X.text_n = X.gz.text_n;
+        piece[0] = 0; piece[1] = F; piece[2] = 0;
+        rc = tokenise_range(ctx, X, 0, ~0ull, check_lengths, threads, extra_rows, T, out);
+        if (rc == RALA_HIP_OK) ctx->ingest_tm.ship_ms += X.gz.ship_ms;
+        return rc;
+    }
+    // A BGZF piece.  Its text has no offset in the file's: positions count from the piece's first member, own of them the
+    // piece's own, what follows the next members'.  A line belongs to the piece that holds the byte in front of its first
+    // byte: the line starts at [1, own + 1) - position `own` is the first byte of the text that follows, inflated anyway for
+    // the halo - and, the first piece's alone, the one at 0.
+    *bgzf = true;
+    BgzfPiece P;
+    uint64_t own = 0;
+    rc = bgzf_open_piece(ctx, X.file.fd, F, path, threads, lo, hi, (uint64_t)paf_halo_bytes() + 1, X.bg, &P, &own, &valid);
+    piece[0] = P.begin; piece[1] = P.end; piece[2] = P.empty;
+    if (rc != RALA_HIP_OK) return rc;
+    if (!valid) { out->flags = 8; return RALA_HIP_OK; }
+    X.text_n = X.bg.text_n;
+    const bool nothing = part != 0 && own == 0;
+    rc = tokenise_range(ctx, X, nothing || part == 0 ? 0 : 1, nothing ? 0 : own + 1, check_lengths, threads, extra_rows, T, out);
+    if (rc != RALA_HIP_OK) return rc;
+    ctx->ingest_tm.ship_ms += X.bg.ship_ms;
+    ctx->inflate_tm.inflate_ms = X.bg.inflate_ms;
+    ctx->inflate_tm.compressed_bytes = X.bg.shipped;
+    ctx->inflate_tm.members = X.bg.jobs.size();
+    if (getenv("RALA_HIP_TRACE")) {
+        fprintf(stderr, "[trace] device inflate: part %u of %u, bytes [%lu, %lu) of %lu: %lu BGZF members, %.3f GB compressed shipped (index and "
+                "ship %.1f ms), %.3f GB of text inflated in %.2f ms\n", part, parts, (unsigned long)P.begin, (unsigned long)P.end,
+                (unsigned long)F, (unsigned long)X.bg.jobs.size(), X.bg.shipped / 1e9, X.bg.ship_ms, X.bg.text_n / 1e9, X.bg.inflate_ms);
+    }
+    return RALA_HIP_OK;
+}
+
 extern "C" {
 
 int rala_hip_set_name_table(rala_hip_ctx* ctx, const void* buckets, uint64_t n_buckets, const char* arena, uint64_t arena_bytes) {
@@ -351,6 +431,28 @@ int rala_hip_tokenise_sensitive_paf(rala_hip_ctx* ctx, const char* path, uint64_
     const PafTarget T = paf_target(ctx->d_sens_col, &ctx->d_sens_strand, false);
     PafRange R;
     const int rc = paf_tokenise_range(ctx, path, lo, hi, false, threads, 0, T, &R);
+    if (rc != RALA_HIP_OK) return rc;
+    if (R.flags) { *irregular = (int)R.flags; return RALA_HIP_OK; }
+    out->a_id = ctx->d_sens_col[0].p; out->b_id = ctx->d_sens_col[1].p; out->a_begin = ctx->d_sens_col[2].p; out->a_end = ctx->d_sens_col[3].p;
+    out->b_begin = ctx->d_sens_col[4].p; out->b_end = ctx->d_sens_col[5].p; out->length = ctx->d_sens_col[6].p; out->strand = ctx->d_sens_strand.p;
+    *n = R.n_lines;
+    return RALA_HIP_OK;
+}
+
+// The same for a share of a sensitive file of any kind (overlap_tokenise_part): plain text by byte range, BGZF by piece, any
+// other gzip file whole (parts == 1, option gzip_on_device); PAF or MHAP.  piece[0 .. 2] = begin, end, empty: the caller of
+// several parts joins them (rala_hip_bgzf_pieces_chain).  Only the d_sens_* columns stay.
+int rala_hip_tokenise_sensitive(rala_hip_ctx* ctx, const char* path, int format, uint32_t part, uint32_t parts, uint32_t threads,
+                                rala_hip_overlaps* out, uint64_t* n, uint64_t piece[3], int* irregular) {
+    if (!ctx || !path || !out || !n || !piece || !irregular || (format != 0 && format != 1)) return RALA_HIP_EINVAL;
+    *irregular = 0;
+    *n = 0;
+    const PafTarget T = paf_target(ctx->d_sens_col, &ctx->d_sens_strand, format == 1);
+    PafRange R;
+    PartKinds take;
+    take.bgzf_pieces = take.gzip_whole = take.refuse_other = true;
+    bool bgzf = false;
+    const int rc = overlap_tokenise_part(ctx, path, part, parts, take, false, threads, 0, T, &R, piece, &bgzf);
     if (rc != RALA_HIP_OK) return rc;
     if (R.flags) { *irregular = (int)R.flags; return RALA_HIP_OK; }
     out->a_id = ctx->d_sens_col[0].p; out->b_id = ctx->d_sens_col[1].p; out->a_begin = ctx->d_sens_col[2].p; out->a_end = ctx->d_sens_col[3].p;

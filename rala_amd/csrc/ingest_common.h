@@ -82,12 +82,21 @@ struct BgzfFile {
     std::vector<BgzfMember> jobs;       // the members with text, in file order
     uint64_t n_members = 0;
     bool resident = false;              // all compressed bytes in ctx->d_bgzf_comp
+    uint64_t comp_origin = 0;           // resident: the file offset of ctx->d_bgzf_comp's first byte (a piece: its range's)
     float ship_ms = 0, inflate_ms = 0;
     uint64_t shipped = 0;
     uint32_t n_readers = 0;
 };
 // index the open file of file_n bytes (and ship it when it fits); *valid = false: not a chain of members the host reader takes
 int bgzf_open(rala_hip_ctx* ctx, int fd, uint64_t file_n, const char* path, uint32_t threads, uint64_t window, BgzfFile& f, bool* valid);
+// A PIECE of the file instead (ingest_formats.h: the members whose header begins in bytes [lo, hi), bgzf_walk_range), indexed
+// and shipped without reading anything in front of lo: the range goes to ctx->d_bgzf_comp through the readers, who scan it;
+// what the piece's last member and the members behind it hold of the next `follow_text` bytes of text (the first byte behind
+// the piece's own text decides who owns the line there, the tokeniser's halo follows) is read header by header and copied
+// behind it.  f then describes the piece alone: resident, text offsets from its first member, text_n = own_text + what follows.
+// *valid = false: the chain broke, in the piece or in what follows it (piece->begin / end say where it stood).
+int bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n, const char* path, uint32_t threads, uint64_t lo, uint64_t hi,
+                    uint64_t follow_text, BgzfFile& f, BgzfPiece* piece, uint64_t* own_text, bool* valid);
 // The text [lo, lo + n_avail) of a BGZF file (and the byte in front of it) in device memory: the members that cover it
 // shipped (unless the file is resident) and inflated into ctx->d_paf_text, `pad` in the bytes behind the text up to cap.
 // meanwhile runs while the readers work (false: `room` could not be made).  out->flag != 0: the inflater refused a member

@@ -120,6 +120,109 @@ inline bool bgzf_index_bytes(const uint8_t* bytes, uint64_t n, uint64_t block_by
     return bgzf_walk(cand, n, le32(bytes + n - 4), members);
 }
 
+// ---- BGZF: a file in pieces by compressed byte range (a rank's share of a sharded run, a context's share of the -s file) ----
+// Piece [lo, hi) of the file holds the members whose header BEGINS in it.  begin: its first member's offset; end: where its
+// chain arrived (>= hi); empty: no header begins in the range.
+struct BgzfPiece {
+    uint64_t begin = 0, end = 0;
+    uint32_t empty = 1;
+};
+
+// The chain of a piece's members through the candidates that begin in [lo, hi) (in file order; candidates behind hi are not
+// looked at): from the FIRST candidate of the range until the chain reaches an offset >= hi, where there must be a candidate
+// - next(o, &c): the candidate at offset o < file_n, false: none - or the file's end (tail: the file's last 4 bytes).  The
+// members' text offsets count from the piece's first member.  false: what bgzf_walk refuses - and a piece never tries to be
+// cleverer than that: a false candidate that starts the chain (a header-shaped string inside the member in front) is not
+// stepped over, the pieces then do not join (bgzf_pieces_chain) and the host reader decides.
+template <class Next>
+bool bgzf_walk_range(const std::vector<std::vector<BgzfCand>>& blocks, uint64_t lo, uint64_t hi, uint64_t file_n, uint32_t tail,
+                     const Next& next, std::vector<BgzfMember>& members, BgzfPiece* piece) {
+    members.clear();
+    piece->begin = piece->end = lo;
+    piece->empty = 1;
+    size_t b = 0, i = 0;
+    auto seek = [&](uint64_t o) {
+        while (b < blocks.size() && (i >= blocks[b].size() || blocks[b][i].pos < o)) {
+            if (i >= blocks[b].size()) { ++b; i = 0; } else { ++i; }
+        }
+        return b < blocks.size();
+    };
+    if (!seek(lo) || blocks[b][i].pos >= hi) return true;
+    uint64_t o = blocks[b][i].pos;
+    piece->begin = piece->end = o;
+    piece->empty = 0;
+    while (o < hi) {
+        piece->end = o;
+        if (!seek(o)) return false;
+        const BgzfCand& c = blocks[b][i];
+        if (c.pos != o || c.bsize == 0 || o + c.bsize > file_n) return false;
+        if (!members.empty()) members.back().isize = c.prev_isize;
+        BgzfMember m;
+        m.off = o; m.bsize = c.bsize; m.hdr = c.hdr; m.isize = 0; m.text_off = 0;
+        members.push_back(m);
+        o += c.bsize;
+    }
+    piece->end = o;
+    if (o == file_n) {
+        members.back().isize = tail;
+    } else {
+        BgzfCand c;
+        if (!next(o, &c)) return false;
+        members.back().isize = c.prev_isize;
+    }
+    uint64_t t = 0;
+    for (BgzfMember& m : members) {
+        if (m.isize > 65536) return false;
+        m.text_off = t;
+        t += m.isize;
+    }
+    return true;
+}
+
+// Do the pieces of a file of file_n bytes, in order, form one chain from offset 0 to its end?  Piece 0 begins at 0, every
+// non-empty piece begins where the non-empty one in front of it ended, the last one ends at the file's end.
+inline bool bgzf_pieces_chain(const BgzfPiece* pieces, size_t n, uint64_t file_n) {
+    if (!n || pieces[0].empty || pieces[0].begin != 0) return false;
+    uint64_t at = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (pieces[k].empty) continue;
+        if (pieces[k].begin != at || pieces[k].end <= at) return false;
+        at = pieces[k].end;
+    }
+    return at == file_n;
+}
+
+// the candidate at offset o of a file in memory, if there is one
+inline bool bgzf_cand_at(const uint8_t* bytes, uint64_t n, uint64_t o, BgzfCand* c) {
+    if (o >= n) return false;
+    std::vector<BgzfCand> v;
+    bgzf_scan(bytes + o, 1, o, n, [&](uint64_t q) { return bytes[q]; }, v);
+    if (v.empty()) return false;
+    *c = v[0];
+    return true;
+}
+
+// piece [lo, hi) of a file in memory, scanned in blocks of block_bytes from lo (the piece at offset 0 wants the first header
+// to be what the host reader's is_bgzf recognises, as bgzf_index_bytes does)
+inline bool bgzf_index_range_bytes(const uint8_t* bytes, uint64_t n, uint64_t lo, uint64_t hi, uint64_t block_bytes,
+                                   std::vector<BgzfMember>& members, BgzfPiece* piece) {
+    hi = std::min(hi, n);
+    lo = std::min(lo, hi);
+    members.clear();
+    piece->begin = piece->end = lo;
+    piece->empty = 1;
+    if (lo == 0 && hi > 0 && !bgzf_head(bytes, n)) return false;
+    const uint64_t n_blocks = (hi - lo + block_bytes - 1) / block_bytes;
+    std::vector<std::vector<BgzfCand>> cand(n_blocks);
+    auto at = [&](uint64_t q) { return bytes[q]; };
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        const uint64_t off = lo + b * block_bytes;
+        bgzf_scan(bytes + off, std::min(block_bytes, hi - off), off, n, at, cand[b]);
+    }
+    return bgzf_walk_range(cand, lo, hi, n, n >= 4 ? le32(bytes + n - 4) : 0,
+                           [&](uint64_t o, BgzfCand* c) { return bgzf_cand_at(bytes, n, o, c); }, members, piece);
+}
+
 // ---- a single-member gzip file (gzip, pigz, Python's gzip) ---------------------------------------------------------
 // The header of a gzip member (RFC 1952 2.3) in the first n bytes of a file: where its deflate bytes begin.  false: not a
 // header inflate would take (magic, CM != 8, reserved flag bits) or one that does not end within the n bytes.

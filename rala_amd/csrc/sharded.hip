@@ -37,6 +37,7 @@
 
 #include "comm.h"
 #include "context.h"
+#include "ingest_formats.h"
 #include "stages.h"
 
 using namespace rala_hip;
@@ -540,24 +541,39 @@ int rala_hip_mg_slice_cuts(const uint32_t* a_id, const uint32_t* b_id, uint64_t 
 // records in front of the first resolved one) travel to the rank that holds the run's start, column by column.
 // *length_error_read: the first record in file order whose length differs from its sequence's (check_lengths); -1: none.
 // *irregular != 0 (the same on every rank): not a file of 12-column records - nothing was set, take the host reader.
+//
+// With the option "bgzf_in_pieces" set on the slice context (rala_hip_mg_context) a BGZF file is taken too, in PIECES: rank k
+// holds the members whose header begins in its byte range (found without a look at the bytes in front of it, inflated on its
+// GPU) and the lines whose first byte follows a byte of their text; begin, end and emptiness of every rank's piece travel with
+// the same exchange, and every rank checks that the pieces are one chain from byte 0 to the file's end.  A file where they
+// are not, a member the inflater refuses on any rank, any other gzip file: *irregular = 8 on every rank.
 namespace {
-int ingest_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular);
-}
-int rala_hip_mg_set_overlaps_from_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
-                                      int* irregular) {
+int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular);
+int set_overlaps_from_text(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read,
+                           int* irregular) {
     if (!mg || !path || !length_error_read || !irregular) return RALA_HIP_EINVAL;
     *length_error_read = -1;
     *irregular = 0;
     if (!mg->comm) return mg_fail(mg, RALA_HIP_EINVAL, "the rank has not joined its group (rala_hip_mg_join)");
     if (!mg->have_reads) return mg_fail(mg, RALA_HIP_EINVAL, "set the reads first");
     mg->verdict_shared = false;
-    const int rc = ingest_paf(mg, path, check_lengths, threads, length_error_read, irregular);
+    const int rc = ingest_paf(mg, path, mhap, check_lengths, threads, length_error_read, irregular);
     // (a failure the others do not know of: they must not wait for this rank in the next collective)
     if (rc != RALA_HIP_OK && !mg->verdict_shared) mg->comm->abort();
     return rc;
 }
+}
+int rala_hip_mg_set_overlaps_from_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
+                                      int* irregular) {
+    return set_overlaps_from_text(mg, path, false, check_lengths, threads, length_error_read, irregular);
+}
+// an MHAP file the same way: twelve numeric columns, no names to look up (no name table needed)
+int rala_hip_mg_set_overlaps_from_mhap(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
+                                       int* irregular) {
+    return set_overlaps_from_text(mg, path, true, check_lengths, threads, length_error_read, irregular);
+}
 namespace {
-int ingest_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular) {
+int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular) {
     rala_hip_ctx* cs = mg->cs;
     const uint32_t P = mg->world, me = mg->rank;
     constexpr uint64_t kNone = 0xFFFFFFFFull;
@@ -568,8 +584,11 @@ int ingest_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t th
     PafTarget T;
     for (int k = 0; k < 7; ++k) T.col[k] = &cs->d_paf_col[k];
     T.strand = &cs->d_paf_strand;
+    T.mhap = mhap;
     PafRange R;
     uint64_t file_n = 0;
+    uint64_t piece[3] = {0, 0, 1};
+    bool in_pieces = false;
     if (rc == RALA_HIP_OK) {
         struct stat st;
         if (stat(path, &st) != 0) rc = mg_fail(mg, RALA_HIP_EINVAL, std::string("cannot open ") + path);
@@ -579,8 +598,10 @@ int ingest_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t th
     cs->inputs_set = false;
     cs->n_ovl = 0;
     if (rc == RALA_HIP_OK) {
-        const uint64_t lo = file_n / P * me + std::min<uint64_t>(me, file_n % P), hi = file_n / P * (me + 1) + std::min<uint64_t>(me + 1, file_n % P);
-        rc = from_ctx(mg, cs, paf_tokenise_range(cs, path, lo, hi, check_lengths != 0, threads, 1u << 16, T, &R), "tokenise");
+        // (a plain file: bytes [n me / P, n (me + 1) / P); a compressed one is text like any other unless the option says otherwise)
+        PartKinds take;
+        take.bgzf_pieces = take.refuse_other = cs->bgzf_in_pieces;
+        rc = from_ctx(mg, cs, overlap_tokenise_part(cs, path, me, P, take, check_lengths != 0, threads, 1u << 16, T, &R, piece, &in_pieces), "tokenise");
     }
     // what the cuts need of this rank's rows
     uint32_t ends[5] = {kNoRow, 0, 0, kNoRow, kNoRow};
@@ -603,14 +624,27 @@ int ingest_paf(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t th
         if (e != hipSuccess) rc = mg_fail(mg, RALA_HIP_EDEVICE, std::string("run ends: ") + hipGetErrorString(e));
     }
     // one host exchange: {rows, first resolved row, end of the first run, query of the first / last resolved row, tokeniser's
-    // flags, first length error}
-    const uint64_t mine[7] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad};
+    // flags, first length error; begin, end, emptiness of its piece of a BGZF file (bit 1 of the last: the file was taken so)}
+    const uint64_t mine[10] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad,
+                               piece[0], piece[1], piece[2] | (in_pieces ? 2u : 0u)};
     std::vector<uint64_t> all;
-    rc = agree_with(mg, rc, "device ingest", 0, mine, 7, all);
+    rc = agree_with(mg, rc, "device ingest", 0, mine, 10, all);
     if (rc != RALA_HIP_OK) return rc;
-    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 8 + 1 + f]; };
+    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 11 + 1 + f]; };
     uint32_t flags = 0;
     for (uint32_t p = 0; p < P; ++p) flags |= (uint32_t)of(p, 5);
+    // the pieces of a BGZF file must be one chain from byte 0 to the file's end: the same verdict from the same words on every rank
+    bool any_pieces = false;
+    for (uint32_t p = 0; p < P; ++p) any_pieces = any_pieces || (of(p, 9) & 2) != 0;
+    if (any_pieces && !flags) {
+        std::vector<ingest::BgzfPiece> pieces(P);
+        bool all_pieces = true;
+        for (uint32_t p = 0; p < P; ++p) {
+            pieces[p].begin = of(p, 7); pieces[p].end = of(p, 8); pieces[p].empty = (uint32_t)(of(p, 9) & 1);
+            all_pieces = all_pieces && (of(p, 9) & 2) != 0;
+        }
+        if (!all_pieces || !ingest::bgzf_pieces_chain(pieces.data(), P, file_n)) flags = 8;
+    }
     if (flags) { *irregular = (int)flags; return RALA_HIP_OK; }
     for (uint32_t p = 0; p < P; ++p) {
         if (of(p, 6) != ~0ull) { *length_error_read = (int64_t)(of(p, 6) & 0xFFFFFFFFull); return RALA_HIP_OK; }   // (file order: the lowest rank's)

@@ -52,6 +52,21 @@ struct PafRange {
 int paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t lo, uint64_t hi, bool check_lengths, uint32_t threads,
                        size_t extra_rows, const PafTarget& T, PafRange* out);
 
+// Part `part` of `parts` of an overlap file of whatever kind, by BYTES OF THE FILE (part k covers [F / P k + min(k, F % P), ...),
+// the split of the sharded ingest): a plain file gives the lines that start in the part's bytes, exactly as
+// paf_tokenise_range; a BGZF file (take.bgzf_pieces) the part's piece - the members whose header begins in its bytes,
+// indexed, shipped and inflated without a look at anything in front of them, the lines whose first byte follows a byte of
+// the piece's text (the line at text offset 0: part 0's); any other gzip file (take.gzip_whole, parts == 1, the context's
+// option gzip_on_device) its whole text.  A compressed file that is not taken so: flags = 8 with take.refuse_other,
+// otherwise read as the text it is not (the tokeniser's flags say so).  piece[0 .. 2] = begin, end, empty of the part
+// (ingest_formats.h: BgzfPiece; a plain file: its byte range): the caller checks that the pieces join (bgzf_pieces_chain).
+// The compressed bytes and the text are released before it returns.  *bgzf: the file was taken in pieces.
+struct PartKinds {
+    bool bgzf_pieces = false, gzip_whole = false, refuse_other = false;
+};
+int overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_t part, uint32_t parts, const PartKinds& take, bool check_lengths,
+                          uint32_t threads, size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t piece[3], bool* bgzf);
+
 // checksums of the rows cl holds (verify_kernels.hip) under the regions / liveness given per row (host arrays, cl->n_reads entries)
 int pile_row_digests(rala_hip_ctx* cl, const uint32_t* begin, const uint32_t* end, const uint8_t* alive, uint64_t* fnv, uint64_t* inside,
                      uint64_t* outside);

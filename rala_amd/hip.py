@@ -32,6 +32,7 @@ SYMBOLS = (
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
     "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_bgzf_index_range", "rala_hip_bgzf_pieces_chain", "rala_hip_tokenise_sensitive", "rala_hip_mg_set_overlaps_from_mhap",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
     "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",

@@ -106,7 +106,7 @@ extern "C" int rala_e2e_from_paf(const char* paf_path, const uint32_t* read_len,
 
 // The same over several ranks (threads of this process, one per device ordinal in `devices`; transport: 0 RCCL, 1 the
 // in-process one, which also lets ranks share a device): every rank ships and tokenises its own byte range of the file on
-// its own GPU (rala_hip_mg_set_overlaps_from_paf), then the sharded step.  ms_ingest: name tables + ship + tokenise + the
+// its own GPU (rala_hip_mg_set_overlaps_from_paf; with io::device_compressed_wanted() its piece of a BGZF file), then the sharded step.  ms_ingest: name tables + ship + tokenise + the
 // cuts' exchange (the slowest rank); ms_device: the step (first call).
 extern "C" int rala_e2e_from_paf_ranks(const char* paf_path, const uint32_t* read_len, uint64_t n_reads, uint32_t num_threads, uint32_t world,
                                        const int* devices, int transport, double* ms_ingest, double* ms_device, uint64_t* n_overlaps,
@@ -153,8 +153,16 @@ extern "C" int rala_e2e_from_paf_ranks(const char* paf_path, const uint32_t* rea
     if (bad_rc == RALA_HIP_OK) {
         on_every_rank([&](uint32_t k) {
             int r = rala_hip_set_name_table(rala_hip_mg_context(ranks[k]), table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
-            const int r2 = rala_hip_mg_set_overlaps_from_paf(ranks[k], r == RALA_HIP_OK ? paf_path : "", 1, std::max(1u, num_threads / world), &bad[k],
-                                                             &irregular[k]);
+            // (io::device_compressed_wanted(): a BGZF file in pieces, a .mhap file as MHAP - as Graph::initialize does)
+            const std::string path(paf_path);
+            const bool mhap = rala::io::has_suffix(path, ".mhap") || rala::io::has_suffix(path, ".mhap.gz");
+            if (r == RALA_HIP_OK && rala::io::device_compressed_wanted() && rala::io::has_suffix(path, ".gz")) {
+                r = rala_hip_set_option(rala_hip_mg_context(ranks[k]), "bgzf_in_pieces", 1);
+            }
+            const char* const p = r == RALA_HIP_OK ? paf_path : "";
+            const int r2 = mhap && rala::io::device_compressed_wanted()
+                               ? rala_hip_mg_set_overlaps_from_mhap(ranks[k], p, 1, std::max(1u, num_threads / world), &bad[k], &irregular[k])
+                               : rala_hip_mg_set_overlaps_from_paf(ranks[k], p, 1, std::max(1u, num_threads / world), &bad[k], &irregular[k]);
             if (r == RALA_HIP_OK) r = r2;
             uint64_t first = 0;
             if (r == RALA_HIP_OK && !irregular[k] && bad[k] < 0) r = rala_hip_mg_get_slice(ranks[k], &first, &rows[k]);

@@ -342,7 +342,12 @@ void Graph::initialize() {
     // several GPUs take the host reader for every .gz file.
     const bool gz = io::has_suffix(overlaps_path_, ".paf.gz") || io::has_suffix(overlaps_path_, ".mhap.gz");
     const bool mhap_text = io::has_suffix(overlaps_path_, ".mhap") || io::has_suffix(overlaps_path_, ".mhap.gz");
-    const bool device_ingest = (io::has_suffix(overlaps_path_, ".paf") || ((mhap_text || gz) && ranks_.empty())) &&
+    // ... unless io::device_compressed_wanted() (RALA_DEVICE_COMPRESSED=1): then the ranks take a plain .mhap as they take a
+    // .paf, and a .gz file that is BGZF in pieces - every rank the members whose header begins in its byte range (option
+    // bgzf_in_pieces; a file whose pieces do not join, or any other gzip file, is irregular there and the host reader decides)
+    const bool ranks_compressed = !ranks_.empty() && io::device_compressed_wanted() &&
+                                  (gz ? io::sniff_compression(overlaps_path_) == 1 : mhap_text);
+    const bool device_ingest = (io::has_suffix(overlaps_path_, ".paf") || ((mhap_text || gz) && ranks_.empty()) || ranks_compressed) &&
                                !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
     // A single-member gzip file (gzip, pigz, `minimap2 | gzip`) is inflated on the device too where io::device_gzip_wanted()
     // says so (option gzip_on_device: speculative decoding); what that cannot prove is flag 8 like
@@ -398,8 +403,10 @@ void Graph::initialize() {
                                                 name_table_.arena().data(), name_table_.arena().size());
                 }
                 // (collective: a rank that failed above still calls it, with nothing to read, so that nobody waits for it)
-                const int r2 = rala_hip_mg_set_overlaps_from_paf(mg, r == RALA_HIP_OK ? overlaps_path_.c_str() : "", 1,
-                                                                 std::max(1u, num_threads_ / P), &bad[k], &irregular[k]);
+                if (r == RALA_HIP_OK && ranks_compressed && gz) r = rala_hip_set_option(rala_hip_mg_context(mg), "bgzf_in_pieces", 1);
+                const char* const path = r == RALA_HIP_OK ? overlaps_path_.c_str() : "";
+                const int r2 = mhap_text ? rala_hip_mg_set_overlaps_from_mhap(mg, path, 1, std::max(1u, num_threads_ / P), &bad[k], &irregular[k])
+                                         : rala_hip_mg_set_overlaps_from_paf(mg, path, 1, std::max(1u, num_threads_ / P), &bad[k], &irregular[k]);
                 rc[k] = r != RALA_HIP_OK ? r : r2;
             });
         }
@@ -498,10 +505,18 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         }
         // an uncompressed PAF file is tokenised on the device(s) - no length check, Overlap::transmute_ has none (round 5;
         // RALA_DEVICE_INGEST=0, or a file the tokeniser cannot take: the host reader)
-        const bool device_ingest = io::has_suffix(sensitive_overlaps_path, ".paf") && name_table_.n_buckets() != 0 &&
+        // With io::device_compressed_wanted() a .mhap and a .paf.gz / .mhap.gz that is BGZF as well (rala_hip_tokenise_sensitive:
+        // every context its piece of the file; whether the pieces are one chain is checked behind the join), any other gzip file
+        // on one context where io::device_gzip_wanted().
+        const uint32_t P = ranks_.empty() ? 1u : (uint32_t)ranks_.size();
+        const bool s_gz = io::has_suffix(sensitive_overlaps_path, ".gz");
+        const bool s_mhap = io::has_suffix(sensitive_overlaps_path, ".mhap") || io::has_suffix(sensitive_overlaps_path, ".mhap.gz");
+        const int s_kind = s_gz && io::device_compressed_wanted() ? io::sniff_compression(sensitive_overlaps_path) : 0;
+        const bool s_compressed = io::device_compressed_wanted() &&
+                                  (s_gz ? s_kind == 1 || (s_kind == 2 && P == 1 && io::device_gzip_wanted()) : s_mhap);
+        const bool device_ingest = (io::has_suffix(sensitive_overlaps_path, ".paf") || s_compressed) && name_table_.n_buckets() != 0 &&
                                    !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
         if (device_ingest) {
-            const uint32_t P = ranks_.empty() ? 1u : (uint32_t)ranks_.size();
             uint64_t file_bytes = 0;
             {
                 std::ifstream f(sensitive_overlaps_path, std::ios::binary | std::ios::ate);
@@ -510,6 +525,7 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
             device_shares_.assign(P, rala_hip_overlaps());
             device_share_n_.assign(P, 0);
             std::vector<int> rc(P, RALA_HIP_OK), irregular(P, 0);
+            std::vector<uint64_t> pieces(3 * (size_t)P, 0);
             std::vector<std::thread> th;
             for (uint32_t k = 0; k < P; ++k) {
                 th.emplace_back([&, k]() {
@@ -517,7 +533,16 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
                     // (a run that took the host reader for the primary overlaps has set no name table yet)
                     rc[k] = rala_hip_set_name_table(c, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
                                                     name_table_.arena().size());
-                    if (rc[k] == RALA_HIP_OK) {
+                    if (rc[k] == RALA_HIP_OK && s_compressed) {
+                        if (s_kind == 2) {
+                            rc[k] = rala_hip_set_option(c, "gzip_on_device", 1);
+                            if (rc[k] == RALA_HIP_OK && io::device_gzip_members_wanted()) rc[k] = rala_hip_set_option(c, "gzip_members", 1);
+                        }
+                        if (rc[k] == RALA_HIP_OK) {
+                            rc[k] = rala_hip_tokenise_sensitive(c, sensitive_overlaps_path.c_str(), s_mhap ? 1 : 0, k, P, std::max(1u, num_threads_ / P),
+                                                                &device_shares_[k], &device_share_n_[k], &pieces[3 * k], &irregular[k]);
+                        }
+                    } else if (rc[k] == RALA_HIP_OK) {
                         rc[k] = rala_hip_tokenise_sensitive_paf(c, sensitive_overlaps_path.c_str(), file_bytes / P * k + std::min<uint64_t>(k, file_bytes % P),
                                                                 file_bytes / P * (k + 1) + std::min<uint64_t>(k + 1, file_bytes % P),
                                                                 std::max(1u, num_threads_ / P), &device_shares_[k], &device_share_n_[k], &irregular[k]);
@@ -527,6 +552,13 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
             for (auto& t : th) t.join();
             sens_on_device_ = true;
             for (uint32_t k = 0; k < P; ++k) sens_on_device_ = sens_on_device_ && rc[k] == RALA_HIP_OK && !irregular[k];
+            if (sens_on_device_ && s_kind == 1) {
+                // (no collective in there: whether the contexts' pieces are the whole file is known only now)
+                std::vector<uint64_t> begin(P), end(P);
+                std::vector<int> empty(P);
+                for (uint32_t k = 0; k < P; ++k) { begin[k] = pieces[3 * k]; end[k] = pieces[3 * k + 1]; empty[k] = (int)pieces[3 * k + 2]; }
+                sens_on_device_ = rala_hip_bgzf_pieces_chain(begin.data(), end.data(), empty.data(), P, file_bytes) == 1;
+            }
             if (sens_on_device_) {
                 for (uint32_t k = 0; k < P; ++k) {
                     rala_hip_ctx* c = ranks_.empty() ? ctx_ : rala_hip_mg_context(ranks_[k]);

@@ -297,6 +297,120 @@ void* hp_paf_device_ranks(const char* path, const char* names, const uint32_t* r
     rala_hip_mg_local_group_destroy(group);
     return out;
 }
+// hp_paf_device_ranks for a file of either format (mhap != 0: MHAP, no names) and any kind, with options of every rank's slice
+// context set first (rala_hip_set_option on rala_hip_mg_context: "bgzf_in_pieces", "gzip_on_device", ...) -
+// tests/test_gpu_ranks_compressed.py, tools/ranks_compressed_bench.py.  before != null: the same group ingests that file
+// first, whatever comes of it (hp_paf_device_before: its irregular flags and length error) - does a refusal leave the group
+// usable?  sensitive != 0: rank k's share of a sensitive file instead (rala_hip_tokenise_sensitive, part k of world; no
+// collective) - the pieces joined behind the threads as a caller has to (rala_hip_bgzf_pieces_chain; irregular |= 8 where
+// they are not one chain); pieces[3 k ..] = begin, end, empty of rank k's share.
+void* hp_text_device_ranks(const char* path, const char* before, const char* names, const uint32_t* read_len, uint64_t n_reads, int check_lengths,
+                           uint32_t threads, uint32_t world, int mhap, int sensitive, const char* const* keys, const int64_t* values,
+                           uint32_t n_options, uint64_t* slices, uint64_t* pieces) {
+    std::vector<std::string> nm;
+    const char* p = names;
+    for (uint64_t i = 0; i < n_reads && !mhap; ++i) {
+        const char* e = strchr(p, '\n');
+        nm.emplace_back(p, e ? (size_t)(e - p) : strlen(p));
+        p = e ? e + 1 : p + strlen(p);
+    }
+    rala::io::NameTable table;
+    if (!mhap) table.build(nm);
+    auto* out = new PafOnDevice();
+    void* group = nullptr;
+    out->rc = rala_hip_mg_local_group_create(world, &group);
+    if (out->rc != RALA_HIP_OK) return out;
+    std::vector<rala_hip_mg*> ranks(world, nullptr);
+    for (uint32_t k = 0; k < world && out->rc == RALA_HIP_OK; ++k) out->rc = rala_hip_mg_create_contexts(0, k, world, &ranks[k]);
+    std::vector<int> rc(world, RALA_HIP_OK), irregular(world, 0), before_irregular(world, 0);
+    std::vector<int64_t> bad(world, -1), before_bad(world, -1);
+    std::vector<std::vector<uint32_t>> col[7];
+    for (auto& c : col) c.resize(world);
+    std::vector<std::vector<uint8_t>> strand(world);
+    std::vector<uint64_t> share(3 * (size_t)world, 0);
+    if (out->rc == RALA_HIP_OK) {
+        std::vector<std::thread> th;
+        for (uint32_t k = 0; k < world; ++k) {
+            th.emplace_back([&, k]() {
+                rala_hip_mg* mg = ranks[k];
+                int r = rala_hip_mg_join(mg, RALA_HIP_COMM_LOCAL, group);
+                if (r == RALA_HIP_OK) r = rala_hip_mg_set_reads(mg, read_len, n_reads);
+                rala_hip_ctx* cs = rala_hip_mg_context(mg);
+                for (uint32_t o = 0; o < n_options && r == RALA_HIP_OK; ++o) r = rala_hip_set_option(cs, keys[o], values[o]);
+                if (r == RALA_HIP_OK && !mhap) r = rala_hip_set_name_table(cs, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
+                uint64_t first = 0, n = 0;
+                std::vector<uint32_t> got[7];
+                std::vector<uint8_t> got_strand;
+                auto read_back = [&](uint64_t rows) {
+                    uint32_t* dst[7];
+                    for (int c = 0; c < 7; ++c) { got[c].resize(rows); dst[c] = got[c].data(); }
+                    got_strand.resize(rows);
+                    uint64_t n2 = 0;
+                    const int r2 = rala_hip_get_overlap_columns(cs, &n2, dst, got_strand.data());
+                    return r2 == RALA_HIP_OK && n2 != rows ? RALA_HIP_EDEVICE : r2;
+                };
+                if (sensitive) {
+                    rala_hip_overlaps dev = {};
+                    if (r == RALA_HIP_OK && before) {
+                        r = rala_hip_tokenise_sensitive(cs, before, mhap ? 1 : 0, k, world, threads, &dev, &n, &share[3 * k], &before_irregular[k]);
+                    }
+                    if (r == RALA_HIP_OK) r = rala_hip_tokenise_sensitive(cs, path, mhap ? 1 : 0, k, world, threads, &dev, &n, &share[3 * k], &irregular[k]);
+                    // (read back through the context: the columns are plain device memory, adopted as its overlaps)
+                    if (r == RALA_HIP_OK && !irregular[k]) r = rala_hip_set_overlaps(cs, &dev, n, RALA_HIP_MEM_DEVICE);
+                    if (r == RALA_HIP_OK && !irregular[k]) r = read_back(n);
+                } else {
+                    auto ingest = [&](const char* file, int64_t* b, int* irr) {
+                        return mhap ? rala_hip_mg_set_overlaps_from_mhap(mg, file, check_lengths, threads, b, irr)
+                                    : rala_hip_mg_set_overlaps_from_paf(mg, file, check_lengths, threads, b, irr);
+                    };
+                    if (r == RALA_HIP_OK && before) {
+                        r = ingest(before, &before_bad[k], &before_irregular[k]);
+                        // (nothing was set by a refusal)
+                        if (r == RALA_HIP_OK && before_irregular[k] && rala_hip_mg_get_slice(mg, &first, &n) == RALA_HIP_OK) r = RALA_HIP_EDEVICE;
+                        first = n = 0;
+                    }
+                    if (r == RALA_HIP_OK) r = ingest(path, &bad[k], &irregular[k]);
+                    if (r == RALA_HIP_OK && !irregular[k] && bad[k] < 0) {
+                        r = rala_hip_mg_get_slice(mg, &first, &n);
+                        if (r == RALA_HIP_OK) r = read_back(n);
+                    } else if (r == RALA_HIP_OK && rala_hip_mg_get_slice(mg, &first, &n) == RALA_HIP_OK) {
+                        r = RALA_HIP_EDEVICE;               // (a refusal that left a slice behind)
+                    }
+                }
+                slices[2 * k] = first; slices[2 * k + 1] = n;
+                for (int c = 0; c < 7; ++c) col[c][k] = std::move(got[c]);
+                strand[k] = std::move(got_strand);
+                rc[k] = r;
+            });
+        }
+        for (auto& t : th) t.join();
+    }
+    for (uint32_t k = 0; k < world; ++k) {
+        if (rc[k] != RALA_HIP_OK && out->rc == RALA_HIP_OK) { out->rc = rc[k]; fprintf(stderr, "[hp_text_device_ranks] rank %u: %s\n", k, rala_hip_mg_last_error(ranks[k])); }
+        out->irregular |= irregular[k];
+        out->before_irregular |= before_irregular[k];
+        if (bad[k] >= 0 && out->bad < 0) out->bad = bad[k];
+        if (before_bad[k] >= 0 && out->before_bad < 0) out->before_bad = before_bad[k];
+        // (every rank the same verdict: one that differs shows as a value no rank gave)
+        if (!sensitive && (irregular[k] != irregular[0] || before_irregular[k] != before_irregular[0])) out->irregular |= 1 << 20;
+        for (int c = 0; c < 7; ++c) out->col[c].insert(out->col[c].end(), col[c][k].begin(), col[c][k].end());
+        out->strand.insert(out->strand.end(), strand[k].begin(), strand[k].end());
+    }
+    if (sensitive && out->rc == RALA_HIP_OK && !out->irregular && rala::io::sniff_compression(path) == 1) {
+        std::vector<uint64_t> begin(world), end(world);
+        std::vector<int> empty(world);
+        for (uint32_t k = 0; k < world; ++k) { begin[k] = share[3 * k]; end[k] = share[3 * k + 1]; empty[k] = (int)share[3 * k + 2]; }
+        uint64_t file_bytes = 0;
+        FILE* f = fopen(path, "rb");
+        if (f) { fseek(f, 0, SEEK_END); file_bytes = (uint64_t)ftell(f); fclose(f); }
+        if (!rala_hip_bgzf_pieces_chain(begin.data(), end.data(), empty.data(), world, file_bytes)) out->irregular |= 8;
+    }
+    for (uint32_t k = 0; pieces && k < 3 * world; ++k) pieces[k] = share[k];
+    out->n = out->strand.size();
+    for (rala_hip_mg* r : ranks) if (r) rala_hip_mg_destroy(r);
+    rala_hip_mg_local_group_destroy(group);
+    return out;
+}
 // info[0 .. 5] = return code, irregular flags, first read with a length mismatch (-1 none), records, ship us, tokenise us
 void hp_paf_device_info(void* h, int64_t* info) {
     const auto* o = (const PafOnDevice*)h;

@@ -77,6 +77,21 @@ bool device_gzip_members_wanted() {
     return e ? atoi(e) == 2 : false;
 }
 
+bool device_compressed_wanted() {
+    const char* e = getenv("RALA_DEVICE_COMPRESSED");
+    return e ? atoi(e) != 0 : false;
+}
+
+int sniff_compression(const std::string& path) {
+    unsigned char h[18] = {0};
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return 0;
+    const size_t got = fread(h, 1, sizeof(h), f);
+    fclose(f);
+    if (got < 2 || h[0] != 0x1f || h[1] != 0x8b) return 0;
+    return got == 18 && h[2] == 8 && (h[3] & 4) != 0 && h[10] == 6 && h[11] == 0 && h[12] == 'B' && h[13] == 'C' && h[14] == 2 && h[15] == 0 ? 1 : 2;
+}
+
 bool pile_rows_wanted() {
     const char* e = getenv("RALA_PILE_ROWS");
     return e ? atoi(e) != 0 : true;

@@ -41,6 +41,15 @@ bool device_gzip_wanted();
  * option "gzip_members") instead of handed to the host reader?  RALA_DEVICE_GZIP=2 says so (and says device_gzip_wanted() as well) */
 bool device_gzip_members_wanted();
 
+/*! @brief do the compressed and MHAP files that still go to the host readers take the device ingest: a BGZF .paf.gz / .mhap.gz
+ * and a plain .mhap in a run on several GPUs (every rank its piece of the file, rala_hip option "bgzf_in_pieces"), a .paf.gz,
+ * .mhap or .mhap.gz given with -s (rala_hip_tokenise_sensitive)?  RALA_DEVICE_COMPRESSED=1 says so; without it: no - unmeasured,
+ * see README.md, "Compressed overlap files" */
+bool device_compressed_wanted();
+/*! @brief what a file is by its first 18 bytes: 0 text (or unreadable), 1 BGZF (what the host reader's BgzfSource recognises),
+ * 2 any other gzip file */
+int sniff_compression(const std::string& path);
+
 /*! @brief are the piles' coverage rows resident on the device (rala_hip option "pile_rows")?  RALA_PILE_ROWS=0 says no - a row is
  * then rebuilt from the read's overlap bounds when Pile::data() or the -d output asks for it, and the device holds 2 bytes per base
  * less; read where the devices are opened; without it: yes - see README.md, "Piles without resident rows" */
