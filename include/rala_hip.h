@@ -125,6 +125,9 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * "debug_gzip_false_sync" (tests: every n-th of those chunks is given a bogus block start at its first bit; 0, the default: none),
  * "debug_sequence_window" (tests: rala_hip_index_sequences takes the read file's text through windows of this many bytes; 0, the
  * default: a quarter of the free device memory, 2 GiB at most),
+ * "layout_fused_max" (default 1024; rala_hip_layout_batch: a component of at most this many points is laid out by one workgroup
+ * in one launch, a larger one step by step with all other larger ones; 0: none is fused; a value above 1024 - what a workgroup's
+ * threads and LDS hold - or below 0 is RALA_HIP_EINVAL),
  * "debug_pile_stop_after" (diagnostics: leave the run-space pile kernel after phase k, 99 = all;
  * 100 * m + k: the same without the row stores (m = 1), tools/phase_probe.py) */
 int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value);
@@ -552,6 +555,32 @@ int rala_hip_mg_get_timings(rala_hip_mg* mg, rala_hip_mg_timings* out);
  * per-point task. */
 int rala_hip_layout(rala_hip_ctx* ctx, uint32_t n, double* x, double* y, const uint32_t* adj_off, const uint32_t* adj,
                     uint32_t iterations, double k, double t, double dt);
+
+/* The same for all components of a round in one call (src/graph.cpp:1132-1226 once per component of the loop at :1106): the
+ * result equals rala_hip_layout on every component's slice in turn, bit for bit; components do not interact.  The points of
+ * component c are x / y[comp_off[c] .. comp_off[c + 1]) (host, in / out, component after component); the partners of point p
+ * (an index into the concatenation) are adj[adj_off[p] .. adj_off[p + 1]), as COMPONENT-LOCAL point indices, n_c = the origin
+ * as above; k[c] is the component's spring constant; iterations, t and dt are shared.  One upload, the device work, one
+ * download, one wait.  A component of at most "layout_fused_max" points (rala_hip_set_option) is laid out by one workgroup
+ * that keeps the positions in LDS through all steps - one launch per size class (256 / 1024 points) over all such components;
+ * the larger ones take one launch per step together.
+ * Checked on the host before anything is enqueued (RALA_HIP_EINVAL, nothing touched): comp_off and adj_off start at 0 and do
+ * not decrease, every adj value of component c is at most n_c.  Empty components, n_components == 0 and iterations == 0 are
+ * valid and leave x and y as they are. */
+int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
+                          const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations, double t,
+                          double dt);
+/* The last rala_hip_layout_batch of the context (zeros before the first; a refused call leaves the previous one's). */
+typedef struct rala_hip_layout_info {
+    uint32_t components_fused_256, components_fused_1024;   /* one workgroup of 256 / 1024 threads each, all steps in one launch */
+    uint32_t components_stepped;                            /* larger ones: one launch per step for all of them */
+    uint32_t components_empty;
+    uint64_t points_fused_256, points_fused_1024, points_stepped;
+    uint32_t step_tiles;        /* workgroups of one step launch */
+    uint32_t launches;          /* kernel launches enqueued */
+    float device_ms;            /* between two HIP events around the kernels (without the copies) */
+} rala_hip_layout_info;
+int rala_hip_get_layout_info(rala_hip_ctx* ctx, rala_hip_layout_info* out);
 
 /* ---- results (host buffers owned by the caller) --------------------------------------- */
 /* is_valid_overlap_ (src/graph.hpp:168), one byte per overlap */

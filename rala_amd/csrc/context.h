@@ -382,6 +382,13 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint32_t> d_sens_off, d_sens_cur, d_sens_ev, d_sens_list, d_sens_split;
     rala_hip::DevBuf<double> d_layout[4];
     rala_hip::DevBuf<uint32_t> d_layout_adj[2];
+    // rala_hip_layout_batch (layout.hip): what one call uploads, packed (positions, k, offsets, lists, tiles), the second
+    // position buffers behind it; the host side of the one copy each way; the events around the device work
+    rala_hip::DevBuf<unsigned char> d_layout_batch;
+    rala_hip::PinnedBuf<unsigned char> p_layout_batch;
+    hipEvent_t ev_layout[2] = {};
+    int64_t layout_fused_max = 1024;      // option: components of at most this many points run fused (0: none)
+    rala_hip_layout_info layout_info = {};
     // pinned staging of small device -> host reads (pipeline.hip: d2h_small / stream_sync)
     struct StagedCopy { void* dst; size_t offset, bytes; };
     rala_hip::PinnedBuf<uint32_t> p_stage;

@@ -677,5 +677,16 @@ void launch_tr_count(uint8_t* marks, uint32_t n_edges, uint32_t* n_pairs, hipStr
 // ---- force-directed layout step (layout_kernels.hip) -------------------------------------------
 void launch_layout_step(uint32_t n, const double* x, const double* y, double* x_out, double* y_out,
                         const uint32_t* adj_off, const uint32_t* adj, double k, double t, hipStream_t s);
+// Many components at once (rala_hip_layout_batch): points concatenated, comp_off their ranges, adj_off global, adj
+// component-local, k per component.  launch_layout_fused: every component of list[] (at most `block` points each; block 256
+// or 1024) in one workgroup, all steps in the launch; x_out / y_out may be x / y.  launch_layout_batch_step: one step of the
+// components behind the tile table {component, first local point of kLayoutTile}.
+constexpr uint32_t kLayoutTile = 256;
+void launch_layout_fused(uint32_t block, uint32_t n_list, const uint32_t* list, const uint32_t* comp_off, const double* x,
+                         const double* y, double* x_out, double* y_out, const uint32_t* adj_off, const uint32_t* adj,
+                         const double* k, uint32_t iterations, double t, double dt, hipStream_t s);
+void launch_layout_batch_step(uint32_t n_tiles, const uint2* tiles, const uint32_t* comp_off, const double* x, const double* y,
+                              double* x_out, double* y_out, const uint32_t* adj_off, const uint32_t* adj, const double* k,
+                              double t, hipStream_t s);
 
 }  // namespace rala_hip

@@ -2296,6 +2296,7 @@ void rala_hip_destroy(rala_hip_ctx* ctx) {
     if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_up) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->ev_layout) if (e) (void)hipEventDestroy(e);
     if (ctx->copy) (void)hipStreamDestroy(ctx->copy);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
@@ -2340,6 +2341,11 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "use_partitioned_buckets")) { ctx->use_partitioned_buckets = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "use_side_stream")) { ctx->use_side_stream = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "sensitive_in_device_memory")) { ctx->sens_in_device = value != 0; return RALA_HIP_OK; }
+    if (!strcmp(key, "layout_fused_max")) {
+        if (value < 0 || value > 1024) return fail(ctx, RALA_HIP_EINVAL, "layout_fused_max: 0 .. 1024");
+        ctx->layout_fused_max = value;
+        return RALA_HIP_OK;
+    }
     if (!strcmp(key, "host_threads")) {
         ctx->host_threads = value;
         ctx->pool.reset(new HostPool((unsigned)std::max<int64_t>(1, std::min<int64_t>(value, 256))));

@@ -28,7 +28,8 @@ SYMBOLS = (
     "rala_hip_dedupe", "rala_hip_emit_bound_tuples", "rala_hip_set_bound_tuples", "rala_hip_import_state",
     "rala_hip_emit_bound_tuples_bucketed", "rala_hip_get_device_state", "rala_hip_import_state_device",
     "rala_hip_bound_records_fit", "rala_hip_emit_bound_records_bucketed", "rala_hip_set_bound_records",
-    "rala_hip_copy_device_state", "rala_hip_layout", "rala_hip_find_repetitive_hills",
+    "rala_hip_copy_device_state", "rala_hip_layout", "rala_hip_layout_batch", "rala_hip_get_layout_info",
+    "rala_hip_find_repetitive_hills",
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
     "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
@@ -93,6 +94,14 @@ class GzipTimings(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LayoutInfo(ctypes.Structure):
+    _fields_ = [("components_fused_256", ctypes.c_uint32), ("components_fused_1024", ctypes.c_uint32),
+                ("components_stepped", ctypes.c_uint32), ("components_empty", ctypes.c_uint32),
+                ("points_fused_256", ctypes.c_uint64), ("points_fused_1024", ctypes.c_uint64),
+                ("points_stepped", ctypes.c_uint64), ("step_tiles", ctypes.c_uint32), ("launches", ctypes.c_uint32),
+                ("device_ms", ctypes.c_float)]
+
+
 class SequenceSliceInfo(ctypes.Structure):
     """rala_hip_sequence_slice_info"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("windows", "max_window_text_bytes", "bases")] + [(n, ctypes.c_float) for n in (
@@ -152,6 +161,8 @@ def lib(build=True):
         L.rala_hip_import_state_device.argtypes = [vp, ctypes.POINTER(DeviceState)]
         L.rala_hip_copy_device_state.argtypes = [vp, ctypes.POINTER(DeviceState)]
         L.rala_hip_layout.argtypes = [vp, u32, vp, vp, vp, vp, u32, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        L.rala_hip_layout_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, ctypes.c_double, ctypes.c_double]
+        L.rala_hip_get_layout_info.argtypes = [vp, ctypes.POINTER(LayoutInfo)]
         L.rala_hip_find_repetitive_hills.argtypes = [vp, u64, u32, u32, ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint16]
         L.rala_hip_mg_unique_id.argtypes = [vp]
         L.rala_hip_mg_local_group_create.argtypes = [u32, ctypes.POINTER(vp)]
@@ -425,6 +436,26 @@ class Context:
         adj = np.ascontiguousarray(adj, dtype=np.uint32)
         self._check(self.L.rala_hip_layout(self.h, len(x), x.ctypes.data, y.ctypes.data, adj_off.ctypes.data,
                                            adj.ctypes.data if len(adj) else None, iterations, k, t, dt))
+
+    def layout_batch(self, comp_off, x, y, adj_off, adj, k, iterations, t, dt):
+        """the layout steps of all components in one call (rala_hip_layout_batch): component c's points are
+        x / y[comp_off[c]:comp_off[c + 1]] (float64, updated in place), adj holds component-local indices, k one per component"""
+        assert x.dtype == np.float64 and y.dtype == np.float64 and x.flags.c_contiguous and y.flags.c_contiguous
+        comp_off = np.ascontiguousarray(comp_off, dtype=np.uint32)
+        adj_off = np.ascontiguousarray(adj_off, dtype=np.uint32)
+        adj = np.ascontiguousarray(adj, dtype=np.uint32)
+        k = np.ascontiguousarray(k, dtype=np.float64)
+        n_components = max(len(comp_off) - 1, 0)
+        assert len(k) == n_components
+        self._check(self.L.rala_hip_layout_batch(self.h, n_components, comp_off.ctypes.data if len(comp_off) else None,
+                                                 x.ctypes.data, y.ctypes.data, adj_off.ctypes.data if len(adj_off) else None,
+                                                 adj.ctypes.data if len(adj) else None, k.ctypes.data, iterations, t, dt))
+
+    def layout_info(self):
+        """the last layout_batch: components and points per path, launches, device milliseconds"""
+        info = LayoutInfo()
+        self._check(self.L.rala_hip_get_layout_info(self.h, ctypes.byref(info)))
+        return {name: getattr(info, name) for name, _ in LayoutInfo._fields_}
 
     def emit_bound_tuples_bucketed(self, world, tuples_ptr):
         """tuples grouped by owner rank; returns the bucket sizes"""

@@ -88,8 +88,9 @@ void AssemblyGraph::note_transitive_edges() {
     std::sort(transitive_edges_.begin(), transitive_edges_.end());
 }
 
-// graph.cpp:1056-1279
-int AssemblyGraph::postprocess(const LayoutEngine& engine, uint32_t seed) {
+// graph.cpp:1060-1130, the part of postprocess that both entries share: the transitive list is cleaned, the
+// components found, and those the layout runs on (at least 6 nodes, a junction) returned in the order it takes them
+std::vector<std::vector<uint32_t>> AssemblyGraph::layout_components() {
     // duplicates and pairs that lost a node leave the transitive list (:1060-1073)
     if (!transitive_edges_.empty()) {
         std::vector<std::pair<uint64_t, uint64_t>> tmp = {transitive_edges_[0]};
@@ -126,16 +127,38 @@ int AssemblyGraph::postprocess(const LayoutEngine& engine, uint32_t seed) {
     std::sort(components.begin(), components.end(), [](const std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
         return a.size() != b.size() ? a.size() > b.size() : a[0] < b[0];
     });
+    components.erase(std::remove_if(components.begin(), components.end(), [&](const std::vector<uint32_t>& component) {
+        if (component.size() < 6) return true;
+        for (uint32_t v : component) if (nodes_[v].is_junction()) return false;
+        return true;
+    }), components.end());
+    return components;
+}
+
+// attraction partners of a component's points in the reference's order: prefix edges, suffix edges, transitive
+// edges; local(node) = the partner's point, or the component's size for a partner outside it (it sits at the
+// origin: points_ is zero there).  Appends to adj; adj_off gets one entry per point (the end of its list).
+template <class Local>
+void AssemblyGraph::attraction_lists(const std::vector<uint32_t>& component, const Local& local,
+    std::vector<uint32_t>& adj_off, std::vector<uint32_t>& adj) const {
+    for (uint32_t v : component) {
+        for (uint32_t e : nodes_[v].prefix_edges) adj.push_back(local(edges_[e].begin_node & ~1u));
+        for (uint32_t e : nodes_[v].suffix_edges) adj.push_back(local(edges_[e].end_node & ~1u));
+        auto lo = std::lower_bound(transitive_edges_.begin(), transitive_edges_.end(),
+            std::make_pair((uint64_t)v, (uint64_t)0));
+        for (; lo != transitive_edges_.end() && lo->first == v; ++lo) adj.push_back(local(lo->second));
+        adj_off.push_back((uint32_t)adj.size());
+    }
+}
+
+// graph.cpp:1056-1279
+int AssemblyGraph::postprocess(const LayoutEngine& engine, uint32_t seed) {
+    const std::vector<std::vector<uint32_t>> components = layout_components();
 
     std::mt19937 generator(seed);
     std::uniform_real_distribution<> distribution(0., 1.);
-    std::vector<int64_t> member_of(n0, -1);
+    std::vector<int64_t> member_of(nodes_.size(), -1);
     for (const auto& component : components) {
-        if (component.size() < 6) continue;
-        bool has_junctions = false;
-        for (uint32_t v : component) if (nodes_[v].is_junction()) { has_junctions = true; break; }
-        if (!has_junctions) continue;
-
         const uint32_t n = (uint32_t)component.size();
         const uint32_t num_iterations = 100;
         const double k = sqrt(1. / static_cast<double>(n));
@@ -147,19 +170,8 @@ int AssemblyGraph::postprocess(const LayoutEngine& engine, uint32_t seed) {
             x[i] = distribution(generator);
             y[i] = distribution(generator);
         }
-        // attraction partners in the reference's order: prefix edges, suffix edges, transitive
-        // edges; a partner outside the component sits at the origin (points_ is zero there)
-        std::vector<uint32_t> adj_off(n + 1, 0), adj;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t v = component[i];
-            auto partner = [&](uint64_t m) { adj.push_back(member_of[m] >= 0 ? (uint32_t)member_of[m] : n); };
-            for (uint32_t e : nodes_[v].prefix_edges) partner(edges_[e].begin_node & ~1u);
-            for (uint32_t e : nodes_[v].suffix_edges) partner(edges_[e].end_node & ~1u);
-            auto lo = std::lower_bound(transitive_edges_.begin(), transitive_edges_.end(),
-                std::make_pair((uint64_t)v, (uint64_t)0));
-            for (; lo != transitive_edges_.end() && lo->first == v; ++lo) partner(lo->second);
-            adj_off[i + 1] = (uint32_t)adj.size();
-        }
+        std::vector<uint32_t> adj_off(1, 0), adj;
+        attraction_lists(component, [&](uint64_t m) { return member_of[m] >= 0 ? (uint32_t)member_of[m] : n; }, adj_off, adj);
         // the reference's loop advances its counter twice per pass (:1132, :1225): 50 steps
         const int rc = engine(n, x.data(), y.data(), adj_off.data(), adj.data(), num_iterations / 2, k, t, dt);
         if (rc != 0) return rc;
@@ -172,6 +184,57 @@ int AssemblyGraph::postprocess(const LayoutEngine& engine, uint32_t seed) {
             edges_[e.id ^ 1].weight = e.weight;
         }
         for (uint32_t v : component) member_of[v] = -1;
+    }
+    return 0;
+}
+
+// The same with ONE engine call for all components (rala_hip_layout_batch) and one pass over the edges behind it.
+// postprocess knows one component at a time: a partner that belongs to ANOTHER component - two components can be
+// joined by a remembered transitive pair after the edge between them is gone - has member_of -1 there and sits at
+// the origin.  Here all components are known at once, so a point carries its component's number beside its index.
+int AssemblyGraph::postprocess_batched(const BatchLayoutEngine& engine, uint32_t seed) {
+    const std::vector<std::vector<uint32_t>> components = layout_components();
+    if (components.empty()) return 0;
+
+    std::mt19937 generator(seed);
+    std::uniform_real_distribution<> distribution(0., 1.);
+    const uint32_t num_iterations = 100;
+    const double t = 0.1;
+    const double dt = t / static_cast<double>(num_iterations + 1);
+    std::vector<int64_t> component_of(nodes_.size(), -1);
+    std::vector<uint32_t> member_of(nodes_.size(), 0);
+    std::vector<uint32_t> comp_off(1, 0);
+    std::vector<double> x, y, k;
+    // the generator's draws in postprocess' order: component after component, x then y per point
+    for (size_t c = 0; c < components.size(); ++c) {
+        const uint32_t n = (uint32_t)components[c].size();
+        k.push_back(sqrt(1. / static_cast<double>(n)));
+        for (uint32_t i = 0; i < n; ++i) {
+            component_of[components[c][i]] = (int64_t)c;
+            member_of[components[c][i]] = i;
+            x.push_back(distribution(generator));
+            y.push_back(distribution(generator));
+        }
+        comp_off.push_back((uint32_t)x.size());
+    }
+    std::vector<uint32_t> adj_off(1, 0), adj;
+    for (size_t c = 0; c < components.size(); ++c) {
+        const uint32_t n = (uint32_t)components[c].size();
+        attraction_lists(components[c], [&](uint64_t m) { return component_of[m] == (int64_t)c ? member_of[m] : n; },
+            adj_off, adj);
+    }
+    const int rc = engine((uint32_t)components.size(), comp_off.data(), x.data(), y.data(), adj_off.data(), adj.data(),
+        k.data(), num_iterations / 2, t, dt);
+    if (rc != 0) return rc;
+    for (auto& e : edges_) {
+        if (!e.alive || (e.id & 1)) continue;
+        const uint32_t va = e.begin_node & ~1u, vb = e.end_node & ~1u;
+        const int64_t c = component_of[va];
+        if (c < 0 || component_of[vb] != c) continue;
+        const size_t a = comp_off[c] + member_of[va], b = comp_off[c] + member_of[vb];
+        const double dx = x[a] - x[b], dy = y[a] - y[b];
+        e.weight = sqrt(dx * dx + dy * dy);
+        edges_[e.id ^ 1].weight = e.weight;
     }
     return 0;
 }

@@ -9,8 +9,8 @@
  *
  * postprocess (:1056-1279) is the force-directed layout that gives edges their weights; its
  * O(n^2) iterations run through a caller-supplied engine (the GPU kernel behind
- * rala_hip_layout), everything around it - components, initial points, attraction lists - is
- * here.  The reference seeds it from std::random_device and walks unordered sets; this build
+ * rala_hip_layout, or rala_hip_layout_batch for all components at once: postprocess_batched),
+ * everything around it - components, initial points, attraction lists - is here.  The reference seeds it from std::random_device and walks unordered sets; this build
  * fixes the seed and the orders (ascending node ids), which makes runs reproducible.
  *
  * Index based: nodes and edges live in two vectors and refer to each other by position;
@@ -78,6 +78,16 @@ public:
         uint32_t iterations, double k, double t, double dt)> LayoutEngine;
     /*! @brief graph.cpp:1056-1279: edge weights from a force-directed layout per component */
     int postprocess(const LayoutEngine& engine, uint32_t seed = 0);
+    /*!
+     * @brief the layouts of all components in one call: the points of component c are x / y[comp_off[c] .. comp_off[c + 1]),
+     * the partners of point p (an index into the concatenation) adj[adj_off[p] .. adj_off[p + 1]) as indices INSIDE p's
+     * component (its size = the origin), k one per component; every component as LayoutEngine would lay it out alone.
+     */
+    typedef std::function<int(uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
+        const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations, double t, double dt)>
+        BatchLayoutEngine;
+    /*! @brief postprocess with one engine call for all components and one pass over the edges; the same weights */
+    int postprocess_batched(const BatchLayoutEngine& engine, uint32_t seed = 0);
     uint32_t remove_long_edges();
     uint32_t remove_tips();
     uint32_t remove_bubbles();
@@ -105,6 +115,12 @@ private:
     // replaces the chain begin .. end by a freshly appended unitig pair, re-attaching the edge
     // that enters the chain and the edge that leaves it
     void splice_unitig(uint32_t begin_node, uint32_t end_node, bool attach);
+    // what postprocess and postprocess_batched share: the components the layout runs on, in its order (cleans the
+    // transitive list first), and the attraction lists of one of them
+    std::vector<std::vector<uint32_t>> layout_components();
+    template <class Local>
+    void attraction_lists(const std::vector<uint32_t>& component, const Local& local, std::vector<uint32_t>& adj_off,
+        std::vector<uint32_t>& adj) const;
 
     std::vector<Node> nodes_;
     std::vector<Edge> edges_;

@@ -43,6 +43,18 @@ int ag_postprocess(void* h, uint32_t seed, ag_layout_fn engine) {
                  double k, double t, double dt) { return engine(n, x, y, adj_off, adj, iterations, k, t, dt); },
         seed);
 }
+// engine: all components in one call (rala_hip_layout_batch through a ctypes callback in the GPU tests)
+typedef int (*ag_layout_batch_fn)(uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
+                                  const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
+                                  double t, double dt);
+int ag_postprocess_batched(void* h, uint32_t seed, ag_layout_batch_fn engine) {
+    return ((rala::AssemblyGraph*)h)->postprocess_batched(
+        [engine](uint32_t n_components, const uint32_t* comp_off, double* x, double* y, const uint32_t* adj_off,
+                 const uint32_t* adj, const double* k, uint32_t iterations, double t, double dt) {
+            return engine(n_components, comp_off, x, y, adj_off, adj, k, iterations, t, dt);
+        },
+        seed);
+}
 void ag_edge_weights(void* h, double* w) {
     auto* g = (rala::AssemblyGraph*)h;
     for (size_t i = 0; i < g->edges().size(); ++i) w[i] = g->edges()[i].alive ? g->edges()[i].weight : 0.0;

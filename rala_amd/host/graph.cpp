@@ -761,10 +761,18 @@ uint32_t Graph::remove_transitive_edges() {
 // reference src/graph.cpp:1056-1279
 void Graph::postprocess() {
     StageTimer timer;
-    const int rc = graph_.postprocess([&](uint32_t n, double* x, double* y, const uint32_t* adj_off, const uint32_t* adj,
-                                          uint32_t iterations, double k, double t, double dt) {
-        return rala_hip_layout(ctx_, n, x, y, adj_off, adj, iterations, k, t, dt);
-    }, layout_seed_++);
+    // all components of the round in one call where io::layout_batch_wanted() (RALA_LAYOUT_BATCH=1), component after
+    // component without it; the same weights either way
+    const int rc = io::layout_batch_wanted()
+        ? graph_.postprocess_batched([&](uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
+                                         const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
+                                         double t, double dt) {
+              return rala_hip_layout_batch(ctx_, n_components, comp_off, x, y, adj_off, adj, k, iterations, t, dt);
+          }, layout_seed_++)
+        : graph_.postprocess([&](uint32_t n, double* x, double* y, const uint32_t* adj_off, const uint32_t* adj,
+                                 uint32_t iterations, double k, double t, double dt) {
+              return rala_hip_layout(ctx_, n, x, y, adj_off, adj, iterations, k, t, dt);
+          }, layout_seed_++);
     check(ctx_, rc, "postprocess");
     timer("[rala::Graph::postprocess]");
 }

@@ -77,6 +77,11 @@ bool device_gzip_members_wanted() {
     return e ? atoi(e) == 2 : false;
 }
 
+bool layout_batch_wanted() {
+    const char* e = getenv("RALA_LAYOUT_BATCH");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool device_compressed_wanted() {
     const char* e = getenv("RALA_DEVICE_COMPRESSED");
     return e ? atoi(e) != 0 : false;

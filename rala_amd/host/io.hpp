@@ -46,6 +46,10 @@ bool device_gzip_members_wanted();
  * .mhap or .mhap.gz given with -s (rala_hip_tokenise_sensitive)?  RALA_DEVICE_COMPRESSED=1 says so; without it: no - unmeasured,
  * see README.md, "Compressed overlap files" */
 bool device_compressed_wanted();
+/*! @brief does Graph::postprocess lay out all components of a round in one call (rala_hip_layout_batch) instead of one
+ * rala_hip_layout per component?  RALA_LAYOUT_BATCH=1 says so; without it: no - the same weights either way; many components
+ * gain a lot, one giant component loses 1 %, see README.md, "Layout of all components in one call" */
+bool layout_batch_wanted();
 /*! @brief what a file is by its first 18 bytes: 0 text (or unreadable), 1 BGZF (what the host reader's BgzfSource recognises),
  * 2 any other gzip file */
 int sniff_compression(const std::string& path);
