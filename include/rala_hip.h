@@ -313,6 +313,36 @@ int rala_hip_get_sequence_index(rala_hip_ctx* ctx, uint64_t* name_off, uint32_t*
 /* ship_ms: the file (BGZF: its compressed bytes) to the device; tokenize_ms: the kernels (BGZF: the inflater among them);
  * bytes: the text's; lines: the records (the "loaded sequences" stage of src/graph.cpp:246-266) */
 int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* out);
+/* The name table built on the device from the index of the last successful rala_hip_index_sequences, and installed exactly where
+ * rala_hip_set_name_table would have put the host's (replaces reference src/graph.cpp:249-264: one string per read into an
+ * unordered_map - here the host's string-plus-map loop, NameTable::build and the upload of its table): the same buckets, hash
+ * (rala_amd/csrc/name_table.h) and capacity - the smallest power of two not below 2 n + 2, at least 16 -, a later record of a name
+ * takes it as in NameTable::build; the arena is a device-to-device COPY of the index's names (a later rala_hip_index_sequences does
+ * not touch the table), a bucket's `off` its read's name_off.  Every look-up answers as in the host's table; which name sits
+ * in which slot of a probe path may differ from it, and from run to run.  *n_buckets: the capacity; *n_distinct: the taken buckets.
+ * RALA_HIP_EINVAL: no index; RALA_HIP_ETOOLARGE: 2^32 bytes of names or more (`off` has 32 bits), or 2^32 - 1 records or more
+ * (id1 = id + 1); RALA_HIP_EDEVICE where a probe path did not end within n_buckets steps (every probe loop is bounded).  After any
+ * refusal the table installed before is still there, untouched: take the host's build. */
+int rala_hip_build_name_table(rala_hip_ctx* ctx, uint64_t* n_buckets, uint64_t* n_distinct);
+/* The installed table read back, whoever installed it (reference src/graph.cpp:249-264: the map it stands for): n_buckets 32-byte
+ * buckets and arena_bytes bytes of names.  buckets and arena may be NULL: the sizes only.  RALA_HIP_EINVAL: no table installed. */
+int rala_hip_get_name_table(rala_hip_ctx* ctx, void* buckets, char* arena, uint64_t* n_buckets, uint64_t* arena_bytes);
+/* src's installed table copied into dst, device to device (the contexts of a sharded run's ranks, the shares of -s: the map of
+ * reference src/graph.cpp:249-264 once per context) - through pinned host memory where the two devices have no peer access. */
+int rala_hip_copy_name_table(rala_hip_ctx* dst, rala_hip_ctx* src);
+/* The table's hash of the n bytes at p, on the host: no context, no device (name_table.h's name_hash_with, the one definition; the
+ * key of the map of reference src/graph.cpp:249-264). */
+uint64_t rala_hip_name_hash(const char* p, uint64_t n);
+/* The last rala_hip_build_name_table of the context that succeeded (zeros before the first; reference src/graph.cpp:249-264 is what
+ * it replaces). */
+typedef struct rala_hip_name_table_info {
+    uint64_t names;             /* records of the index */
+    uint64_t distinct;          /* taken buckets */
+    uint64_t n_buckets;
+    uint32_t longest_probe;     /* slots the longest insert looked at */
+    float device_ms;            /* between two HIP events around the clear, the two kernels and the arena's copy */
+} rala_hip_name_table_info;
+int rala_hip_get_name_table_info(rala_hip_ctx* ctx, rala_hip_name_table_info* out);
 /* With the option "gzip_on_device" set, rala_hip_index_sequences takes a gzip file of ONE member that is not BGZF as well (what
  * gzip, pigz and basecallers write).  The compressed bytes stay in device memory while the file is indexed - the only buffer
  * whose size depends on the file's; block starts are found and the chain from chunk 0 is followed as for the overlaps (see

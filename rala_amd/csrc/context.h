@@ -237,7 +237,12 @@ struct rala_hip_ctx {
 
     // the device tokeniser (ingest.hip): the host's name table as it is, the file's text, the columns it leaves
     rala_hip::DevBuf<uint8_t> d_name_buckets, d_name_arena, d_paf_text, d_paf_strand;
-    uint64_t n_name_buckets = 0;
+    uint64_t n_name_buckets = 0, n_name_arena_bytes = 0;
+    // ... or the table built here from the sequence index (name_table.hip: rala_hip_build_name_table): the insert kernel's words
+    // (error, longest probe path, taken buckets), the events around the two kernels, the last build
+    rala_hip::DevBuf<uint32_t> d_name_stats;
+    hipEvent_t ev_names[2] = {};
+    rala_hip_name_table_info name_table_info = {};
     rala_hip::DevBuf<uint32_t> d_paf_col[7], d_paf_chunk[2], d_paf_win[7];
     rala_hip::DevBuf<uint8_t> d_paf_win_strand;
     int64_t ingest_window_bytes = 0;    // option: the tokeniser's window over the file's text (0: a quarter of the free device memory)

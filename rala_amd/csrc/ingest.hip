@@ -279,6 +279,7 @@ int rala_hip_set_name_table(rala_hip_ctx* ctx, const void* buckets, uint64_t n_b
     INGEST_CHECK(hipMemcpy(ctx->d_name_buckets.p, buckets, n_buckets * sizeof(NameBucket), hipMemcpyHostToDevice));
     if (arena_bytes) INGEST_CHECK(hipMemcpy(ctx->d_name_arena.p, arena, arena_bytes, hipMemcpyHostToDevice));
     ctx->n_name_buckets = n_buckets;
+    ctx->n_name_arena_bytes = arena_bytes;
     return RALA_HIP_OK;
 }
 

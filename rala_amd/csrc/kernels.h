@@ -522,6 +522,13 @@ void launch_paf_parse(const uint8_t* text, uint64_t n, uint64_t n_avail, bool fi
                       uint64_t n_buckets, const char* arena, const uint32_t* read_len, uint32_t n_reads, bool check_lengths,
                       const PafColumns& out, uint32_t* flags, unsigned long long* first_bad, hipStream_t s, bool mhap = false);
 
+// ---- the name table from the sequence index (name_table_kernels.hip) --------------------------
+// buckets: n_buckets (a power of two, > n) zeroed NameBuckets; arena, name_off, name_len: the index's n records; stats: three zeroed
+// words - [0] != 0 a probe path did not end (nothing of the table may be used), [1] the longest probe path in slots, [2] the
+// taken buckets (the distinct names).  Insert, then fill, on s.
+void launch_name_table_build(const uint8_t* arena, const uint64_t* name_off, const uint32_t* name_len, uint32_t n, void* buckets,
+                             uint64_t n_buckets, uint32_t* stats, hipStream_t s);
+
 // ---- FASTA / FASTQ text -> the sequence index (sequence_kernels.hip) -------------------------
 // why a file is not indexed here (rala_hip_index_sequences' *irregular; 8 is the inflater's, as for the overlaps)
 constexpr uint32_t kSeqNotFourLines = 1;        // FASTQ that is not four lines per record

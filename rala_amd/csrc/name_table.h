@@ -1,8 +1,9 @@
 // Read name -> id as the tokenisers look it up, on the host (rala_amd/host/io.cpp: NameTable) and on the device
 // (ingest_kernels.hip): open addressing over 32-byte buckets - hash, id, length and the first 16 bytes of the name in one
 // line - and the names' bytes in an arena for the names that are longer.  The table is built on the host
-// (rala::io::NameTable::build) and handed to the device as it is (rala_hip_set_name_table): one definition of the hash and
-// of a bucket for both sides.
+// (rala::io::NameTable::build) and handed to the device as it is (rala_hip_set_name_table), or built on the device from the
+// sequence index (name_table_kernels.hip: rala_hip_build_name_table) and adopted by the host where a host reader needs it
+// (rala::io::NameTable::adopt): one definition of the hash and of a bucket for both sides.
 #pragma once
 
 #include <stdint.h>

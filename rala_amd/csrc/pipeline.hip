@@ -2297,6 +2297,7 @@ void rala_hip_destroy(rala_hip_ctx* ctx) {
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_up) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_layout) if (e) (void)hipEventDestroy(e);
+    for (auto& e : ctx->ev_names) if (e) (void)hipEventDestroy(e);
     if (ctx->copy) (void)hipStreamDestroy(ctx->copy);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);

@@ -36,6 +36,8 @@ SYMBOLS = (
     "rala_hip_bgzf_index_range", "rala_hip_bgzf_pieces_chain", "rala_hip_tokenise_sensitive", "rala_hip_mg_set_overlaps_from_mhap",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
+    "rala_hip_build_name_table", "rala_hip_get_name_table", "rala_hip_copy_name_table", "rala_hip_name_hash",
+    "rala_hip_get_name_table_info",
     "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",
     "rala_hip_mg_destroy", "rala_hip_mg_last_error", "rala_hip_mg_set_reads", "rala_hip_mg_slice_cuts",
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
@@ -102,6 +104,15 @@ class LayoutInfo(ctypes.Structure):
                 ("device_ms", ctypes.c_float)]
 
 
+class NameTableInfo(ctypes.Structure):
+    """rala_hip_name_table_info"""
+    _fields_ = [("names", ctypes.c_uint64), ("distinct", ctypes.c_uint64), ("n_buckets", ctypes.c_uint64),
+                ("longest_probe", ctypes.c_uint32), ("device_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SequenceSliceInfo(ctypes.Structure):
     """rala_hip_sequence_slice_info"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("windows", "max_window_text_bytes", "bases")] + [(n, ctypes.c_float) for n in (
@@ -112,6 +123,12 @@ class SequenceSliceInfo(ctypes.Structure):
 
 
 _lib = None
+
+
+def name_hash(name):
+    """rala_hip_name_hash: the name table's hash of a name (bytes), on the host - no context, no device"""
+    name = bytes(name)
+    return int(lib().rala_hip_name_hash(ctypes.c_char_p(name), len(name)))
 
 
 def lib(build=True):
@@ -192,6 +209,15 @@ def lib(build=True):
         L.rala_hip_index_sequences.argtypes = [vp, ctypes.c_char_p, i32, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32)]
         L.rala_hip_get_sequence_index.argtypes = [vp] + [vp] * 6
         L.rala_hip_get_sequence_timings.argtypes = [vp, ctypes.POINTER(IngestTimings)]
+        L.rala_hip_set_name_table.argtypes = [vp, vp, u64, vp, u64]
+        L.rala_hip_build_name_table.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.rala_hip_get_name_table.argtypes = [vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.rala_hip_copy_name_table.argtypes = [vp, vp]
+        L.rala_hip_name_hash.argtypes = [vp, u64]
+        L.rala_hip_name_hash.restype = u64
+        L.rala_hip_get_name_table_info.argtypes = [vp, ctypes.POINTER(NameTableInfo)]
+        L.rala_hip_set_overlaps_from_paf.argtypes = [vp, ctypes.c_char_p, i32, u32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
+        L.rala_hip_get_overlap_columns.argtypes = [vp, ctypes.POINTER(u64), vp, vp]
         L.rala_hip_slice_sequences.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, vp, u32, ctypes.POINTER(i32)]
         L.rala_hip_get_sequence_slice_info.argtypes = [vp, ctypes.POINTER(SequenceSliceInfo)]
         L.rala_hip_crc32_chain.argtypes = [vp, vp, u64]
@@ -357,6 +383,59 @@ class Context:
         names = [raw[int(o):int(o) + int(k)] for o, k in zip(name_off, name_len)]
         self.n_reads = n.value
         return 0, {"names": names, "name_off": name_off, "length": length, "data_off": data_off, "data_span": data_span}
+
+    # ---- the name table (name_table.h: 32-byte buckets as a (n_buckets, 8) uint32 array, the names' bytes as a uint8 array) ----
+    def build_name_table(self):
+        """rala_hip_build_name_table: the table from the current sequence index, built and installed on the device
+        -> (n_buckets, n_distinct)"""
+        nb, nd = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.rala_hip_build_name_table(self.h, ctypes.byref(nb), ctypes.byref(nd)))
+        return nb.value, nd.value
+
+    def get_name_table(self):
+        """rala_hip_get_name_table: the installed table -> (buckets, arena)"""
+        nb, ab = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.rala_hip_get_name_table(self.h, None, None, ctypes.byref(nb), ctypes.byref(ab)))
+        buckets = np.zeros((nb.value, 8), dtype=np.uint32)
+        arena = np.zeros(max(ab.value, 1), dtype=np.uint8)
+        self._check(self.L.rala_hip_get_name_table(self.h, buckets.ctypes.data, arena.ctypes.data, ctypes.byref(nb), ctypes.byref(ab)))
+        return buckets, arena[:ab.value]
+
+    def set_name_table(self, buckets, arena):
+        """rala_hip_set_name_table: a table built elsewhere (the host's)"""
+        buckets = np.ascontiguousarray(buckets, dtype=np.uint32)
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        self._check(self.L.rala_hip_set_name_table(self.h, buckets.ctypes.data, buckets.shape[0], arena.ctypes.data if len(arena) else None,
+                                                   len(arena)))
+
+    def copy_name_table_from(self, src):
+        """rala_hip_copy_name_table: src's installed table into this context, device to device"""
+        self._check(self.L.rala_hip_copy_name_table(self.h, src.h))
+
+    def name_table_info(self):
+        t = NameTableInfo()
+        self._check(self.L.rala_hip_get_name_table_info(self.h, ctypes.byref(t)))
+        return t.as_dict()
+
+    def set_overlaps_from_paf(self, path, check_lengths=False, threads=2):
+        """rala_hip_set_overlaps_from_paf with the installed name table -> (irregular, first read with a length mismatch or -1)"""
+        bad, irregular = ctypes.c_int64(-1), ctypes.c_int(0)
+        self._check(self.L.rala_hip_set_overlaps_from_paf(self.h, os.fsencode(path), int(check_lengths), threads, ctypes.byref(bad),
+                                                          ctypes.byref(irregular)))
+        return irregular.value, bad.value
+
+    def overlap_columns(self):
+        """rala_hip_get_overlap_columns: the context's overlaps as they lie on the device -> dict of columns"""
+        n = ctypes.c_uint64(0)
+        self._check(self.L.rala_hip_get_overlap_columns(self.h, ctypes.byref(n), None, None))
+        names = ("a_id", "b_id", "a_begin", "a_end", "b_begin", "b_end", "length")
+        cols = {f: np.zeros(max(n.value, 1), dtype=np.uint32) for f in names}
+        strand = np.zeros(max(n.value, 1), dtype=np.uint8)
+        ptrs = (ctypes.c_void_p * 7)(*[cols[f].ctypes.data for f in names])
+        self._check(self.L.rala_hip_get_overlap_columns(self.h, ctypes.byref(n), ptrs, strand.ctypes.data))
+        out = {f: cols[f][:n.value] for f in names}
+        out["strand"] = strand[:n.value]
+        return out
 
     def slice_sequences(self, path, wanted, length, threads=4):
         """rala_hip_slice_sequences: the bases of the reads `wanted` (ascending records of the current index; length = the

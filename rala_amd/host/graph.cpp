@@ -309,13 +309,45 @@ bool Graph::index_sequences() {
         sequence_index_gzip_ = !ok && gzip_wanted;
         if (!ok && !gzip_wanted) { sequence_index_ = io::SequenceIndex(); return false; }
     }
-    names_.reserve(n);
     read_len_ = ix.length;
+    // the name table built on the device as well, straight from the index (reference src/graph.cpp:249-264): no string and no map
+    // here - the names stay in the arena as it was downloaded.  A refusal (too many bytes of names for 32-bit offsets, no room)
+    // takes the host's build below, whole
+    if (io::device_names_wanted()) {
+        uint64_t n_buckets = 0, n_distinct = 0;
+        if (rala_hip_build_name_table(ctx_, &n_buckets, &n_distinct) == RALA_HIP_OK) {
+            device_names_ = true;
+            name_arena_.swap(arena);
+            name_off_.swap(name_off);
+            name_len_.swap(name_len);
+            return true;
+        }
+    }
+    names_.reserve(n);
     for (uint64_t i = 0; i < n; ++i) {
         names_.emplace_back(arena.data() + name_off[i], name_len[i]);
         name_to_id_[names_.back()] = i;
     }
     return true;
+}
+
+// A host reader is about to run although the device built the name table: it probes exactly that table (adopted through
+// rala_hip_get_name_table); the one reader that wants name_to_id_ - a file with an unknown extension - gets it from the arena.
+void Graph::host_names(const std::string& overlaps_path) {
+    if (!device_names_) return;
+    if (name_table_.n_buckets() == 0) {
+        uint64_t n_buckets = 0, arena_bytes = 0;
+        check(ctx_, rala_hip_get_name_table(ctx_, nullptr, nullptr, &n_buckets, &arena_bytes), "initialize");
+        std::vector<rala_hip::NameBucket> buckets(n_buckets);
+        std::string arena(arena_bytes, '\0');
+        check(ctx_, rala_hip_get_name_table(ctx_, buckets.data(), &arena[0], &n_buckets, &arena_bytes), "initialize");
+        name_table_.adopt(buckets.data(), n_buckets, std::move(arena));
+    }
+    const bool known = io::has_suffix(overlaps_path, ".paf") || io::has_suffix(overlaps_path, ".paf.gz") ||
+                       io::has_suffix(overlaps_path, ".mhap") || io::has_suffix(overlaps_path, ".mhap.gz");
+    if (!known && name_to_id_.empty()) {
+        for (uint64_t i = 0; i < name_off_.size(); ++i) name_to_id_[name_of(i)] = i;
+    }
 }
 
 // reference src/graph.cpp:244-425
@@ -331,7 +363,7 @@ void Graph::initialize() {
     }
     timer("[rala::Graph::initialize] loaded sequences");
     timer();
-    name_table_.build(names_);
+    if (!device_names_) name_table_.build(names_);
     // An uncompressed PAF file: the text goes to the device and is tokenised there (rala_hip_set_overlaps_from_paf;
     // RALA_DEVICE_INGEST=0 keeps the host reader).  A file that tokeniser calls irregular - or cannot take: no regular file,
     // too large for its 32-bit counts, no room for its text in device memory - falls through to the host reader, which knows
@@ -364,8 +396,10 @@ void Graph::initialize() {
     };
     if (ranks_.empty() && device_ingest) {
         check(ctx_, rala_hip_set_reads(ctx_, read_len_.data(), read_len_.size()), "initialize");
-        check(ctx_, rala_hip_set_name_table(ctx_, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
-                                            name_table_.arena().size()), "initialize");
+        if (!device_names_) {               // (else: rala_hip_build_name_table has installed it)
+            check(ctx_, rala_hip_set_name_table(ctx_, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
+                                                name_table_.arena().size()), "initialize");
+        }
         int64_t bad = -1;
         int irregular = 0;
         const int rc = mhap_text ? rala_hip_set_overlaps_from_mhap(ctx_, overlaps_path_.c_str(), 1, std::max(1u, num_threads_), &bad, &irregular)
@@ -398,7 +432,9 @@ void Graph::initialize() {
             th.emplace_back([&, k]() {
                 rala_hip_mg* mg = ranks_[k];
                 int r = rala_hip_mg_set_reads(mg, read_len_.data(), read_len_.size());
-                if (r == RALA_HIP_OK) {
+                if (r == RALA_HIP_OK && device_names_) {
+                    r = rala_hip_copy_name_table(rala_hip_mg_context(mg), ctx_);       // (the main context built it; device to device)
+                } else if (r == RALA_HIP_OK) {
                     r = rala_hip_set_name_table(rala_hip_mg_context(mg), name_table_.buckets(), name_table_.n_buckets(),
                                                 name_table_.arena().data(), name_table_.arena().size());
                 }
@@ -434,6 +470,7 @@ void Graph::initialize() {
         // (irregular, or beyond the tokeniser's limits on some rank: the host reader below - the group is intact unless a
         // rank failed alone, which ends the run at the first collective)
     }
+    host_names(overlaps_path_);
     read_overlaps(overlaps_path_, name_to_id_, name_table_, read_len_, true, num_threads_, overlaps_);
     if (!ranks_.empty()) {
         // every rank gets all read lengths and its slice of the overlaps (cut between runs of
@@ -514,7 +551,8 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         const int s_kind = s_gz && io::device_compressed_wanted() ? io::sniff_compression(sensitive_overlaps_path) : 0;
         const bool s_compressed = io::device_compressed_wanted() &&
                                   (s_gz ? s_kind == 1 || (s_kind == 2 && P == 1 && io::device_gzip_wanted()) : s_mhap);
-        const bool device_ingest = (io::has_suffix(sensitive_overlaps_path, ".paf") || s_compressed) && name_table_.n_buckets() != 0 &&
+        const bool device_ingest = (io::has_suffix(sensitive_overlaps_path, ".paf") || s_compressed) &&
+                                   (name_table_.n_buckets() != 0 || device_names_) &&       // (a table is installed, or can be)
                                    !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
         if (device_ingest) {
             uint64_t file_bytes = 0;
@@ -531,8 +569,9 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
                 th.emplace_back([&, k]() {
                     rala_hip_ctx* c = ranks_.empty() ? ctx_ : rala_hip_mg_context(ranks_[k]);
                     // (a run that took the host reader for the primary overlaps has set no name table yet)
-                    rc[k] = rala_hip_set_name_table(c, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
-                                                    name_table_.arena().size());
+                    rc[k] = device_names_ ? rala_hip_copy_name_table(c, ctx_)
+                                          : rala_hip_set_name_table(c, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
+                                                                    name_table_.arena().size());
                     if (rc[k] == RALA_HIP_OK && s_compressed) {
                         if (s_kind == 2) {
                             rc[k] = rala_hip_set_option(c, "gzip_on_device", 1);
@@ -569,6 +608,7 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
             }
         }
         if (!sens_on_device_) {
+            host_names(sensitive_overlaps_path);
             read_overlaps(sensitive_overlaps_path, name_to_id_, name_table_, read_len_, false, num_threads_, s_cols);
             sens.a_id = s_cols.a_id.data(); sens.b_id = s_cols.b_id.data(); sens.a_begin = s_cols.a_begin.data();
             sens.a_end = s_cols.a_end.data(); sens.b_begin = s_cols.b_begin.data(); sens.b_end = s_cols.b_end.data();
@@ -680,12 +720,12 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
                                               std::max(1u, num_threads_), &irregular) == RALA_HIP_OK && !irregular;
             // (read by read out of the packed buffer: no second copy of all the kept bases)
             for (size_t w = 0; sliced && w < wanted.size(); ++w) {
-                keep(wanted[w], names_[wanted[w]], std::string((const char*)packed.data() + base_off[w], base_off[w + 1] - base_off[w]));
+                keep(wanted[w], name_of(wanted[w]), std::string((const char*)packed.data() + base_off[w], base_off[w + 1] - base_off[w]));
             }
         } else {
             std::vector<std::string> bases;
             sliced = io::slice_sequences(sequences_path_, sequence_index_, wanted, std::max(1u, num_threads_), bases);
-            for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], names_[wanted[w]], bases[w]);
+            for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], name_of(wanted[w]), bases[w]);
         }
     }
     uint64_t seq_id = 0;

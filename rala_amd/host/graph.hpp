@@ -90,6 +90,15 @@ private:
     io::SequenceIndex sequence_index_;  // where the reads' bases lie in the file (the device indexed it; empty: the host reader did)
     bool sequence_index_gzip_ = false;  // ... of a single gzip member's text: the second pass is rala_hip_slice_sequences
     bool index_sequences();
+    // io::device_names_wanted() and the device built the name table from its index (rala_hip_build_name_table): names_ and
+    // name_to_id_ stay empty, the names are the index's bytes as they were downloaded; name_table_ is empty until a host reader
+    // needs it (host_names: it adopts the device's table then)
+    bool device_names_ = false;
+    std::string name_arena_;
+    std::vector<uint64_t> name_off_;
+    std::vector<uint32_t> name_len_;
+    std::string name_of(uint64_t i) const { return device_names_ ? std::string(name_arena_.data() + name_off_[i], name_len_[i]) : names_[i]; }
+    void host_names(const std::string& overlaps_path);
 
     AssemblyGraph graph_;
     uint32_t layout_seed_ = 0;          // one fixed seed per layout round

@@ -107,6 +107,11 @@ bool device_sequences_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool device_names_wanted() {
+    const char* e = getenv("RALA_DEVICE_NAMES");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool read_fasta(const std::string& path, const SequenceSink& sink) {
     Lines in(path);
     if (!in.ok()) return false;
@@ -521,7 +526,7 @@ NameTable::~NameTable() {
     if (bucket_) free_block(bucket_, n_bucket_ * sizeof(Bucket));
 }
 
-void NameTable::build(const std::vector<std::string>& names) {
+void NameTable::build(const std::vector<std::string>& names, const uint64_t* order) {
     const NearParserCores near;
     uint64_t cap = 16;
     while (cap < 2 * names.size() + 2) cap <<= 1;
@@ -533,7 +538,8 @@ void NameTable::build(const std::vector<std::string>& names) {
     arena_.clear();
     // a later duplicate name replaces an earlier one, like unordered_map::operator[] in the
     // reference (src/graph.cpp:262)
-    for (size_t i = 0; i < names.size(); ++i) {
+    for (size_t at = 0; at < names.size(); ++at) {
+        const size_t i = order ? (size_t)order[at] : at;
         const std::string& s = names[i];
         const uint64_t h = hash_bytes(s.data(), s.size());
         Bucket nb = Bucket();
@@ -548,6 +554,20 @@ void NameTable::build(const std::vector<std::string>& names) {
             }
         }
     }
+}
+
+void NameTable::adopt(const rala_hip::NameBucket* buckets, size_t n_buckets, std::string arena) {
+    const NearParserCores near;
+    if (bucket_) free_block(bucket_, n_bucket_ * sizeof(Bucket));
+    bucket_ = nullptr;
+    n_bucket_ = 0;
+    mask_ = 0;
+    arena_ = std::move(arena);
+    if (n_buckets == 0 || (n_buckets & (n_buckets - 1)) != 0) return;
+    bucket_ = (Bucket*)allocate_block(n_buckets * sizeof(Bucket));
+    memcpy((void*)bucket_, buckets, n_buckets * sizeof(Bucket));
+    n_bucket_ = n_buckets;
+    mask_ = n_buckets - 1;
 }
 
 uint64_t NameTable::find(const char* p, size_t n, uint64_t h) const {

@@ -64,6 +64,12 @@ bool pile_rows_wanted();
  * overlap files", for what was measured */
 bool device_sequences_wanted();
 
+/*! @brief with the read file indexed on the device (device_sequences_wanted(), and only where that index succeeded): is the name
+ * table built there as well, straight from the index (rala_hip_build_name_table), instead of one string per read, a map and
+ * NameTable::build on one host thread?  RALA_DEVICE_NAMES=1 says so, read where the file is opened; without it: no - see README.md,
+ * "The name table from the device's index", for what was measured */
+bool device_names_wanted();
+
 // ---- the second pass over the read file, from the device's sequence index ----------------------
 // Where every read's bases lie (rala_hip_get_sequence_index): the text [data_off, data_off + data_span) with every newline
 // and every carriage return in front of one taken out, `length` bases.  A BGZF file: offsets are offsets into its text, and
@@ -94,7 +100,12 @@ bool slice_sequences(const std::string& path, const SequenceIndex& index, const 
 // caller start the bucket's load while it parses on (io.cpp: lines are resolved in batches).
 class NameTable {
 public:
-    void build(const std::vector<std::string>& names);
+    // order (optional, a permutation of the ids): the names are inserted in this order, names[order[k]] as id order[k] -
+    // which slot of its probe path a name takes depends on it, no answer does as long as a name's last id comes last
+    void build(const std::vector<std::string>& names, const uint64_t* order = nullptr);
+    // takes over a finished table - the one the device built from its sequence index (rala_hip_get_name_table): n_buckets (a
+    // power of two) buckets, copied, and the bytes their `off` point into.  The host readers then probe exactly what the device built.
+    void adopt(const rala_hip::NameBucket* buckets, size_t n_buckets, std::string arena);
     static uint64_t hash(const char* p, size_t n);
     void prefetch(uint64_t h) const { if (bucket_) __builtin_prefetch(&bucket_[h & mask_]); }
     // id of the name [p, p + n) whose hash is h, or ~0ull

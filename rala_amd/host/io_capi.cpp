@@ -108,6 +108,55 @@ void io_paf_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uin
 }
 void io_paf_free(void* h) { delete (Parsed*)h; }
 
+// rala::io::NameTable by itself (tests/test_name_table_cpu.py, tests/test_gpu_name_table.py): built from n names given in order
+// (names: one behind the other, name_len their lengths), or adopted from finished buckets; find; the buckets and the arena
+// (order: null, or the permutation of the ids in which the names are inserted)
+void* io_names_build(const char* names, const uint32_t* name_len, uint64_t n, const uint64_t* order) {
+    std::vector<std::string> nm;
+    nm.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) { nm.emplace_back(names, name_len[i]); names += name_len[i]; }
+    auto* t = new rala::io::NameTable();
+    t->build(nm, order);
+    return t;
+}
+void* io_names_adopt(const void* buckets, uint64_t n_buckets, const char* arena, uint64_t arena_bytes) {
+    auto* t = new rala::io::NameTable();
+    t->adopt((const rala_hip::NameBucket*)buckets, n_buckets, std::string(arena ? arena : "", arena ? arena_bytes : 0));
+    return t;
+}
+// What Graph::index_sequences and Graph::initialize do on the host between the device's index and the first tokeniser launch when
+// the device does not build the table (tools/name_table_bench.py: the leg to beat): one string per read and its entry in an
+// unordered_map, then NameTable::build over the strings.  *map_size: the distinct names (and keeps the map from being optimised away)
+void* io_names_strings_map_build(const char* arena, const uint64_t* name_off, const uint32_t* name_len, uint64_t n, uint64_t* map_size) {
+    std::vector<std::string> names;
+    std::unordered_map<std::string, uint64_t> name_to_id;
+    names.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        names.emplace_back(arena + name_off[i], name_len[i]);
+        name_to_id[names.back()] = i;
+    }
+    if (map_size) *map_size = name_to_id.size();
+    auto* t = new rala::io::NameTable();
+    t->build(names);
+    return t;
+}
+const void* io_names_bucket_ptr(void* h) { return ((rala::io::NameTable*)h)->buckets(); }
+const char* io_names_arena_ptr(void* h) { return ((rala::io::NameTable*)h)->arena().data(); }
+uint64_t io_names_buckets(void* h) { return ((rala::io::NameTable*)h)->n_buckets(); }
+uint64_t io_names_arena_bytes(void* h) { return ((rala::io::NameTable*)h)->arena().size(); }
+void io_names_copy(void* h, void* buckets, char* arena) {
+    const auto& t = *(rala::io::NameTable*)h;
+    if (buckets) memcpy(buckets, (const void*)t.buckets(), t.n_buckets() * sizeof(rala_hip::NameBucket));
+    if (arena) memcpy(arena, t.arena().data(), t.arena().size());
+}
+// the ids of n queries (one behind the other), ~0 where a name is absent
+void io_names_find(void* h, const char* queries, const uint32_t* query_len, uint64_t n, uint64_t* id) {
+    const auto& t = *(rala::io::NameTable*)h;
+    for (uint64_t i = 0; i < n; ++i) { id[i] = t.find(queries, query_len[i]); queries += query_len[i]; }
+}
+uint64_t io_names_hash(const char* p, uint64_t n) { return rala::io::NameTable::hash(p, n); }
+void io_names_free(void* h) { delete (rala::io::NameTable*)h; }
+
 // io::read_fasta (fastq = 0) / io::read_fastq (1): per record the name, the number of bases and a hash of them
 void* io_seq_parse(const char* path, int fastq) {
     auto* out = new Sequences();
