@@ -40,6 +40,43 @@ def oracle_stages(ds, n_threads=8, ref=False, with_tr=True, n_data=64, data_of=(
     return st
 
 
+_crafted = {}
+
+
+def crafted_stages(case, n_threads=8):
+    """The oracle on a case of tests/compcase.py: the first pass, then every read's crafted row in place of its pile, and the
+    per-pile annotation of Graph::initialize (graph.cpp:387-403) on it: find_valid_region - which leaves a live read's region
+    [0, length) as it is, no value of its row is below 4, and takes the pile of a read that is to be dead, whose row is all zero -
+    find_median, find_chimeric_hills, find_chimeric_pits.  Then the snapshot rala_hip_import_state takes, then the stages of
+    oracle_stages.  Computed once per case and never changed."""
+    import compcase
+    if case.name in _crafted:
+        return _crafted[case.name]
+    o = Oracle(case.read_len, case.overlaps, n_threads=n_threads)
+    o.pass1()
+    for r in range(case.n_reads):
+        o.set_pile_state(r, compcase.row_of(case, r), 0, int(case.read_len[r]))
+    st = {"init_rc": o.annotate()}    # (the oracle itself, with every row, is let go when this returns)
+    assert st["init_rc"] == 0
+    st["valid"] = o.valid()
+    st["piles0"] = o.piles()
+    st["pits0"] = o.all_intervals(0)
+    st["hills0"] = o.all_intervals(1)
+    o.pass2()
+    st["ov_pass2"] = o.overlap_list(0)
+    st["int_pass2"] = o.overlap_list(1)
+    o.preprocess_chimeras()
+    st["piles2"] = o.piles()
+    st["ov"] = o.overlap_list(0)
+    st["int"] = o.overlap_list(1)
+    o.build_graph()
+    st["nodes"] = o.nodes()
+    st["n_tr"] = o.remove_transitive_edges()
+    st["edges"] = o.edges()
+    _crafted[case.name] = st
+    return st
+
+
 def assert_same(name, a, b):
     a, b = np.asarray(a), np.asarray(b)
     assert a.shape == b.shape, "%s: shape %s vs %s" % (name, a.shape, b.shape)
@@ -57,12 +94,26 @@ def check_initialize(ctx, st, ds):
     op = st["piles0"]
     for k in ("alive", "begin", "end", "median", "p10"):
         assert_same("piles0." + k, hp[k], op[k])
+    pit_aux = None
     for kind, key in ((0, "pits0"), (1, "hills0")):
         offs, pairs, aux = ctx.intervals(kind)
         assert_same(key + ".offsets", offs, st[key][0])
         assert_same(key + ".pairs", pairs, st[key][1])
+        if kind == 0:
+            pit_aux = aux
     for r, want in st["data0"].items():
         assert_same("pile_data[%d]" % r, ctx.pile_data(r), want)
+    # the minimum the pile kernels record with every pit - the left side of `minimum * 1.84 <= component median` in
+    # break_pits_kernel - is the row's minimum over [first, second], both ends inclusive: the positions the lambda of
+    # Pile::break_over_chimeric_pits walks (reference pile.cpp:368-375); the kernels take the same range (pile_kernels.hip and
+    # pile_runs_kernel.hip, where a pit is published), so no other one has to be argued equivalent
+    offs, pairs = st["pits0"]
+    for r, want in st["data0"].items():
+        for k in range(int(offs[r]), int(offs[r + 1])):
+            first, second = int(pairs[k][0]), int(pairs[k][1])
+            low = int(want[first:second + 1].min())
+            assert int(pit_aux[k]) == low, "pit %d of read %d, [%d, %d]: recorded minimum %d, the row's is %d" % (
+                k - int(offs[r]), r, first, second, int(pit_aux[k]), low)
     # every row, hashed and summed where it lies (rala_hip_get_pile_row_digests) against the same vectors from the oracle's objects
     if "rows0" in st:
         fnv, inside, outside = ctx.pile_row_digests()
