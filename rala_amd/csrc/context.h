@@ -394,7 +394,7 @@ struct rala_hip_ctx {
     hipEvent_t ev_layout[2] = {};
     int64_t layout_fused_max = 1024;      // option: components of at most this many points run fused (0: none)
     rala_hip_layout_info layout_info = {};
-    // pinned staging of small device -> host reads (pipeline.hip: d2h_small / stream_sync)
+    // pinned staging of small device -> host reads (context.hip: d2h_small / stream_sync)
     struct StagedCopy { void* dst; size_t offset, bytes; };
     rala_hip::PinnedBuf<uint32_t> p_stage;
     std::vector<StagedCopy> stage_pending;

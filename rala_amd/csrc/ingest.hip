@@ -2,6 +2,7 @@
 // where the file is BGZF or one gzip member: ingest_bgzf.hip, ingest_gzip.hip), then count, scan, parse, and the columns
 // become the context's overlaps (rala_hip_set_overlaps, device memory).
 #include "ingest_common.h"
+#include "lifecycle.h"
 #include "name_table.h"
 
 using namespace rala_hip;
@@ -39,19 +40,19 @@ int tokenise_text(rala_hip_ctx* ctx, const uint8_t* text, uint64_t n, uint64_t n
     if (n_chunks) {
         launch_paf_count(text, n, first_is_start, ctx->d_paf_chunk[0].p, s);
         launch_exclusive_scan(ctx->d_paf_chunk[0].p, ctx->d_paf_chunk[1].p, n_chunks, ctx->d_scan_ws.p, s);
-        INGEST_CHECK(hipMemcpyAsync(&n_lines, ctx->d_paf_chunk[1].p + n_chunks, 4, hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipMemcpyAsync(&n_lines, ctx->d_paf_chunk[1].p + n_chunks, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
     }
     tc = now_ms();
-    if ((uint64_t)n_lines >= 0xFFFFFFF0ull / 2) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many overlaps for 32-bit bound offsets");
-    for (int k = 0; k < 7; ++k) INGEST_CHECK(T.col[k]->ensure((size_t)n_lines + 1 + extra_rows));
-    INGEST_CHECK(T.strand->ensure((size_t)n_lines + 1 + extra_rows));
+    if ((uint64_t)n_lines >= 0xFFFFFFF0ull / 2) return fail(ctx, RALA_HIP_ETOOLARGE, "too many overlaps for 32-bit bound offsets");
+    for (int k = 0; k < 7; ++k) HIPCHECK(T.col[k]->ensure((size_t)n_lines + 1 + extra_rows));
+    HIPCHECK(T.strand->ensure((size_t)n_lines + 1 + extra_rows));
     unsigned long long bad = ~0ull;
     uint32_t flags = 0;
     if (n_lines) {
         tp0 = now_ms();
-        INGEST_CHECK(hipMemsetAsync(ctx->d_paf_bad.p, 0xFF, 8, s));
-        INGEST_CHECK(hipMemsetAsync(ctx->d_paf_bad.p + 1, 0, 8, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_paf_bad.p, 0xFF, 8, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_paf_bad.p + 1, 0, 8, s));
         PafColumns cols;
         cols.a_id = T.col[0]->p; cols.b_id = T.col[1]->p; cols.a_begin = T.col[2]->p; cols.a_end = T.col[3]->p;
         cols.b_begin = T.col[4]->p; cols.b_end = T.col[5]->p; cols.length = T.col[6]->p; cols.strand = T.strand->p;
@@ -59,9 +60,9 @@ int tokenise_text(rala_hip_ctx* ctx, const uint8_t* text, uint64_t n, uint64_t n
                          (const char*)ctx->d_name_arena.p, ctx->d_read_len.p, (uint32_t)ctx->n_reads, check_lengths, cols,
                          (uint32_t*)(ctx->d_paf_bad.p + 1), ctx->d_paf_bad.p, s, T.mhap);
         unsigned long long back[2] = {0, 0};
-        INGEST_CHECK(hipMemcpyAsync(back, ctx->d_paf_bad.p, 16, hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
-        INGEST_CHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(back, ctx->d_paf_bad.p, 16, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipGetLastError());
         bad = back[0];
         flags = (uint32_t)back[1];
         tp1 = now_ms();
@@ -92,8 +93,8 @@ PafTarget paf_target(DevBuf<uint32_t>* col, DevBuf<uint8_t>* strand, bool mhap) 
 }
 
 int ingest_ready(rala_hip_ctx* ctx, bool mhap) {
-    if (ctx->n_reads == 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_name_buckets == 0 && !mhap) return ingest_fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
+    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
+    if (ctx->n_name_buckets == 0 && !mhap) return fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
     return RALA_HIP_OK;
 }
 
@@ -111,8 +112,8 @@ struct OverlapText {
 
 // the byte in front of text position lo (> 0): the file's for a plain file, else the one in front of `text` in device memory
 int byte_before(rala_hip_ctx* ctx, const OverlapText& X, const uint8_t* text, uint64_t lo, uint8_t* before) {
-    if (X.kind != kTextPlain) INGEST_CHECK(hipMemcpy(before, text - 1, 1, hipMemcpyDeviceToHost));
-    else if (pread(X.file.fd, before, 1, (off_t)(lo - 1)) != 1) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + X.path + " failed");
+    if (X.kind != kTextPlain) HIPCHECK(hipMemcpy(before, text - 1, 1, hipMemcpyDeviceToHost));
+    else if (pread(X.file.fd, before, 1, (off_t)(lo - 1)) != 1) return fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + X.path + " failed");
     return RALA_HIP_OK;
 }
 
@@ -127,7 +128,7 @@ int overlap_text_range(rala_hip_ctx* ctx, OverlapText& X, uint64_t lo, uint64_t 
         return rc != RALA_HIP_OK || out->flag || !lo ? rc : byte_before(ctx, X, out->text, lo, before);
     }
     if (X.kind == kTextGzip) {
-        if (!meanwhile()) return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
+        if (!meanwhile()) return fail(ctx, RALA_HIP_ENOMEM, room);
         out->text = ctx->d_gzip_text.p + lo;
         X.n_readers = X.gz.n_readers;
         const int rc = lo ? byte_before(ctx, X, out->text, lo, before) : RALA_HIP_OK;
@@ -137,12 +138,12 @@ int overlap_text_range(rala_hip_ctx* ctx, OverlapText& X, uint64_t lo, uint64_t 
     if (lo) { const int rc = byte_before(ctx, X, nullptr, lo, before); if (rc != RALA_HIP_OK) return rc; }
     hipStream_t s = ctx->stream;
     out->t0 = now_ms();
-    if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
-    INGEST_CHECK(hipMemsetAsync(ctx->d_paf_text.p + n_avail, '\n', cap - n_avail, s));
+    if (ctx->d_paf_text.ensure(cap) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+    HIPCHECK(hipMemsetAsync(ctx->d_paf_text.p + n_avail, '\n', cap - n_avail, s));
     const int shipped = ship_file(X.file.fd, lo, n_avail, ctx->d_paf_text.p, ctx->device, threads, nullptr, meanwhile, &X.n_readers);
-    if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
-    if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + X.path + " failed");
-    INGEST_CHECK(hipStreamSynchronize(s));
+    if (shipped == 2) return fail(ctx, RALA_HIP_ENOMEM, room);
+    if (shipped) return fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + X.path + " failed");
+    HIPCHECK(hipStreamSynchronize(s));
     out->text = ctx->d_paf_text.p;
     out->t_ship = out->t1 = now_ms();
     return RALA_HIP_OK;
@@ -160,7 +161,7 @@ int tokenise_range(rala_hip_ctx* ctx, OverlapText& X, uint64_t lo, uint64_t hi, 
     const uint64_t n_avail = std::min<uint64_t>(X.text_n - lo, n + paf_halo_bytes());
     const uint32_t chunk = paf_chunk_bytes();
     const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    if (n_chunks >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    if (n_chunks >= 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
     const uint64_t cap = n_chunks * chunk + 4096 + 64;
     TextArrival A;
     uint8_t before = '\n';
@@ -180,7 +181,7 @@ int rala_hip::paf_tokenise_range(rala_hip_ctx* ctx, const char* path, uint64_t l
     *out = PafRange();
     int rc = ingest_ready(ctx, T.mhap);
     if (rc != RALA_HIP_OK) return rc;
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     OverlapText X;
     X.path = path;
     rc = open_regular(ctx, path, X.file, &X.file_n);
@@ -198,7 +199,7 @@ int rala_hip::overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_
     piece[2] = 1;
     int rc = ingest_ready(ctx, T.mhap);
     if (rc != RALA_HIP_OK) return rc;
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     OverlapText X;
     X.path = path;
     rc = open_regular(ctx, path, X.file, &X.file_n);
@@ -273,11 +274,11 @@ extern "C" {
 
 int rala_hip_set_name_table(rala_hip_ctx* ctx, const void* buckets, uint64_t n_buckets, const char* arena, uint64_t arena_bytes) {
     if (!ctx || !buckets || n_buckets == 0 || (n_buckets & (n_buckets - 1)) != 0 || (!arena && arena_bytes)) return RALA_HIP_EINVAL;
-    INGEST_CHECK(hipSetDevice(ctx->device));
-    INGEST_CHECK(ctx->d_name_buckets.ensure(n_buckets * sizeof(NameBucket)));
-    INGEST_CHECK(ctx->d_name_arena.ensure(arena_bytes + 16));
-    INGEST_CHECK(hipMemcpy(ctx->d_name_buckets.p, buckets, n_buckets * sizeof(NameBucket), hipMemcpyHostToDevice));
-    if (arena_bytes) INGEST_CHECK(hipMemcpy(ctx->d_name_arena.p, arena, arena_bytes, hipMemcpyHostToDevice));
+    HIPCHECK(hipSetDevice(ctx->device));
+    HIPCHECK(ctx->d_name_buckets.ensure(n_buckets * sizeof(NameBucket)));
+    HIPCHECK(ctx->d_name_arena.ensure(arena_bytes + 16));
+    HIPCHECK(hipMemcpy(ctx->d_name_buckets.p, buckets, n_buckets * sizeof(NameBucket), hipMemcpyHostToDevice));
+    if (arena_bytes) HIPCHECK(hipMemcpy(ctx->d_name_arena.p, arena, arena_bytes, hipMemcpyHostToDevice));
     ctx->n_name_buckets = n_buckets;
     ctx->n_name_arena_bytes = arena_bytes;
     return RALA_HIP_OK;
@@ -290,10 +291,7 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
     *irregular = 0;
     // (the columns a successful call before this one left are about to be written over - whatever happens
     // here, the context has no overlaps until this call has set them)
-    ctx->inputs_set = false;
-    ctx->n_ovl = 0;
-    ctx->ovl = OvlSoA();
-    ctx->initialized = ctx->constructed = false;
+    inputs_withdrawn(ctx);
     const PafTarget T = paf_target(ctx->d_paf_col, &ctx->d_paf_strand, mhap);
     PafRange R;
     // The file's text goes through device memory in WINDOWS (round 5; before, all of it had to fit at once): at most a
@@ -302,7 +300,7 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
     // a window takes the lines that START in it).  One window - the usual case - tokenises straight into the columns.
     uint64_t window = (uint64_t)ctx->ingest_window_bytes;
     if (window == 0 && getenv("RALA_INGEST_WINDOW")) window = (uint64_t)atoll(getenv("RALA_INGEST_WINDOW"));      // (tests)
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     window = text_window_bytes(window);
     ctx->inflate_tm = rala_hip_inflate_timings();
     ctx->gzip_tm = rala_hip_gzip_timings();
@@ -366,13 +364,13 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
                 R.first_bad = (((part.first_bad >> 32) + rows) << 32) | (part.first_bad & 0xFFFFFFFFull);
                 break;
             }
-            if (rows + part.n_lines >= 0xFFFFFFF0ull / 2) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many overlaps for 32-bit bound offsets");
+            if (rows + part.n_lines >= 0xFFFFFFF0ull / 2) return fail(ctx, RALA_HIP_ETOOLARGE, "too many overlaps for 32-bit bound offsets");
             for (int k = 0; k < 7; ++k) {
-                if (ctx->d_paf_col[k].grow(rows, rows + part.n_lines + 1) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
-                if (part.n_lines) INGEST_CHECK(hipMemcpy(ctx->d_paf_col[k].p + rows, ctx->d_paf_win[k].p, part.n_lines * 4, hipMemcpyDeviceToDevice));
+                if (ctx->d_paf_col[k].grow(rows, rows + part.n_lines + 1) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+                if (part.n_lines) HIPCHECK(hipMemcpy(ctx->d_paf_col[k].p + rows, ctx->d_paf_win[k].p, part.n_lines * 4, hipMemcpyDeviceToDevice));
             }
-            if (ctx->d_paf_strand.grow(rows, rows + part.n_lines + 1) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
-            if (part.n_lines) INGEST_CHECK(hipMemcpy(ctx->d_paf_strand.p + rows, ctx->d_paf_win_strand.p, part.n_lines, hipMemcpyDeviceToDevice));
+            if (ctx->d_paf_strand.grow(rows, rows + part.n_lines + 1) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the overlap columns");
+            if (part.n_lines) HIPCHECK(hipMemcpy(ctx->d_paf_strand.p + rows, ctx->d_paf_win_strand.p, part.n_lines, hipMemcpyDeviceToDevice));
             rows += part.n_lines;
         }
         R.n_lines = rows;
@@ -464,16 +462,16 @@ int rala_hip_tokenise_sensitive(rala_hip_ctx* ctx, const char* path, int format,
 
 int rala_hip_get_overlap_columns(rala_hip_ctx* ctx, uint64_t* n, uint32_t* const cols[7], uint8_t* strand) {
     if (!ctx || !n) return RALA_HIP_EINVAL;
-    if (!ctx->inputs_set || ctx->tuple_mode) return ingest_fail(ctx, RALA_HIP_EINVAL, "no overlaps set");
+    if (!ctx->inputs_set || ctx->tuple_mode) return fail(ctx, RALA_HIP_EINVAL, "no overlaps set");
     *n = ctx->n_ovl;
     if (!cols && !strand) return RALA_HIP_OK;
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     { const int rcu = rala_hip::flush_upload(ctx); if (rcu != RALA_HIP_OK) return rcu; }
     const uint32_t* src[7] = {ctx->ovl.a_id, ctx->ovl.b_id, ctx->ovl.a_begin, ctx->ovl.a_end, ctx->ovl.b_begin, ctx->ovl.b_end, ctx->ovl.length};
     for (int k = 0; cols && k < 7; ++k) {
-        if (cols[k] && ctx->n_ovl) INGEST_CHECK(hipMemcpy(cols[k], src[k], ctx->n_ovl * 4, hipMemcpyDeviceToHost));
+        if (cols[k] && ctx->n_ovl) HIPCHECK(hipMemcpy(cols[k], src[k], ctx->n_ovl * 4, hipMemcpyDeviceToHost));
     }
-    if (strand && ctx->n_ovl) INGEST_CHECK(hipMemcpy(strand, ctx->ovl.strand, ctx->n_ovl, hipMemcpyDeviceToHost));
+    if (strand && ctx->n_ovl) HIPCHECK(hipMemcpy(strand, ctx->ovl.strand, ctx->n_ovl, hipMemcpyDeviceToHost));
     return RALA_HIP_OK;
 }
 

@@ -15,7 +15,7 @@ int rala_hip::ingest::bgzf_open(rala_hip_ctx* ctx, int fd, uint64_t file_n, cons
     if (file_n < 18) return RALA_HIP_OK;
     const double t0 = now_ms();
     f.resident = file_n <= window;
-    if (f.resident && ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    if (f.resident && ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
     const uint64_t n_blocks = (file_n + kBlockBytes - 1) / kBlockBytes;
     std::vector<std::vector<BgzfCand>> cand(n_blocks);
     std::atomic<int> edge_failed(0);
@@ -39,9 +39,9 @@ int rala_hip::ingest::bgzf_open(rala_hip_ctx* ctx, int fd, uint64_t file_n, cons
     };
     const int shipped = ship_file(fd, 0, file_n, f.resident ? ctx->d_bgzf_comp.p : nullptr, ctx->device, threads, &scan,
                                   []() { return true; }, &f.n_readers);
-    if (shipped || edge_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+    if (shipped || edge_failed) return fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
     uint8_t tail[4];
-    if (pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
+    if (pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return fail(ctx, RALA_HIP_EDEVICE, std::string("reading ") + path + " failed");
     std::vector<BgzfMember> members;
     if (!bgzf_walk(cand, file_n, le32(tail), members)) return RALA_HIP_OK;
     f.n_members = members.size();
@@ -71,7 +71,7 @@ int rala_hip::ingest::bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n
     const double t0 = now_ms();
     const uint64_t len = hi - lo;
     // (room for the member across hi and a usual halo's members at once; more is made below where they need more)
-    if (ctx->d_bgzf_comp.ensure(len + 4 * 65536 + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    if (ctx->d_bgzf_comp.ensure(len + 4 * 65536 + 64) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
     const std::string read_failed = std::string("reading / copying ") + path + " failed";
     const uint64_t n_blocks = (len + kBlockBytes - 1) / kBlockBytes;
     std::vector<std::vector<BgzfCand>> cand(n_blocks);
@@ -94,9 +94,9 @@ int rala_hip::ingest::bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n
         bgzf_scan(bytes, n, off, file_n, at, cand[b]);
     };
     const int shipped = ship_file(fd, lo, len, ctx->d_bgzf_comp.p, ctx->device, threads, &scan, []() { return true; }, &f.n_readers);
-    if (shipped || edge_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+    if (shipped || edge_failed) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
     uint8_t tail[4] = {0, 0, 0, 0};
-    if (file_n >= 4 && pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+    if (file_n >= 4 && pread(fd, tail, 4, (off_t)(file_n - 4)) != 4) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
     // the candidate at an offset behind the range: the 4 bytes in front of it, its fixed part, then its extra field
     bool io_failed = false;
     auto next = [&](uint64_t o, BgzfCand* c) {
@@ -114,7 +114,7 @@ int rala_hip::ingest::bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n
     };
     std::vector<BgzfMember> members;
     const bool chained = bgzf_walk_range(cand, lo, hi, file_n, le32(tail), next, members, piece);
-    if (io_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+    if (io_failed) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
     if (!chained) return RALA_HIP_OK;
     f.n_members = members.size();
     if (piece->empty) { *valid = true; return RALA_HIP_OK; }
@@ -128,10 +128,10 @@ int rala_hip::ingest::bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n
         BgzfCand c;
         uint8_t isize[4];
         if (!next(o, &c) || c.bsize == 0 || o + c.bsize > file_n) {
-            if (io_failed) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+            if (io_failed) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
             return RALA_HIP_OK;
         }
-        if (pread(fd, isize, 4, (off_t)(o + c.bsize - 4)) != 4) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+        if (pread(fd, isize, 4, (off_t)(o + c.bsize - 4)) != 4) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
         BgzfMember m;
         m.off = o; m.bsize = c.bsize; m.hdr = c.hdr; m.isize = le32(isize); m.text_off = text;
         if (m.isize > 65536) return RALA_HIP_OK;
@@ -145,11 +145,11 @@ int rala_hip::ingest::bgzf_open_piece(rala_hip_ctx* ctx, int fd, uint64_t file_n
         std::vector<uint8_t> rest(o - hi);
         for (uint64_t got = 0; got < rest.size();) {
             const ssize_t r = pread(fd, rest.data() + got, rest.size() - got, (off_t)(hi + got));
-            if (r <= 0) return ingest_fail(ctx, RALA_HIP_EDEVICE, read_failed);
+            if (r <= 0) return fail(ctx, RALA_HIP_EDEVICE, read_failed);
             got += (uint64_t)r;
         }
-        if (ctx->d_bgzf_comp.grow(len, o - lo + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
-        INGEST_CHECK(hipMemcpy(ctx->d_bgzf_comp.p + len, rest.data(), rest.size(), hipMemcpyHostToDevice));
+        if (ctx->d_bgzf_comp.grow(len, o - lo + 64) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        HIPCHECK(hipMemcpy(ctx->d_bgzf_comp.p + len, rest.data(), rest.size(), hipMemcpyHostToDevice));
     }
     for (const BgzfMember& m : members) if (m.isize) f.jobs.push_back(m);
     f.text_n = text;
@@ -175,18 +175,18 @@ int rala_hip::ingest::bgzf_text_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t l
     const uint64_t extent = j1 > j0 ? f.jobs[j1 - 1].text_off + f.jobs[j1 - 1].isize - base : 0;
     const uint64_t size = std::max(shift + cap, extent) + 64;
     out->t0 = now_ms();
-    if (ctx->d_paf_text.ensure(size) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+    if (ctx->d_paf_text.ensure(size) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
     uint64_t comp_base = 0;
     if (!f.resident && j1 > j0) {
         comp_base = f.jobs[j0].off;
         const uint64_t c_len = f.jobs[j1 - 1].off + f.jobs[j1 - 1].bsize - comp_base;
-        if (ctx->d_bgzf_comp.ensure(c_len + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        if (ctx->d_bgzf_comp.ensure(c_len + 64) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
         const int shipped = ship_file(f.fd, comp_base, c_len, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, meanwhile, &f.n_readers);
-        if (shipped == 2) return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
-        if (shipped) return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying the compressed file failed");
+        if (shipped == 2) return fail(ctx, RALA_HIP_ENOMEM, room);
+        if (shipped) return fail(ctx, RALA_HIP_EDEVICE, "reading / copying the compressed file failed");
         f.shipped += c_len;
     } else if (!meanwhile()) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, room);
+        return fail(ctx, RALA_HIP_ENOMEM, room);
     }
     out->t_ship = now_ms();
     std::vector<BgzfJob> jobs(j1 - j0);
@@ -200,17 +200,17 @@ int rala_hip::ingest::bgzf_text_range(rala_hip_ctx* ctx, BgzfFile& f, uint64_t l
     }
     uint32_t flag = 0;
     if (!jobs.empty()) {
-        INGEST_CHECK(ctx->d_bgzf_jobs.ensure(jobs.size() * sizeof(BgzfJob)));
-        INGEST_CHECK(ctx->d_bgzf_flag.ensure(1));
-        INGEST_CHECK(hipMemcpyAsync(ctx->d_bgzf_jobs.p, jobs.data(), jobs.size() * sizeof(BgzfJob), hipMemcpyHostToDevice, s));
-        INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+        HIPCHECK(ctx->d_bgzf_jobs.ensure(jobs.size() * sizeof(BgzfJob)));
+        HIPCHECK(ctx->d_bgzf_flag.ensure(1));
+        HIPCHECK(hipMemcpyAsync(ctx->d_bgzf_jobs.p, jobs.data(), jobs.size() * sizeof(BgzfJob), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
         launch_bgzf_inflate(ctx->d_bgzf_comp.p, (const BgzfJob*)ctx->d_bgzf_jobs.p, (uint32_t)jobs.size(), ctx->d_paf_text.p, size, ctx->d_bgzf_flag.p, s);
-        INGEST_CHECK(hipGetLastError());
-        INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
     }
     uint8_t* const text = ctx->d_paf_text.p + shift;
-    INGEST_CHECK(hipMemsetAsync(text + n_avail, pad, cap - n_avail, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipMemsetAsync(text + n_avail, pad, cap - n_avail, s));
+    HIPCHECK(hipStreamSynchronize(s));
     out->t1 = now_ms();
     f.inflate_ms += (float)(out->t1 - out->t_ship);
     if (flag) ctx->d_paf_text.release();

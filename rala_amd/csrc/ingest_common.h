@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "ctx_check.h"
 #include "ingest_formats.h"
 #include "kernels.h"
 #include "stages.h"
@@ -22,20 +23,6 @@ namespace rala_hip {
 namespace ingest {
 
 constexpr size_t kBlockBytes = 32u << 20;       // one staging block
-
-inline int ingest_fail(rala_hip_ctx* ctx, int code, const std::string& msg) {
-    ctx->err = msg;
-    return code;
-}
-
-#define INGEST_CHECK(call)                                                                                  \
-    do {                                                                                                    \
-        const hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                             \
-            return ingest_fail(ctx, e_ == hipErrorOutOfMemory ? RALA_HIP_ENOMEM : RALA_HIP_EDEVICE,         \
-                               std::string(#call) + ": " + hipGetErrorString(e_));                          \
-        }                                                                                                   \
-    } while (0)
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -49,9 +36,9 @@ struct Fd {                                         // (closed on every way out 
 // the file opened for reading, its size; what is no regular file (a directory; a FIFO, its writer not waited for) is refused
 inline int open_regular(rala_hip_ctx* ctx, const char* path, Fd& file, uint64_t* size) {
     file.fd = open(path, O_RDONLY | O_NONBLOCK);
-    if (file.fd < 0) return ingest_fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+    if (file.fd < 0) return fail(ctx, RALA_HIP_EINVAL, std::string("cannot open ") + path);
     struct stat st;
-    if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return ingest_fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+    if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
     *size = (uint64_t)st.st_size;
     return RALA_HIP_OK;
 }

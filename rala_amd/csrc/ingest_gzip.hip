@@ -18,22 +18,22 @@ int gzip_member_find(rala_hip_ctx* ctx, const uint8_t* comp, uint64_t n, uint64_
     *n_cands = 0;
     const uint64_t n_tiles = (n + gzip_member_tile_bytes() - 1) / gzip_member_tile_bytes();
     if (!n_tiles) return RALA_HIP_OK;
-    if (n_tiles >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit tile ids");
+    if (n_tiles >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit tile ids");
     if (ctx->d_gzip_tile.ensure(n_tiles + 2) != hipSuccess || ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
     }
     launch_gzip_member_count(comp, n, ctx->d_gzip_tile.p, s);
     launch_exclusive_scan(ctx->d_gzip_tile.p, ctx->d_gzip_tile.p, n_tiles, ctx->d_scan_ws.p, s);
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     uint32_t total = 0;
-    INGEST_CHECK(hipMemcpyAsync(&total, ctx->d_gzip_tile.p + n_tiles, 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipMemcpyAsync(&total, ctx->d_gzip_tile.p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
     if (ctx->d_gzip_cands.ensure(((size_t)total + 1) * sizeof(GzipMemberCand)) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the member find");
     }
     launch_gzip_member_write(comp, n, ctx->d_gzip_tile.p, (GzipMemberCand*)ctx->d_gzip_cands.p, s);
-    INGEST_CHECK(hipGetLastError());
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
     *n_cands = total;
     return RALA_HIP_OK;
 }
@@ -65,19 +65,19 @@ int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t thread
     g.crc = le32(trailer);
     const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, ctx->gzip_chunk_bytes);
     const uint64_t n_chunks = (end - deflate_off + chunk - 1) / chunk;
-    if (!given && n_chunks >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+    if (!given && n_chunks >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
     hipStream_t s = ctx->stream;
     const double t0 = now_ms();
     if (ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess || ctx->d_bgzf_flag.ensure(1) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
     }
     const uint8_t* comp = ctx->d_bgzf_comp.p;
-    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
-    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
     if (ship_file(fd, 0, file_n, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, []() { return true; }, &g.n_readers)) {
-        return ingest_fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
+        return fail(ctx, RALA_HIP_EDEVICE, std::string("reading / copying ") + path + " failed");
     }
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipStreamSynchronize(s));
     const double t1 = now_ms();
     g.ship_ms = (float)(t1 - t0);
     rala_hip_gzip_timings& tm = g.tm;
@@ -108,32 +108,32 @@ int gzip_chain_open(rala_hip_ctx* ctx, int fd, const char* path, uint32_t thread
     if (members) {
         const int rc = gzip_member_find(ctx, comp, file_n, &n_cands);
         if (rc != RALA_HIP_OK) return rc;
-        if (n_chunks + n_cands >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many member candidates for 32-bit span ids");
+        if (n_chunks + n_cands >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "too many member candidates for 32-bit span ids");
     }
     const double t1b = now_ms();
     g.n_cands = n_cands;
     g.member_find_ms = (float)(t1b - t1);
     if (ctx->d_gzip_starts.ensure(n_chunks) != hipSuccess || ctx->d_gzip_spans.ensure(n_chunks * sizeof(GzipSpan)) != hipSuccess ||
         ctx->d_gzip_mspans.ensure((n_cands + 1) * sizeof(GzipSpan)) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
     }
     launch_gzip_find(comp, end, (file_n + 56) / 8, deflate_off, chunk, (uint32_t)n_chunks, ctx->debug_gzip_false_sync, ctx->d_gzip_starts.p, s);
-    INGEST_CHECK(hipGetLastError());
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
     const double t2 = now_ms();
     launch_gzip_count(comp, end, ctx->d_gzip_starts.p, (uint32_t)n_chunks, (GzipSpan*)ctx->d_gzip_spans.p, s, (const GzipMemberCand*)ctx->d_gzip_cands.p,
                       (uint32_t)n_cands, deflate_off, chunk, (GzipSpan*)ctx->d_gzip_mspans.p);
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     std::vector<uint64_t> starts(n_chunks);
     std::vector<GzipSpan> spans(n_chunks), mspans(n_cands);
     std::vector<GzipMemberCand> cands(n_cands);
-    INGEST_CHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(starts.data(), ctx->d_gzip_starts.p, n_chunks * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(spans.data(), ctx->d_gzip_spans.p, n_chunks * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
     if (n_cands) {
-        INGEST_CHECK(hipMemcpyAsync(cands.data(), ctx->d_gzip_cands.p, n_cands * sizeof(GzipMemberCand), hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipMemcpyAsync(mspans.data(), ctx->d_gzip_mspans.p, n_cands * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(cands.data(), ctx->d_gzip_cands.p, n_cands * sizeof(GzipMemberCand), hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(mspans.data(), ctx->d_gzip_mspans.p, n_cands * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
     }
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipStreamSynchronize(s));
     const double t3 = now_ms();
     ctx->d_gzip_starts.release();
     ctx->d_gzip_spans.release();
@@ -183,15 +183,15 @@ int gzip_prove_members(rala_hip_ctx* ctx, GzipStream& g, const uint8_t* text, ui
     }
     std::vector<uint32_t> piece_crc(pieces.size());
     if (!pieces.empty()) {
-        if (pieces.size() >= 0x7FFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "too many member boundaries in one window");
+        if (pieces.size() >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "too many member boundaries in one window");
         if (ctx->d_gzip_pieces.ensure(pieces.size() * sizeof(GzipPiece)) != hipSuccess || ctx->d_gzip_piece_crc.ensure(pieces.size()) != hipSuccess) {
-            return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the members' pieces");
+            return fail(ctx, RALA_HIP_ENOMEM, "device memory for the members' pieces");
         }
-        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_pieces.p, pieces.data(), pieces.size() * sizeof(GzipPiece), hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemcpyAsync(ctx->d_gzip_pieces.p, pieces.data(), pieces.size() * sizeof(GzipPiece), hipMemcpyHostToDevice, s));
         launch_gzip_piece_crc(text, (const GzipPiece*)ctx->d_gzip_pieces.p, (uint32_t)pieces.size(), ctx->d_gzip_piece_crc.p, s);
-        INGEST_CHECK(hipGetLastError());
-        INGEST_CHECK(hipMemcpyAsync(piece_crc.data(), ctx->d_gzip_piece_crc.p, pieces.size() * 4, hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(piece_crc.data(), ctx->d_gzip_piece_crc.p, pieces.size() * 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
     }
     for (const Item& it : items) {
         if (it.kind == 2) {
@@ -226,31 +226,31 @@ int rala_hip::ingest::gzip_inflate(rala_hip_ctx* ctx, int fd, const char* path, 
     std::vector<uint64_t> text_off(n_jobs);
     for (size_t j = 0; j < n_jobs; ++j) text_off[j] = g.chain[j].text_off;
     const uint64_t n_seg = (text_n + gzip_segment_bytes() - 1) / gzip_segment_bytes();
-    if (n_seg >= 0xFFFFFFF0ull) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
+    if (n_seg >= 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
     if (ctx->d_gzip_sym.ensure(text_n + 64) != hipSuccess || ctx->d_gzip_text.ensure(text_n + paf_chunk_bytes() + 8192) != hipSuccess ||
         ctx->d_gzip_jobs.ensure(n_jobs * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(n_jobs) != hipSuccess ||
         ctx->d_gzip_floor.ensure(n_jobs) != hipSuccess || ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the inflated text");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the inflated text");
     }
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, g.chain.data(), n_jobs * sizeof(GzipJob), hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, g.job_floor.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, g.chain.data(), n_jobs * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, g.job_floor.data(), n_jobs * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipStreamSynchronize(s));
     const double t3 = now_ms();
     launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)n_jobs, ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
-    INGEST_CHECK(hipGetLastError());
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
     const double t4 = now_ms();
     launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, (uint32_t)n_jobs, text_n, ctx->d_gzip_text.p, ctx->d_gzip_crc.p,
                         ctx->d_bgzf_flag.p, s);
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     // what lies behind the text reads as newlines (as for the plain file)
-    INGEST_CHECK(hipMemsetAsync(ctx->d_gzip_text.p + text_n, '\n', paf_chunk_bytes() + 8192, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_gzip_text.p + text_n, '\n', paf_chunk_bytes() + 8192, s));
     std::vector<uint32_t> seg_crc(n_seg);
     uint32_t flag = 0;
-    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
+    if (n_seg) HIPCHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(&flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
     if (!flag) { const int rcp = gzip_prove_members(ctx, g, ctx->d_gzip_text.p, 0, text_n, seg_crc); if (rcp != RALA_HIP_OK) return rcp; }
     const double t5 = now_ms();
     ctx->d_gzip_sym.release();
@@ -286,17 +286,17 @@ int rala_hip::ingest::gzip_walk_open(rala_hip_ctx* ctx, int fd, const char* path
         window = std::max<uint64_t>(64ull << 20, free_b / 12);
     }
     window = std::max<uint64_t>(std::min<uint64_t>(window, 1ull << 31), g.tm.max_wave_text_bytes);
-    if (window > (1ull << 31)) return ingest_fail(ctx, RALA_HIP_ENOMEM, "a chunk of the gzip file gives more text than a window holds");
+    if (window > (1ull << 31)) return fail(ctx, RALA_HIP_ENOMEM, "a chunk of the gzip file gives more text than a window holds");
     window = std::min(window, std::max<uint64_t>(g.text_n, 1));
     g.window = window;
     const uint64_t ring = gzip_ring_symbols();
     if (ctx->d_gzip_sym.ensure(ring + window + 64) != hipSuccess || ctx->d_gzip_text.ensure(front + window + behind) != hipSuccess ||
         ctx->d_gzip_crc.ensure(window / gzip_segment_bytes() + 2) != hipSuccess || ctx->d_gzip_carry.ensure(ring) != hipSuccess ||
         ctx->d_gzip_hold.ensure(front + 16) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
     }
     // nothing lies in front of the first window: a marker that points there is no byte
-    INGEST_CHECK(hipMemsetD16Async((hipDeviceptr_t)ctx->d_gzip_sym.p, (unsigned short)0x8000u, ring, s));
+    HIPCHECK(hipMemsetD16Async((hipDeviceptr_t)ctx->d_gzip_sym.p, (unsigned short)0x8000u, ring, s));
     *valid = true;
     return RALA_HIP_OK;
 }
@@ -318,33 +318,33 @@ int rala_hip::ingest::gzip_walk_next(rala_hip_ctx* ctx, GzipWalk& g, uint8_t* te
         const uint64_t f = g.job_floor[j0 + j];
         floors[j] = f + ring >= a ? f + ring - a : 0;
     }
-    if (n_w > g.window) return ingest_fail(ctx, RALA_HIP_EDEVICE, "a chunk larger than the window");
+    if (n_w > g.window) return fail(ctx, RALA_HIP_EDEVICE, "a chunk larger than the window");
     *lo = a;
     *n = n_w;
     *flag = 0;
     g.next_job = j1;
     if (ctx->d_gzip_jobs.ensure(jobs.size() * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(jobs.size()) != hipSuccess ||
         ctx->d_gzip_floor.ensure(jobs.size()) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's chunks");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's chunks");
     }
     const double t0 = now_ms();
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, floors.data(), floors.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, floors.data(), floors.size() * 8, hipMemcpyHostToDevice, s));
     launch_gzip_write(ctx->d_bgzf_comp.p, g.end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
-    INGEST_CHECK(hipGetLastError());
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
     const double t1 = now_ms();
     const uint64_t n_seg = (n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
     launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, (uint32_t)jobs.size(), n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p,
                         s, ring);
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     std::vector<uint32_t> seg_crc(n_seg);
-    if (n_seg) INGEST_CHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipMemcpyAsync(flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    if (n_seg) HIPCHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
     if (j1 < g.chain.size()) launch_gzip_carry(ctx->d_gzip_sym.p, text, n_w, ctx->d_gzip_carry.p, s);
-    INGEST_CHECK(hipGetLastError());
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
     if (!*flag) { const int rc = gzip_prove_members(ctx, g, text, a, n_w, seg_crc); if (rc != RALA_HIP_OK) return rc; }
     g.tm.decode_ms += (float)(t1 - t0);
     g.tm.resolve_ms += (float)(now_ms() - t1);
@@ -453,22 +453,22 @@ int rala_hip_gzip_find_members(rala_hip_ctx* ctx, const uint8_t* bytes, uint64_t
                                uint64_t* deflate_off) {
     if (!ctx || !n_found || (!bytes && n)) return RALA_HIP_EINVAL;
     *n_found = 0;
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (ctx->d_bgzf_comp.ensure(n + 64) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the bytes");
+    if (ctx->d_bgzf_comp.ensure(n + 64) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the bytes");
     struct Release {
         rala_hip_ctx* ctx;
         ~Release() { ctx->d_bgzf_comp.release(); ctx->d_gzip_cands.release(); ctx->d_gzip_tile.release(); }
     } release{ctx};
-    if (n) INGEST_CHECK(hipMemcpyAsync(ctx->d_bgzf_comp.p, bytes, n, hipMemcpyHostToDevice, s));
-    INGEST_CHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + n, 0, 64, s));
+    if (n) HIPCHECK(hipMemcpyAsync(ctx->d_bgzf_comp.p, bytes, n, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + n, 0, 64, s));
     uint64_t found = 0;
     const int rc = gzip_member_find(ctx, ctx->d_bgzf_comp.p, n, &found);
     if (rc != RALA_HIP_OK) return rc;
     *n_found = found;
     if (!found || cap < found) return RALA_HIP_OK;
     std::vector<GzipMemberCand> cands(found);
-    INGEST_CHECK(hipMemcpy(cands.data(), ctx->d_gzip_cands.p, found * sizeof(GzipMemberCand), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(cands.data(), ctx->d_gzip_cands.p, found * sizeof(GzipMemberCand), hipMemcpyDeviceToHost));
     for (uint64_t k = 0; k < found; ++k) {
         if (header_off) header_off[k] = cands[k].header_off;
         if (deflate_off) deflate_off[k] = cands[k].deflate_bit / 8;

@@ -23,20 +23,20 @@ int index_window(rala_hip_ctx* ctx, SequenceRun& R, const uint8_t* text, uint64_
     const uint64_t n_tiles = (n + sequence_tile_bytes() - 1) / sequence_tile_bytes();
     *flags = 0;
     if (!n_tiles) return RALA_HIP_OK;
-    INGEST_CHECK(ctx->d_seq_tile[0].ensure(n_tiles + 2));
-    INGEST_CHECK(ctx->d_seq_tile[1].ensure(n_tiles + 2));
-    INGEST_CHECK(ctx->d_seq_flags.ensure(1));
-    INGEST_CHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)));
+    HIPCHECK(ctx->d_seq_tile[0].ensure(n_tiles + 2));
+    HIPCHECK(ctx->d_seq_tile[1].ensure(n_tiles + 2));
+    HIPCHECK(ctx->d_seq_flags.ensure(1));
+    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)));
     launch_sequence_count(text, n, R.last_is_newline, R.fastq, ctx->d_seq_tile[0].p, ctx->d_seq_tile[1].p, s);
     launch_exclusive_scan(ctx->d_seq_tile[0].p, ctx->d_seq_tile[0].p, n_tiles, ctx->d_scan_ws.p, s);
     launch_exclusive_scan(ctx->d_seq_tile[1].p, ctx->d_seq_tile[1].p, n_tiles, ctx->d_scan_ws.p, s);
     uint32_t events = 0, stripped = 0;
     uint8_t last = 0;
-    INGEST_CHECK(hipMemcpyAsync(&events, ctx->d_seq_tile[0].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipMemcpyAsync(&stripped, ctx->d_seq_tile[1].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipMemcpyAsync(&last, text + n - 1, 1, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(&events, ctx->d_seq_tile[0].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(&stripped, ctx->d_seq_tile[1].p + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(&last, text + n - 1, 1, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipGetLastError());
     // (a FASTQ record is four events; one whose lines are spread over two windows is counted where its header lies)
     const uint64_t ev_after = R.n_events + events;
     const uint64_t rec_before = R.n_records, rec_after = R.fastq ? (ev_after + 3) / 4 : ev_after;
@@ -44,9 +44,9 @@ int index_window(rala_hip_ctx* ctx, SequenceRun& R, const uint8_t* text, uint64_
         ctx->d_seq_name_pos.grow(rec_before, rec_after + 1) != hipSuccess || ctx->d_seq_name_len.grow(rec_before, rec_after + 1) != hipSuccess ||
         ctx->d_seq_data_off.grow(rec_before, rec_after + 1) != hipSuccess || ctx->d_seq_data_stripped.grow(rec_before, rec_after + 1) != hipSuccess ||
         ctx->d_seq_name_off.grow(rec_before, rec_after + 1) != hipSuccess) {
-        return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
     }
-    INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
     SequenceWindow W;
     W.text = text; W.n = n; W.n_avail = n_avail; W.text_off = lo; W.text_n = R.text_n;
     W.first_is_start = R.last_is_newline ? 1u : 0u;
@@ -57,26 +57,26 @@ int index_window(rala_hip_ctx* ctx, SequenceRun& R, const uint8_t* text, uint64_
     C.name_pos = ctx->d_seq_name_pos.p; C.name_len = ctx->d_seq_name_len.p;
     C.data_off = ctx->d_seq_data_off.p; C.data_stripped = ctx->d_seq_data_stripped.p;
     launch_sequence_records(W, R.fastq, C, ctx->d_seq_flags.p, s);
-    INGEST_CHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     // the headers of this window: FASTA - every event; FASTQ - the events 4r
     const uint64_t hdr_before = R.fastq ? (R.n_events + 3) / 4 : R.n_events;
     const uint64_t n_hdr = rec_after - hdr_before;
     uint32_t bytes = 0;
     if (n_hdr) {
-        INGEST_CHECK(ctx->d_seq_name_at.ensure(n_hdr + 2));
-        INGEST_CHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_hdr + 2)));
+        HIPCHECK(ctx->d_seq_name_at.ensure(n_hdr + 2));
+        HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(n_hdr + 2)));
         launch_exclusive_scan(ctx->d_seq_name_len.p + hdr_before, ctx->d_seq_name_at.p, n_hdr, ctx->d_scan_ws.p, s);
-        INGEST_CHECK(hipMemcpyAsync(&bytes, ctx->d_seq_name_at.p + n_hdr, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(&bytes, ctx->d_seq_name_at.p + n_hdr, 4, hipMemcpyDeviceToHost, s));
     }
-    INGEST_CHECK(hipMemcpyAsync(flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
-    INGEST_CHECK(hipStreamSynchronize(s));
+    HIPCHECK(hipMemcpyAsync(flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
     if (*flags) return RALA_HIP_OK;
     if (n_hdr) {
-        if (ctx->d_seq_arena.grow(R.name_bytes, R.name_bytes + bytes + 1) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the names");
+        if (ctx->d_seq_arena.grow(R.name_bytes, R.name_bytes + bytes + 1) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the names");
         launch_sequence_names(text, lo, ctx->d_seq_name_pos.p + hdr_before, ctx->d_seq_name_len.p + hdr_before, ctx->d_seq_name_at.p, n_hdr,
                               R.name_bytes, ctx->d_seq_arena.p, ctx->d_seq_name_off.p + hdr_before, s);
-        INGEST_CHECK(hipGetLastError());
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(s));
     }
     R.n_events = ev_after;
     R.n_stripped += stripped;
@@ -152,7 +152,7 @@ int source_next(rala_hip_ctx* ctx, TextSource& S, TextWindow* w) {
         uint64_t a = 0, n_w = 0;
         const int rc = gzip_walk_next(ctx, *S.gz, at, &a, &n_w, &S.flag);
         if (rc != RALA_HIP_OK || S.flag) return rc;
-        if (a != S.lo + S.hold) return ingest_fail(ctx, RALA_HIP_EDEVICE, "the gzip windows do not follow each other");
+        if (a != S.lo + S.hold) return fail(ctx, RALA_HIP_EDEVICE, "the gzip windows do not follow each other");
         uint8_t* text = at - S.hold;
         w->n_avail = S.hold + n_w;
         const bool last = a + n_w == S.text_n;
@@ -162,12 +162,12 @@ int source_next(rala_hip_ctx* ctx, TextSource& S, TextWindow* w) {
         // them is held back, any number of bytes, and the text in front of `at` does not begin at a multiple of 16, where
         // the index's and the slicer's kernels load it 16 bytes at a time.  Such a window goes to a buffer of its own.
         if (S.hold % 16) {
-            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
-            INGEST_CHECK(hipMemcpyAsync(ctx->d_paf_text.p, text, w->n_avail, hipMemcpyDeviceToDevice, s));
+            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for a window of the inflated text");
+            HIPCHECK(hipMemcpyAsync(ctx->d_paf_text.p, text, w->n_avail, hipMemcpyDeviceToDevice, s));
             text = ctx->d_paf_text.p;
         }
-        INGEST_CHECK(hipMemsetAsync(text + w->n_avail, 0, cap - w->n_avail, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipMemsetAsync(text + w->n_avail, 0, cap - w->n_avail, s));
+        HIPCHECK(hipStreamSynchronize(s));
         w->text = text;
         w->t_kernels = t0;
     } else {
@@ -184,11 +184,11 @@ int source_next(rala_hip_ctx* ctx, TextSource& S, TextWindow* w) {
             w->t_kernels = bt.t1;
             S.ship_ms += bt.t_ship - bt.t0;
         } else {
-            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
+            if (ctx->d_paf_text.ensure(cap) != hipSuccess) return fail(ctx, RALA_HIP_ENOMEM, "device memory for the file's text");
             if (hipMemsetAsync(ctx->d_paf_text.p + w->n_avail, 0, cap - w->n_avail, s) != hipSuccess ||
                 ship_file(S.fd, S.lo, w->n_avail, ctx->d_paf_text.p, ctx->device, S.threads, nullptr, []() { return true; }, nullptr) ||
                 hipStreamSynchronize(s) != hipSuccess) {
-                return ingest_fail(ctx, RALA_HIP_EDEVICE, "reading / copying " + S.path + " failed");
+                return fail(ctx, RALA_HIP_EDEVICE, "reading / copying " + S.path + " failed");
             }
             w->text = ctx->d_paf_text.p;
             w->t_kernels = now_ms();
@@ -207,9 +207,9 @@ int source_advance(rala_hip_ctx* ctx, TextSource& S, const TextWindow& w) {
     S.hold = w.n_avail - w.n;
     if (S.hold && S.lo < S.text_n) {
         hipStream_t s = ctx->stream;
-        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_hold.p, w.text + w.n, S.hold, hipMemcpyDeviceToDevice, s));
-        INGEST_CHECK(hipMemcpyAsync(ctx->d_gzip_text.p + S.front - S.hold, ctx->d_gzip_hold.p, S.hold, hipMemcpyDeviceToDevice, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipMemcpyAsync(ctx->d_gzip_hold.p, w.text + w.n, S.hold, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(hipMemcpyAsync(ctx->d_gzip_text.p + S.front - S.hold, ctx->d_gzip_hold.p, S.hold, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(hipStreamSynchronize(s));
     }
     return RALA_HIP_OK;
 }
@@ -234,7 +234,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     ctx->n_seq_records = ctx->n_seq_name_bytes = 0;
     ctx->seq_tm = rala_hip_ingest_timings();
     ctx->gzip_members_last.clear();
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     Fd file;
     uint64_t file_n = 0;
     { const int rc = open_regular(ctx, path, file, &file_n); if (rc != RALA_HIP_OK) return rc; }
@@ -287,18 +287,18 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     std::vector<uint32_t> length(R.n_records);
     if (!flags && R.n_records) {
         if (ctx->d_seq_span.ensure(R.n_records) != hipSuccess || ctx->d_seq_length.ensure(R.n_records) != hipSuccess) {
-            return ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
+            return fail(ctx, RALA_HIP_ENOMEM, "device memory for the sequence index");
         }
         SequenceColumns C;
         C.event_pos = ctx->d_seq_event[0].p; C.event_stripped = ctx->d_seq_event[1].p;
         C.name_pos = ctx->d_seq_name_pos.p; C.name_len = ctx->d_seq_name_len.p;
         C.data_off = ctx->d_seq_data_off.p; C.data_stripped = ctx->d_seq_data_stripped.p;
-        INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
         launch_sequence_finish(R.n_records, R.n_events, R.text_n, R.n_stripped, R.fastq, C, ctx->d_seq_span.p, ctx->d_seq_length.p, ctx->d_seq_flags.p, s);
-        INGEST_CHECK(hipGetLastError());
-        INGEST_CHECK(hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipMemcpyAsync(length.data(), ctx->d_seq_length.p, R.n_records * 4, hipMemcpyDeviceToHost, s));
-        INGEST_CHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(length.data(), ctx->d_seq_length.p, R.n_records * 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
     }
     kernel_ms += now_ms() - tf;
     ctx->seq_tm.ship_ms = (float)ship_ms;
@@ -309,7 +309,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
         fprintf(stderr, "[trace] device sequence index: %.2f GB of text shipped in %.1f ms, %lu records indexed in %.2f ms (flags %u)\n", R.text_n / 1e9,
                 ship_ms, (unsigned long)R.n_records, kernel_ms, flags);
     }
-    if (flags & kSeqTooLong) return ingest_fail(ctx, RALA_HIP_ETOOLARGE, "a sequence of 2^32 bases or more");
+    if (flags & kSeqTooLong) return fail(ctx, RALA_HIP_ETOOLARGE, "a sequence of 2^32 bases or more");
     if (flags) {
         *irregular = (int)flags;
         return RALA_HIP_OK;
@@ -340,15 +340,15 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
 int rala_hip_get_sequence_index(rala_hip_ctx* ctx, uint64_t* name_off, uint32_t* name_len, uint64_t* data_off, uint64_t* data_span,
                                 uint32_t* length, char* names) {
     if (!ctx) return RALA_HIP_EINVAL;
-    if (!ctx->seq_index_valid) return ingest_fail(ctx, RALA_HIP_EINVAL, "no sequence index (rala_hip_index_sequences)");
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->seq_index_valid) return fail(ctx, RALA_HIP_EINVAL, "no sequence index (rala_hip_index_sequences)");
+    HIPCHECK(hipSetDevice(ctx->device));
     const uint64_t n = ctx->n_seq_records;
-    if (n && name_off) INGEST_CHECK(hipMemcpy(name_off, ctx->d_seq_name_off.p, n * 8, hipMemcpyDeviceToHost));
-    if (n && name_len) INGEST_CHECK(hipMemcpy(name_len, ctx->d_seq_name_len.p, n * 4, hipMemcpyDeviceToHost));
-    if (n && data_off) INGEST_CHECK(hipMemcpy(data_off, ctx->d_seq_data_off.p, n * 8, hipMemcpyDeviceToHost));
-    if (n && data_span) INGEST_CHECK(hipMemcpy(data_span, ctx->d_seq_span.p, n * 8, hipMemcpyDeviceToHost));
-    if (n && length) INGEST_CHECK(hipMemcpy(length, ctx->d_seq_length.p, n * 4, hipMemcpyDeviceToHost));
-    if (ctx->n_seq_name_bytes && names) INGEST_CHECK(hipMemcpy(names, ctx->d_seq_arena.p, ctx->n_seq_name_bytes, hipMemcpyDeviceToHost));
+    if (n && name_off) HIPCHECK(hipMemcpy(name_off, ctx->d_seq_name_off.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && name_len) HIPCHECK(hipMemcpy(name_len, ctx->d_seq_name_len.p, n * 4, hipMemcpyDeviceToHost));
+    if (n && data_off) HIPCHECK(hipMemcpy(data_off, ctx->d_seq_data_off.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && data_span) HIPCHECK(hipMemcpy(data_span, ctx->d_seq_span.p, n * 8, hipMemcpyDeviceToHost));
+    if (n && length) HIPCHECK(hipMemcpy(length, ctx->d_seq_length.p, n * 4, hipMemcpyDeviceToHost));
+    if (ctx->n_seq_name_bytes && names) HIPCHECK(hipMemcpy(names, ctx->d_seq_arena.p, ctx->n_seq_name_bytes, hipMemcpyDeviceToHost));
     return RALA_HIP_OK;
 }
 
@@ -364,24 +364,24 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
     *irregular = 0;
     ctx->slice_info = rala_hip_sequence_slice_info();
     if (!ctx->seq_index_valid) { *irregular = 64; return RALA_HIP_OK; }
-    INGEST_CHECK(hipSetDevice(ctx->device));
+    HIPCHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint64_t n_rec = ctx->n_seq_records;
     // what the index holds of the wanted reads (none of them empty): where their text lies, where their bases go
     std::vector<uint64_t> data_off(n_rec), span(n_rec), data_stripped(n_rec);
     std::vector<uint32_t> length(n_rec);
     if (n_rec) {
-        INGEST_CHECK(hipMemcpy(data_off.data(), ctx->d_seq_data_off.p, n_rec * 8, hipMemcpyDeviceToHost));
-        INGEST_CHECK(hipMemcpy(span.data(), ctx->d_seq_span.p, n_rec * 8, hipMemcpyDeviceToHost));
-        INGEST_CHECK(hipMemcpy(data_stripped.data(), ctx->d_seq_data_stripped.p, n_rec * 8, hipMemcpyDeviceToHost));
-        INGEST_CHECK(hipMemcpy(length.data(), ctx->d_seq_length.p, n_rec * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(data_off.data(), ctx->d_seq_data_off.p, n_rec * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(span.data(), ctx->d_seq_span.p, n_rec * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(data_stripped.data(), ctx->d_seq_data_stripped.p, n_rec * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(length.data(), ctx->d_seq_length.p, n_rec * 4, hipMemcpyDeviceToHost));
     }
     std::vector<uint64_t> w_off, w_end, w_adj, w_base;
-    if (base_off[0] != 0) return ingest_fail(ctx, RALA_HIP_EINVAL, "base_off does not begin at 0");
+    if (base_off[0] != 0) return fail(ctx, RALA_HIP_EINVAL, "base_off does not begin at 0");
     for (uint64_t k = 0; k < n_wanted; ++k) {
         const uint64_t r = wanted[k];
-        if (r >= n_rec || (k && r <= wanted[k - 1])) return ingest_fail(ctx, RALA_HIP_EINVAL, "wanted reads not ascending records of the index");
-        if (base_off[k + 1] - base_off[k] != length[r]) return ingest_fail(ctx, RALA_HIP_EINVAL, "base_off is not the scan of the wanted reads' lengths");
+        if (r >= n_rec || (k && r <= wanted[k - 1])) return fail(ctx, RALA_HIP_EINVAL, "wanted reads not ascending records of the index");
+        if (base_off[k + 1] - base_off[k] != length[r]) return fail(ctx, RALA_HIP_EINVAL, "base_off is not the scan of the wanted reads' lengths");
         if (!length[r]) continue;
         w_off.push_back(data_off[r]);
         w_end.push_back(data_off[r] + span[r]);
@@ -402,10 +402,10 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
             for (int k = 0; k < 3; ++k) ctx->d_slice_w[k].release();
         }
     } release{ctx};
-    for (int k = 0; k < 3; ++k) INGEST_CHECK(ctx->d_slice_w[k].ensure(n_w));
-    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[0].p, w_off.data(), n_w * 8, hipMemcpyHostToDevice));
-    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[1].p, w_end.data(), n_w * 8, hipMemcpyHostToDevice));
-    INGEST_CHECK(hipMemcpy(ctx->d_slice_w[2].p, w_adj.data(), n_w * 8, hipMemcpyHostToDevice));
+    for (int k = 0; k < 3; ++k) HIPCHECK(ctx->d_slice_w[k].ensure(n_w));
+    HIPCHECK(hipMemcpy(ctx->d_slice_w[0].p, w_off.data(), n_w * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ctx->d_slice_w[1].p, w_end.data(), n_w * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ctx->d_slice_w[2].p, w_adj.data(), n_w * 8, hipMemcpyHostToDevice));
     TextSource S;
     S.fd = file.fd;
     S.path = path;
@@ -428,8 +428,8 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
     double kernel_ms = 0, gather_ms = 0, copy_ms = 0;
     uint32_t flags = 0;
     int rc = RALA_HIP_OK;
-    INGEST_CHECK(ctx->d_seq_flags.ensure(1));
-    INGEST_CHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
+    HIPCHECK(ctx->d_seq_flags.ensure(1));
+    HIPCHECK(hipMemsetAsync(ctx->d_seq_flags.p, 0, 4, s));
     // (a gzip member is inflated to its end, wanted reads or not: a window's markers point into the one before, and CRC32
     // and ISIZE say at the end whether this was the text the index saw)
     while (S.lo < S.text_n && rc == RALA_HIP_OK && !S.flag && !flags && (k_lo < n_w || S.gz)) {
@@ -441,7 +441,7 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
             // the stripped bytes in front of every tile, as the index counted them
             if (ctx->d_seq_tile[0].ensure(n_tiles + 2) != hipSuccess || ctx->d_seq_tile[1].ensure(n_tiles + 2) != hipSuccess ||
                 ctx->d_scan_ws.ensure(scan_workspace_bytes(n_tiles + 2)) != hipSuccess) {
-                rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for the tiles' counts");
+                rc = fail(ctx, RALA_HIP_ENOMEM, "device memory for the tiles' counts");
                 break;
             }
             launch_sequence_count(w.text, w.n, last_is_newline, ctx->seq_fastq, ctx->d_seq_tile[0].p, ctx->d_seq_tile[1].p, s);
@@ -450,7 +450,7 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
             uint8_t last = 0;
             if (hipMemcpyAsync(&stripped, ctx->d_seq_tile[1].p + n_tiles, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipMemcpyAsync(&last, w.text + w.n - 1, 1, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "counting a window's stripped bytes failed");
+                rc = fail(ctx, RALA_HIP_EDEVICE, "counting a window's stripped bytes failed");
                 break;
             }
             // the wanted reads with text in [lo, hi), and the share of the output that is this window's
@@ -463,7 +463,7 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
                 if (out_hi < out_lo || out_hi > n_bases || out_hi - out_lo > w.n) { flags = kSeqSliceMismatch; break; }
                 const uint64_t out_n = out_hi - out_lo;
                 if (out_n) {
-                    if (ctx->d_slice_out.ensure(out_n) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's bases"); break; }
+                    if (ctx->d_slice_out.ensure(out_n) != hipSuccess) { rc = fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's bases"); break; }
                     SequenceGather G;
                     G.text = w.text; G.n = w.n; G.text_off = lo;
                     G.tile_stripped0 = ctx->d_seq_tile[1].p; G.stripped0 = n_stripped;
@@ -472,11 +472,11 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
                     G.out_lo = out_lo; G.out_n = out_n; G.out = ctx->d_slice_out.p; G.flags = ctx->d_seq_flags.p;
                     const double tg = now_ms();
                     launch_sequence_gather(G, s);
-                    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "the gather kernel failed"); break; }
+                    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail(ctx, RALA_HIP_EDEVICE, "the gather kernel failed"); break; }
                     const double tc = now_ms();
                     if (hipMemcpyAsync(bases + out_lo, ctx->d_slice_out.p, out_n, hipMemcpyDeviceToHost, s) != hipSuccess ||
                         hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                        rc = ingest_fail(ctx, RALA_HIP_EDEVICE, "copying a window's bases failed");
+                        rc = fail(ctx, RALA_HIP_EDEVICE, "copying a window's bases failed");
                         break;
                     }
                     gather_ms += tc - tg;

@@ -10,26 +10,12 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "ctx_check.h"
 #include "stages.h"
 
 using namespace rala_hip;
 
 namespace {
-
-#define LAYOUT_HIPCHECK(call)                                                                \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            return e_ == hipErrorOutOfMemory ? RALA_HIP_ENOMEM : RALA_HIP_EDEVICE;           \
-        }                                                                                    \
-    } while (0)
-
-int refuse(rala_hip_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return RALA_HIP_EINVAL;
-}
 
 size_t align8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
 
@@ -39,25 +25,25 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
                           const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations, double t,
                           double dt) {
     if (!ctx) return RALA_HIP_EINVAL;
-    if (n_components && !comp_off) return refuse(ctx, "rala_hip_layout_batch: comp_off is null");
+    if (n_components && !comp_off) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: comp_off is null");
     // ---- everything is checked before anything is enqueued ----
     const uint32_t C = n_components;
-    if (C && comp_off[0] != 0) return refuse(ctx, "rala_hip_layout_batch: comp_off does not start at 0");
+    if (C && comp_off[0] != 0) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: comp_off does not start at 0");
     for (uint32_t c = 0; c < C; ++c) {
-        if (comp_off[c + 1] < comp_off[c]) return refuse(ctx, "rala_hip_layout_batch: comp_off decreases");
+        if (comp_off[c + 1] < comp_off[c]) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: comp_off decreases");
     }
     const size_t N = C ? comp_off[C] : 0;
-    if (N && (!x || !y || !adj_off || !k)) return refuse(ctx, "rala_hip_layout_batch: a null array");
-    if (N && adj_off[0] != 0) return refuse(ctx, "rala_hip_layout_batch: adj_off does not start at 0");
+    if (N && (!x || !y || !adj_off || !k)) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: a null array");
+    if (N && adj_off[0] != 0) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: adj_off does not start at 0");
     for (size_t p = 0; p < N; ++p) {
-        if (adj_off[p + 1] < adj_off[p]) return refuse(ctx, "rala_hip_layout_batch: adj_off decreases");
+        if (adj_off[p + 1] < adj_off[p]) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: adj_off decreases");
     }
     const size_t A = N ? adj_off[N] : 0;
-    if (A && !adj) return refuse(ctx, "rala_hip_layout_batch: adj is null");
+    if (A && !adj) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: adj is null");
     for (uint32_t c = 0; c < C && N; ++c) {
         const uint32_t n_c = comp_off[c + 1] - comp_off[c];
         for (size_t a = adj_off[comp_off[c]]; a < adj_off[comp_off[c + 1]]; ++a) {
-            if (adj[a] > n_c) return refuse(ctx, "rala_hip_layout_batch: a partner index beyond its component");
+            if (adj[a] > n_c) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: a partner index beyond its component");
         }
     }
 
@@ -84,7 +70,7 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
     info.components_fused_256 = (uint32_t)list256.size();
     info.components_fused_1024 = (uint32_t)list1024.size();
     const size_t T = tiles.size() / 2;
-    if (T > 0x7FFFFFFFull) return refuse(ctx, "rala_hip_layout_batch: too many points for one launch");
+    if (T > 0x7FFFFFFFull) return fail(ctx, RALA_HIP_EINVAL, "rala_hip_layout_batch: too many points for one launch");
     info.step_tiles = (uint32_t)T;
     if (N == 0 || iterations == 0) {
         ctx->layout_info = info;
@@ -98,10 +84,10 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
     const size_t o_adj_off = o_comp + ((size_t)C + 1) * 4, o_adj = o_adj_off + (N + 1) * 4, o_l256 = o_adj + A * 4;
     const size_t o_l1024 = o_l256 + list256.size() * 4, o_tiles = align8(o_l1024 + list1024.size() * 4);
     const size_t upload = o_tiles + T * 8, o_x2 = align8(upload), o_y2 = o_x2 + N * 8, total = o_y2 + N * 8;
-    LAYOUT_HIPCHECK(hipSetDevice(ctx->device));
-    for (auto& e : ctx->ev_layout) if (!e) LAYOUT_HIPCHECK(hipEventCreate(&e));
-    LAYOUT_HIPCHECK(ctx->d_layout_batch.ensure(total));
-    LAYOUT_HIPCHECK(ctx->p_layout_batch.ensure(upload));
+    HIPCHECK(hipSetDevice(ctx->device));
+    for (auto& e : ctx->ev_layout) if (!e) HIPCHECK(hipEventCreate(&e));
+    HIPCHECK(ctx->d_layout_batch.ensure(total));
+    HIPCHECK(ctx->p_layout_batch.ensure(upload));
     unsigned char* const h = ctx->p_layout_batch.p;
     unsigned char* const d = ctx->d_layout_batch.p;
     memcpy(h + o_x, x, N * 8);
@@ -115,7 +101,7 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
     if (T) memcpy(h + o_tiles, tiles.data(), T * 8);
 
     hipStream_t s = ctx->stream;
-    LAYOUT_HIPCHECK(hipMemcpyAsync(d, h, upload, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(d, h, upload, hipMemcpyHostToDevice, s));
     double* const px[2] = {(double*)(d + o_x), (double*)(d + o_x2)};
     double* const py[2] = {(double*)(d + o_y), (double*)(d + o_y2)};
     const double* const d_k = (const double*)(d + o_k);
@@ -124,7 +110,7 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
     const uint32_t* const d_adj = (const uint32_t*)(d + o_adj);
     // where the stepped components end up after `iterations` swaps; the fused ones write there directly
     const int last = (int)(iterations & 1u);
-    LAYOUT_HIPCHECK(hipEventRecord(ctx->ev_layout[0], s));
+    HIPCHECK(hipEventRecord(ctx->ev_layout[0], s));
     launch_layout_fused(256, (uint32_t)list256.size(), (const uint32_t*)(d + o_l256), d_comp, px[0], py[0], px[last], py[last],
                         d_adj_off, d_adj, d_k, iterations, t, dt, s);
     launch_layout_fused(1024, (uint32_t)list1024.size(), (const uint32_t*)(d + o_l1024), d_comp, px[0], py[0], px[last],
@@ -139,14 +125,14 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
             t_step -= dt;
         }
     }
-    LAYOUT_HIPCHECK(hipEventRecord(ctx->ev_layout[1], s));
+    HIPCHECK(hipEventRecord(ctx->ev_layout[1], s));
     // x and y of a buffer lie side by side: one copy (into the pinned block, which the upload has left by now)
-    LAYOUT_HIPCHECK(hipMemcpyAsync(h, px[last], 2 * N * 8, hipMemcpyDeviceToHost, s));
-    LAYOUT_HIPCHECK(stream_sync(ctx, s));
-    LAYOUT_HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(h, px[last], 2 * N * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(stream_sync(ctx, s));
+    HIPCHECK(hipGetLastError());
     memcpy(x, h, N * 8);
     memcpy(y, h + N * 8, N * 8);
-    LAYOUT_HIPCHECK(hipEventElapsedTime(&info.device_ms, ctx->ev_layout[0], ctx->ev_layout[1]));
+    HIPCHECK(hipEventElapsedTime(&info.device_ms, ctx->ev_layout[0], ctx->ev_layout[1]));
     ctx->layout_info = info;
     return RALA_HIP_OK;
 }

@@ -1,4 +1,6 @@
-// librala_hip: C ABI (include/rala_hip.h) and host orchestration of the stages.
+// librala_hip: the stages of the C ABI (include/rala_hip.h) and their host orchestration - rala_hip_initialize,
+// rala_hip_construct, the transitive reduction, the building blocks of sharded runs - and the getters.  (A context's
+// creation, options, inputs and installed state: context.hip; what each call means for the context's life: lifecycle.h.)
 //
 // Device work: duplicate removal, bound bucketing, pile build + annotation,
 // overlap classification, the containment fixed point, hill counters,
@@ -15,76 +17,16 @@
 #include <chrono>
 #include <numeric>
 
-#include "context.h"
+#include "ctx_check.h"
+#include "lifecycle.h"
 #include "scan_pass.h"
 #include "stages.h"
 
 using namespace rala_hip;
 
 
-// Small device -> host reads (counters, flags) go through a pinned staging area: an async copy
-// into pageable memory is staged by the runtime and costs tens of microseconds more, and the
-// tail does a dozen of them per call.  d2h_small queues the copy, stream_sync waits for the
-// stream and delivers what was queued.
-hipError_t rala_hip::d2h_small(rala_hip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (ctx->p_stage.ensure(256) != hipSuccess || ctx->stage_used + bytes > 256 * sizeof(uint32_t) ||
-        ctx->stage_pending.size() >= 16) {
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
-    }
-    char* at = (char*)ctx->p_stage.p + ctx->stage_used;
-    const hipError_t e = hipMemcpyAsync(at, src, bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    ctx->stage_pending.push_back({dst, ctx->stage_used, bytes});
-    ctx->stage_used += (bytes + 7) & ~(size_t)7;
-    return hipSuccess;
-}
-
-hipError_t rala_hip::stream_sync(rala_hip_ctx* ctx, hipStream_t s) {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) {      // a failed wait delivers nothing
-        for (const auto& c : ctx->stage_pending) memcpy(c.dst, (const char*)ctx->p_stage.p + c.offset, c.bytes);
-    }
-    ctx->stage_pending.clear();
-    ctx->stage_used = 0;
-    return e;
-}
-
-namespace {
-
-// Every error return drops the staged device -> host copies that were queued but not delivered
-// yet (d2h_small below): their destinations are mostly locals of the function that is returning.
-#define HIPCHECK(call)                                                                       \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            ctx->stage_pending.clear();                                                      \
-            ctx->stage_used = 0;                                                             \
-            return e_ == hipErrorOutOfMemory ? RALA_HIP_ENOMEM : RALA_HIP_EDEVICE;           \
-        }                                                                                    \
-    } while (0)
-
-int fail(rala_hip_ctx* ctx, int code, const char* msg) {
-    ctx->err = msg;
-    ctx->stage_pending.clear();
-    ctx->stage_used = 0;
-    return code;
-}
-
-ReadState read_state(rala_hip_ctx* ctx) {
-    ReadState rs;
-    rs.begin = ctx->d_begin.p; rs.end = ctx->d_end.p; rs.alive = ctx->d_alive.p;
-    rs.n_pits = ctx->d_n_pits.p; rs.n_hills = ctx->d_n_hills.p; rs.iv_slot = ctx->d_iv_slot.p;
-    rs.pool = ctx->d_pool.p;
-    return rs;
-}
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // ---- host mirror of the per-read state -------------------------------------------
-int download_read_state(rala_hip_ctx* ctx) {
+int rala_hip::download_read_state(rala_hip_ctx* ctx) {
     const uint64_t n = ctx->n_reads;
     HIPCHECK(hipSetDevice(ctx->device));        // (getters may be called with another rank's device current)
     ctx->h_begin.resize(n); ctx->h_end.resize(n); ctx->h_median.resize(n); ctx->h_p10.resize(n);
@@ -107,8 +49,22 @@ int download_read_state(rala_hip_ctx* ctx) {
     if (used) {
         HIPCHECK(hipMemcpy(ctx->h_pool.data(), ctx->d_pool.p, (size_t)used * sizeof(Interval), hipMemcpyDeviceToHost));
     }
-    ctx->host_state_fresh = true;
+    host_mirrors_fresh(ctx);
     return RALA_HIP_OK;
+}
+
+namespace {
+
+ReadState read_state(rala_hip_ctx* ctx) {
+    ReadState rs;
+    rs.begin = ctx->d_begin.p; rs.end = ctx->d_end.p; rs.alive = ctx->d_alive.p;
+    rs.n_pits = ctx->d_n_pits.p; rs.n_hills = ctx->d_n_hills.p; rs.iv_slot = ctx->d_iv_slot.p;
+    rs.pool = ctx->d_pool.p;
+    return rs;
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // ---- launch classes of the position-space kernel: reads grouped by LDS image size ------
@@ -900,7 +856,7 @@ int download_repeat_hills(rala_hip_ctx* ctx) {
     if (ctx->n_rep_hills) {
         HIPCHECK(hipMemcpy(ctx->h_rep_pool.data(), ctx->d_rep_pool.p, (size_t)ctx->n_rep_hills * sizeof(Interval), hipMemcpyDeviceToHost));
     }
-    ctx->rep_host_stale = false;
+    repeat_hills_fetched(ctx);
     return RALA_HIP_OK;
 }
 void build_graph(rala_hip_ctx* ctx);
@@ -1252,8 +1208,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     }
     trc("rep: bridged hills", n_sens);
     // the host's copy of the hills: at once where the host filters the overlaps below, otherwise with the first getter
-    cs->n_rep_hills = n_hills;
-    cs->rep_host_stale = true;
+    repeat_hills_left_on_device(cs, n_hills);
     if (!device_lists) {
         const int rcd = download_repeat_hills(cs);
         if (rcd != RALA_HIP_OK) return rcd;
@@ -1276,8 +1231,8 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         cs->overlaps.resize(w);
     }
     trc("rep: filter overlaps", cs->overlaps.size());
-    cs->have_repeats = true;
-    cl->sens_csr_ready = true;
+    repeat_hills_found(cs);
+    sensitive_bounds_kept(cl);
     return RALA_HIP_OK;
 }
 
@@ -1651,8 +1606,7 @@ int gpu_tail_part_b(rala_hip_ctx* ctx) {
     ctx->t_n_nodes = 2 * n_final;
     ctx->t_n_edges = 2 * totals[1];
     mark("tail: final list, nodes, edges", ctx->t_n_edges);
-    ctx->tail_on_device = true;
-    ctx->host_stale = true;
+    tail_left_on_device(ctx);
     return RALA_HIP_OK;
 }
 
@@ -1709,7 +1663,7 @@ int materialize_host(rala_hip_ctx* ctx) {
     ctx->overlaps.clear(); ctx->internals.clear();
     for (uint32_t k : kept) ctx->overlaps.push_back(item(k));
     for (uint32_t k = ctx->t_n0; k < M; ++k) if (state[k] == 2) ctx->internals.push_back(item(k));
-    ctx->host_stale = false;
+    host_lists_fetched(ctx);
     return RALA_HIP_OK;
 }
 
@@ -1747,7 +1701,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
 
     if (ctx->dedupe_pending) {          // (a sharded run's duplicate removal ran beside the emit, on the side stream)
         HIPCHECK(hipStreamWaitEvent(s, ctx->ev[1], 0));
-        ctx->dedupe_pending = false;
+        dedupe_joined(ctx);
     }
     // ---- static part ----
     // (a sharded run gathers up to 65 536 undecided killers of ALL ranks on every rank: room for them whatever the slice's size)
@@ -2096,19 +2050,18 @@ int rala_hip::construct_stages(rala_hip_ctx* ctx, Comm* comm, bool sensitive_pas
     if (!ctx) return RALA_HIP_EINVAL;
     int rc = check_constructible(ctx);
     if (rc != RALA_HIP_OK) return rc;
-    ctx->have_repeats = false;
+    construct_begun(ctx);
     HIPCHECK(hipSetDevice(ctx->device));
     rc = pass2(ctx, comm);
     if (rc != RALA_HIP_OK) return rc;
-    ctx->tail_on_device = false;
-    ctx->host_stale = false;
+    tail_begun(ctx);
     const double t0 = now_ms();
     rc = sensitive_pass_follows ? gpu_tail_part_a(ctx) : gpu_tail_run(ctx);      // (repeats_stage builds the graph)
     if (rc != RALA_HIP_OK) return rc;
     rc = pass2_times(ctx);
     if (rc != RALA_HIP_OK) return rc;
     ctx->tm.tail_host_ms = (float)(now_ms() - t0);
-    ctx->constructed = true;
+    constructed(ctx);
     return RALA_HIP_OK;
 }
 
@@ -2129,7 +2082,7 @@ int rala_hip::transitive_stage(rala_hip_ctx* ctx, Comm* comm, uint32_t* n_pairs)
     HIPCHECK(hipSetDevice(ctx->device));
     if (ctx->tail_on_device) {
         const int rc = tr_mark_device(ctx, ctx->t_n_nodes, ctx->t_n_edges, ctx->d_e[0].p, ctx->d_e[1].p, ctx->d_e[2].p, n_pairs, comm);
-        ctx->marks_on_device = rc == RALA_HIP_OK;
+        marks_left_on_device(ctx, rc == RALA_HIP_OK);
         return rc;
     }
     // (the tail ran on the host, or the sensitive pass rebuilt the graph there: a host graph)
@@ -2141,15 +2094,6 @@ int rala_hip::transitive_stage(rala_hip_ctx* ctx, Comm* comm, uint32_t* n_pairs)
 
 // A sender of a sharded run: duplicate removal on the side stream (joined by the second pass), the bounds of the slice
 // scattered once by (owner, partition) into `send` (shard_send_words() words); words[p] = 8-byte words of owner p's block.
-// RALA_HIP_MEM_HOST_ASYNC columns that rala_hip_initialize has not uploaded yet: now, for a caller that reads them first
-int rala_hip::flush_upload(rala_hip_ctx* ctx) {
-    if (!ctx->upload_pending) return RALA_HIP_OK;
-    for (int k = 0; k < 7; ++k) HIPCHECK(hipMemcpy(ctx->d_ovl_u32[k].p, ctx->up_src[k], (size_t)ctx->n_ovl * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_ovl_strand.p, ctx->up_strand, ctx->n_ovl, hipMemcpyHostToDevice));
-    ctx->upload_pending = false;
-    return RALA_HIP_OK;
-}
-
 int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* send, uint64_t* words) {
     if (!ctx || !send || !words) return RALA_HIP_EINVAL;
     if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
@@ -2174,11 +2118,11 @@ int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* se
         HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[0], 0));
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, ctx->side);
         HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
-        ctx->dedupe_pending = true;
+        dedupe_forked(ctx);
     } else {
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, s);
     }
-    ctx->valid_ready = true;
+    validity_bits_ready(ctx);
     HIPCHECK(ctx->d_shard_group.ensure((size_t)g.world * g.groups + 2));
     HIPCHECK(ctx->d_shard_part.ensure((size_t)g.world * g.n_part + 2));
     HIPCHECK(ctx->d_shard_words.ensure(64));
@@ -2189,7 +2133,7 @@ int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* se
         HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[0], 0));
         launch_dedupe_fix(ctx->ovl, n_reads, bd, ctx->side);
         HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
-        ctx->dedupe_pending = true;
+        dedupe_forked(ctx);
     }
     uint32_t h[64];
     HIPCHECK(d2h_small(ctx, h, ctx->d_shard_words.p, g.world * 4, s));
@@ -2199,314 +2143,7 @@ int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* se
     return RALA_HIP_OK;
 }
 
-// An owner of a sharded run: its input is the blocks of all senders where they lie (base: what was received; base_self:
-// the send buffer, for the rank's own block); n_records of them in all.  rala_hip_initialize takes it from there.
-int rala_hip::set_bound_blocks(rala_hip_ctx* ctx, const uint64_t* base, const uint64_t* base_self, const ShardBlocks& blocks,
-                               const ShardGeometry& g, uint64_t n_records) {
-    if (!ctx) return RALA_HIP_EINVAL;
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (n_records >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_EINVAL, "too many records");
-    HIPCHECK(hipSetDevice(ctx->device));
-    ctx->blocks_base = base; ctx->blocks_base_self = base_self; ctx->blocks = blocks; ctx->shard_geom = g;
-    ctx->n_block_records = n_records;
-    ctx->blocks_mode = true;
-    ctx->records = nullptr; ctx->n_records = 0;
-    ctx->tuples = nullptr; ctx->n_tuples = 2 * n_records;
-    ctx->tuple_mode = true;
-    ctx->inputs_set = true;
-    ctx->n_ovl = 0;
-    ctx->ovl = OvlSoA();
-    HIPCHECK(ctx->d_ev.ensure(2 * n_records + 8));
-    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(2 * n_records, ctx->n_reads) + 2)));
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    return RALA_HIP_OK;
-}
-
-int rala_hip::install_read_state(rala_hip_ctx* ctx, uint64_t pool_count) {
-    if (!ctx) return RALA_HIP_EINVAL;
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_ovl && !ctx->valid_ready) return fail(ctx, RALA_HIP_EINVAL, "validity bits required (rala_hip_dedupe)");
-    if (pool_count > ctx->pool_cap) return fail(ctx, RALA_HIP_ECAPACITY, "interval pool smaller than the installed state");
-    HIPCHECK(hipSetDevice(ctx->device));
-    { const int rcu = flush_upload(ctx); if (rcu != RALA_HIP_OK) return rcu; }
-    hipStream_t s = ctx->stream;
-    ctx->tm = rala_hip_timings();
-    ctx->overlaps.clear(); ctx->internals.clear();
-    const uint32_t small[8] = {(uint32_t)pool_count, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHECK(hipMemcpyAsync(ctx->d_small.p, small, sizeof(small), hipMemcpyHostToDevice, s));
-    HIPCHECK(ctx->d_cc_flags.ensure(8));
-    HIPCHECK(hipMemsetAsync(ctx->d_cc_flags.p + 6, 0, 4, s));
-    launch_count_zero_u8(ctx->d_alive.p, (uint32_t)ctx->n_reads, ctx->d_cc_flags.p + 6, s);
-    uint32_t n_dead = 0;
-    HIPCHECK(d2h_small(ctx, &n_dead, ctx->d_cc_flags.p + 6, 4, s));
-    HIPCHECK(stream_sync(ctx, s));                  // `small` is a local
-    ctx->host_state_fresh = false;
-    ctx->pool_used = (uint32_t)pool_count;
-    ctx->n_prefiltered = n_dead;
-    ctx->initialized = true;
-    ctx->constructed = false;
-    ctx->piles_resident = ctx->ev_ready = false;
-    ctx->tail_on_device = ctx->host_stale = ctx->marks_on_device = false;
-    if (ctx->n_prefiltered == ctx->n_reads) return fail(ctx, RALA_HIP_EFILTERED, "filtered all sequences");
-    return RALA_HIP_OK;
-}
-
 extern "C" {
-
-int rala_hip_create(int device, rala_hip_ctx** out) {
-    if (!out) return RALA_HIP_EINVAL;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return RALA_HIP_EDEVICE;
-    if (hipSetDevice(device) != hipSuccess) return RALA_HIP_EDEVICE;
-    rala_hip_ctx* ctx = new rala_hip_ctx;
-    ctx->device = device;
-    if (const char* mb = getenv("RALA_HIP_PILE_CHUNK_MB")) ctx->pile_chunk_mb = (uint32_t)std::max(0, atoi(mb));      // (measurements: the option's default)
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
-            ctx->n_compute_units = (uint32_t)prop.multiProcessorCount;
-        }
-    }
-    // (the side stream at the highest priority the device offers: what runs there beside a kernel that fills the chip - the
-    // position-space kernels of the sensitive pass, whose workgroups want most of a compute unit's LDS - gets the compute
-    // units as they come free instead of when the other kernel has drained)
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    bool ok = hipStreamCreate(&ctx->stream) == hipSuccess &&
-              hipStreamCreateWithPriority(&ctx->side, hipStreamDefault, prio_greatest) == hipSuccess &&
-              hipStreamCreate(&ctx->aux) == hipSuccess;
-    for (auto& e : ctx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && ctx->d_small.ensure(16) == hipSuccess;
-    if (!ok) {                                  // (rala_hip_destroy releases whatever was created)
-        rala_hip_destroy(ctx);
-        return RALA_HIP_EDEVICE;
-    }
-    ctx->pool.reset(new HostPool(std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
-    *out = ctx;
-    return RALA_HIP_OK;
-}
-
-void rala_hip_destroy(rala_hip_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    ctx->stage_pending.clear();             // nobody is waiting for staged copies any more
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
-    if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
-    for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_up) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_layout) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_names) if (e) (void)hipEventDestroy(e);
-    if (ctx->copy) (void)hipStreamDestroy(ctx->copy);
-    if (ctx->side) (void)hipStreamDestroy(ctx->side);
-    if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
-
-const char* rala_hip_last_error(const rala_hip_ctx* ctx) { return ctx ? ctx->err.c_str() : "no context"; }
-
-int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
-    if (!ctx || !key) return RALA_HIP_EINVAL;
-    if (!strcmp(key, "interval_pool_per_read_x1000")) { ctx->pool_per_read_x1000 = value; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_big_caps")) { ctx->debug_big_caps = value; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_force_big")) { ctx->debug_force_big = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "max_lds_read_len")) { ctx->max_lds_read_len = value; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_pile_stop_after")) { ctx->debug_pile_stop_after = value; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_run_kernel")) { ctx->use_run_kernel = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_round_batches")) { ctx->use_round_batches = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_bound_records")) { ctx->use_bound_records = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_fused_emit")) { ctx->use_fused_emit = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "ingest_window_bytes")) { ctx->ingest_window_bytes = std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_sequence_window")) { ctx->debug_sequence_window = std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "gzip_on_device")) { ctx->gzip_on_device = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "gzip_members")) { ctx->gzip_members = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "bgzf_in_pieces")) { ctx->bgzf_in_pieces = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "gzip_chunk_bytes")) { ctx->gzip_chunk_bytes = value > 0 ? value : 64 << 10; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_gzip_false_sync")) { ctx->debug_gzip_false_sync = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "pile_rows")) { ctx->pile_rows = value ? 1u : 0u; return RALA_HIP_OK; }
-    if (!strcmp(key, "pile_rows_scratch_mb")) { ctx->pile_rows_scratch_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
-    if (!strcmp(key, "pile_chunk_mb")) { ctx->pile_chunk_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_ev_events")) { ctx->debug_ev_events = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_count_window")) { ctx->debug_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_part_shift")) { ctx->debug_part_shift = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_pile_variant")) { ctx->debug_pile_variant = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_dedupe_list_cap")) { ctx->debug_dedupe_list_cap = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_fp_lds_limit")) { ctx->debug_fp_lds_limit = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_fp_give_up")) { ctx->debug_fp_give_up = value == 2 ? 2u : value != 0 ? 1u : 0u; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_chunk_fail")) { ctx->debug_chunk_fail = value; return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_fail_construct")) { ctx->debug_fail_construct = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_gpu_tail")) { ctx->use_gpu_tail = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_fixed_buckets")) { ctx->use_fixed_buckets = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_partitioned_buckets")) { ctx->use_partitioned_buckets = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "use_side_stream")) { ctx->use_side_stream = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "sensitive_in_device_memory")) { ctx->sens_in_device = value != 0; return RALA_HIP_OK; }
-    if (!strcmp(key, "layout_fused_max")) {
-        if (value < 0 || value > 1024) return fail(ctx, RALA_HIP_EINVAL, "layout_fused_max: 0 .. 1024");
-        ctx->layout_fused_max = value;
-        return RALA_HIP_OK;
-    }
-    if (!strcmp(key, "host_threads")) {
-        ctx->host_threads = value;
-        ctx->pool.reset(new HostPool((unsigned)std::max<int64_t>(1, std::min<int64_t>(value, 256))));
-        return RALA_HIP_OK;
-    }
-    return fail(ctx, RALA_HIP_EINVAL, "unknown option");
-}
-
-void* rala_hip_stream(rala_hip_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
-
-int rala_hip_set_reads(rala_hip_ctx* ctx, const uint32_t* read_len, uint64_t n_reads) {
-    if (!ctx || (!read_len && n_reads)) return RALA_HIP_EINVAL;
-    if (n_reads >= 0x7FFFFFFFull) return fail(ctx, RALA_HIP_EINVAL, "too many reads");
-    HIPCHECK(hipSetDevice(ctx->device));
-    HIPCHECK(hipStreamSynchronize(ctx->side));
-    HIPCHECK(hipStreamSynchronize(ctx->aux));
-    ctx->n_reads = n_reads;
-    ctx->h_read_len.assign(read_len, read_len + n_reads);
-    ctx->max_read_len = 0;
-    for (uint64_t r = 0; r < n_reads; ++r) ctx->max_read_len = std::max(ctx->max_read_len, read_len[r]);
-    {
-        // length classes of the pile chain (kernels.h: kPileClassBases)
-        uint32_t cnt[kPileClasses] = {};
-        auto cls = [](uint32_t n) {
-            uint32_t c = 0;
-            while (c + 1 < kPileClasses && n > kPileClassBases[c]) ++c;
-            return c;
-        };
-        for (uint64_t r = 0; r < n_reads; ++r) ++cnt[cls(read_len[r])];
-        for (uint32_t c = 0; c < kPileClasses; ++c) ctx->n_class[c] = cnt[c];
-        if (cnt[0] != n_reads) {
-            std::vector<uint32_t> order(n_reads);
-            uint32_t at[kPileClasses] = {};
-            for (uint32_t c = 1; c < kPileClasses; ++c) at[c] = at[c - 1] + cnt[c - 1];
-            for (uint64_t r = 0; r < n_reads; ++r) order[at[cls(read_len[r])]++] = (uint32_t)r;
-            HIPCHECK(ctx->d_class_order.ensure(n_reads));
-            HIPCHECK(hipMemcpy(ctx->d_class_order.p, order.data(), n_reads * 4, hipMemcpyHostToDevice));
-        }
-    }
-    ctx->h_pile_off.resize(n_reads + 1);
-    // Rows start on 128-byte boundaries (64 elements): a row's first and last cache line are then its own, not shared
-    // with the neighbouring rows, which other wavefronts write at other times.  Round 4, one box, pile kernel at C3:
-    // 16-byte boundaries (rounds 1 - 3: what the 16-byte stores need) 4.26 ms, 128 bytes 4.17, 1 KB 4.18, 4 KB 4.21
-    // (docs/history/gpurun/r4_rowalign.sh; RALA_PILE_ROW_ALIGN=<elements, a power of two >= 8> for the experiment).
-    static const uint64_t row_align = [] {
-        uint64_t want = getenv("RALA_PILE_ROW_ALIGN") ? (uint64_t)atoll(getenv("RALA_PILE_ROW_ALIGN")) : 64ull, a = 8;
-        while (a * 2 <= want && a < (1ull << 20)) a *= 2;           // a power of two, 8 elements at least
-        return a;
-    }();
-    uint64_t off = 0;
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        ctx->h_pile_off[r] = off;
-        off += ((uint64_t)read_len[r] + row_align - 1) & ~(row_align - 1);
-    }
-    ctx->h_pile_off[n_reads] = off;
-    ctx->pile_elems = off;
-    HIPCHECK(ctx->d_read_len.ensure(n_reads + 1));
-    HIPCHECK(ctx->d_pile_off.ensure(n_reads + 1));
-    ctx->d_pile.release();                       // allocated by rala_hip_initialize (owners only)
-    HIPCHECK(hipMemcpy(ctx->d_read_len.p, read_len, n_reads * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_pile_off.p, ctx->h_pile_off.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHECK(ctx->d_order.ensure(n_reads + 1));
-    HIPCHECK(ctx->d_overflow.ensure(n_reads + 1));
-    HIPCHECK(ctx->d_ev_off.ensure(n_reads + 2)); HIPCHECK(ctx->d_cursor.ensure(n_reads + 2));
-    HIPCHECK(ctx->d_suspect.ensure(n_reads + 1));
-    HIPCHECK(ctx->d_begin.ensure(n_reads)); HIPCHECK(ctx->d_end.ensure(n_reads));
-    HIPCHECK(ctx->d_median.ensure(n_reads)); HIPCHECK(ctx->d_p10.ensure(n_reads));
-    HIPCHECK(ctx->d_alive.ensure(n_reads)); HIPCHECK(ctx->d_n_pits.ensure(n_reads));
-    HIPCHECK(ctx->d_n_hills.ensure(n_reads)); HIPCHECK(ctx->d_iv_slot.ensure(n_reads));
-    HIPCHECK(ctx->d_death[0].ensure(n_reads)); HIPCHECK(ctx->d_death[1].ensure(n_reads));
-    // scans run over reads as well as over overlaps / tuples, whichever call comes first
-    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(std::max(ctx->n_ovl, ctx->n_tuples), n_reads) + 2)));
-    // host mirrors of the per-read state.  They are NOT registered with the runtime: registration
-    // pins whole pages, small vectors of different contexts share pages of the heap, and
-    // unregistering one context's vectors then unmapped pages another context's copies still went
-    // to ("Memory access fault by GPU" in a later, unrelated call).
-    ctx->h_begin.resize(n_reads); ctx->h_end.resize(n_reads); ctx->h_median.resize(n_reads);
-    ctx->h_p10.resize(n_reads); ctx->h_alive.resize(n_reads); ctx->h_n_pits.resize(n_reads);
-    ctx->h_n_hills.resize(n_reads); ctx->h_slot.resize(n_reads);
-    // (a hint: a pool that turns out too small grows to the counted need; 0 = start at 16 slots, for the tests of that)
-    ctx->pool_cap = (uint32_t)std::max<int64_t>(ctx->pool_per_read_x1000 == 0 ? 16 : 1024, (int64_t)n_reads * ctx->pool_per_read_x1000 / 1000);
-    ctx->pool_cap_first = ctx->pool_cap;        // (the repeat hills' pool starts there too, and grows on its own)
-    ctx->rep_pool_cap = 0;
-    HIPCHECK(ctx->d_pool.ensure(ctx->pool_cap));
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    return RALA_HIP_OK;
-}
-
-int rala_hip_set_overlaps(rala_hip_ctx* ctx, const rala_hip_overlaps* o, uint64_t n, int mem) {
-    if (!ctx || (!o && n)) return RALA_HIP_EINVAL;
-    // (2 n bound pairs in 32 bits - the partitioned bucketing's offsets, kernels.h: kBucketPairShift; the other bucketing paths count
-    // 4 n events and say so in rala_hip_initialize when they meet more)
-    if (n >= 0xFFFFFFF0ull / 2) return fail(ctx, RALA_HIP_EINVAL, "too many overlaps for 32-bit bound offsets");
-    HIPCHECK(hipSetDevice(ctx->device));
-    HIPCHECK(hipStreamSynchronize(ctx->side));          // a failed call may have left work there
-    HIPCHECK(hipStreamSynchronize(ctx->aux));
-    if (ctx->copy) HIPCHECK(hipStreamSynchronize(ctx->copy));
-    ctx->upload_pending = false;
-    if (mem == RALA_HIP_MEM_HOST_ASYNC && !ctx->copy) {
-        // (made when first asked for: a process has few hardware queues - four by default - and its streams share them; a
-        // stream that is not used must not push a context's main and aux streams onto one queue.  It did, in the sharded
-        // runner's owner contexts: their small pile kernels ran in front of the big one instead of beside it, +0.13 ms at C3)
-        // (all or nothing: a stream whose events could not all be made would leave later calls with null events - advisor round 5)
-        hipStream_t made = nullptr;
-        HIPCHECK(hipStreamCreate(&made));
-        hipError_t bad = hipSuccess;
-        for (auto& e : ctx->ev_up) {
-            e = nullptr;
-            if (bad == hipSuccess) bad = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-        }
-        if (bad != hipSuccess) {
-            for (auto& e : ctx->ev_up) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-            (void)hipStreamDestroy(made);
-            HIPCHECK(bad);
-        }
-        ctx->copy = made;
-    }
-    ctx->n_ovl = n;
-    const uint32_t* src[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (n) {
-        src[0] = o->a_id; src[1] = o->b_id; src[2] = o->a_begin; src[3] = o->a_end;
-        src[4] = o->b_begin; src[5] = o->b_end; src[6] = o->length;
-    }
-    const uint32_t* dev[7];
-    const uint8_t* dev_strand;
-    if (mem == RALA_HIP_MEM_DEVICE) {
-        for (int k = 0; k < 7; ++k) dev[k] = src[k];
-        dev_strand = n ? o->strand : nullptr;
-    } else {
-        // (RALA_HIP_MEM_HOST_ASYNC: room now, the copies in rala_hip_initialize - upload_columns)
-        const bool later = mem == RALA_HIP_MEM_HOST_ASYNC && n != 0;
-        for (int k = 0; k < 7; ++k) {
-            HIPCHECK(ctx->d_ovl_u32[k].ensure(n));
-            if (n && !later) HIPCHECK(hipMemcpy(ctx->d_ovl_u32[k].p, src[k], n * 4, hipMemcpyHostToDevice));
-            dev[k] = ctx->d_ovl_u32[k].p;
-            ctx->up_src[k] = src[k];
-        }
-        HIPCHECK(ctx->d_ovl_strand.ensure(n));
-        if (n && !later) HIPCHECK(hipMemcpy(ctx->d_ovl_strand.p, o->strand, n, hipMemcpyHostToDevice));
-        dev_strand = ctx->d_ovl_strand.p;
-        ctx->up_strand = n ? o->strand : nullptr;
-        ctx->upload_pending = later;
-    }
-    ctx->ovl.a_id = dev[0]; ctx->ovl.b_id = dev[1]; ctx->ovl.a_begin = dev[2]; ctx->ovl.a_end = dev[3];
-    ctx->ovl.b_begin = dev[4]; ctx->ovl.b_end = dev[5]; ctx->ovl.length = dev[6]; ctx->ovl.strand = dev_strand;
-    ctx->ovl.n = n;
-    ctx->ovl.base = 0;
-    ctx->tuple_mode = false;
-    ctx->blocks_mode = false;
-    ctx->dedupe_pending = false;
-    ctx->inputs_set = true;
-    ctx->valid_ready = false;
-    HIPCHECK(ctx->d_valid.ensure(n));
-    HIPCHECK(ctx->d_ev.ensure(4 * n + 8));
-    HIPCHECK(ctx->d_cls.ensure(n / 4 + 64));        // survivor masks of the second pass: two bits per overlap
-    for (int k = 0; k < 4; ++k) HIPCHECK(ctx->d_chunk[k].ensure(pass2_chunks(n) + 2));
-    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(n, ctx->n_reads) + 2)));
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    return RALA_HIP_OK;
-}
 
 static int initialize_stages(rala_hip_ctx* ctx);
 int rala_hip_initialize(rala_hip_ctx* ctx) {
@@ -2517,7 +2154,7 @@ int rala_hip_initialize(rala_hip_ctx* ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->copy);
         // (a call that left before it had queued the copies has uploaded nothing: the next reader does, flush_upload)
-        if (ctx->upload_queued) ctx->upload_pending = false;
+        if (ctx->upload_queued) upload_done(ctx);
     }
     ctx->upload_queued = false;
     return rc;
@@ -2530,11 +2167,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     const uint32_t n_reads = (uint32_t)ctx->n_reads;
     ctx->tm = rala_hip_timings();
     ctx->overlaps.clear(); ctx->internals.clear();
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    ctx->tail_on_device = ctx->host_stale = ctx->marks_on_device = false;
-
-    ctx->rowless = ctx->pile_rows == 0;
-    ctx->sens_csr_ready = false;
+    initialize_begun(ctx);
     ctx->rows_materialised = 0;
     if (ctx->rowless && ctx->debug_pile_stop_after != 99) {
         return fail(ctx, RALA_HIP_EINVAL, "debug_pile_stop_after is a diagnostic of the kernels that store rows: not with pile_rows = 0");
@@ -2846,7 +2479,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     if (uploading) {
         // (the host's columns are free from here on)
         HIPCHECK(hipStreamSynchronize(ctx->copy));
-        ctx->upload_pending = false;
+        upload_done(ctx);
     }
     const uint32_t slot_overflow = fixed ? small[6] : 0;
     if (small[8] && !slot_overflow) {
@@ -2869,8 +2502,6 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         ctx->use_fixed_buckets = keep;
         return rc_again;
     }
-    ctx->host_state_fresh = false;
-    ctx->pool_used = std::min(small[0], ctx->pool_cap);
     ctx->tm.pile_overflow_reads = ctx->use_run_kernel ? small[3] + small[4] : 0;      // event-dense + handed on
     if (getenv("RALA_HIP_TRACE") || getenv("RALA_HIP_TRACE_BUFFERS")) {
         fprintf(stderr, "[trace] buffers: events %p (CSR %p) slots %p counts %p piles %p a_id %p b_id %p b_begin %p\n", (void*)ctx->d_ev.p, (void*)ctx->d_ev_off.p, (void*)ctx->d_ev_fixed.p,
@@ -2904,12 +2535,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         ctx->tm.pool_regrown = regrown;
         return rc_again;
     }
-    ctx->n_prefiltered = n_dead;
-    ctx->ev_ready = true;
-    ctx->ev_fixed = fixed;
-    ctx->initialized = true;
-    ctx->valid_ready = !ctx->tuple_mode;
-    ctx->piles_resident = true;
+    state_installed(ctx, n_dead, std::min(small[0], ctx->pool_cap), true, fixed, !ctx->tuple_mode);
     if (ctx->n_prefiltered == ctx->n_reads) return fail(ctx, RALA_HIP_EFILTERED, "filtered all sequences");
     return RALA_HIP_OK;
 }
@@ -2923,7 +2549,7 @@ int rala_hip_dedupe(rala_hip_ctx* ctx) {
     launch_dedupe(ctx->ovl, (uint32_t)ctx->n_reads, ctx->d_suspect.p, ctx->d_valid.p, ctx->stream);
     HIPCHECK(stream_sync(ctx, ctx->stream));
     HIPCHECK(hipGetLastError());
-    ctx->valid_ready = true;
+    validity_bits_ready(ctx);
     return RALA_HIP_OK;
 }
 
@@ -2978,214 +2604,6 @@ int emit_bucketed(rala_hip_ctx* ctx, uint32_t world, uint64_t* tuples_dev, uint6
 }
 }  // namespace
 
-int rala_hip_get_device_state(rala_hip_ctx* ctx, rala_hip_device_state* out) {
-    if (!ctx || !out) return RALA_HIP_EINVAL;
-    if (!ctx->initialized) return fail(ctx, RALA_HIP_EINVAL, "not initialized");
-    out->begin = ctx->d_begin.p; out->end = ctx->d_end.p; out->median = ctx->d_median.p; out->p10 = ctx->d_p10.p;
-    out->alive = ctx->d_alive.p; out->n_pits = ctx->d_n_pits.p; out->n_hills = ctx->d_n_hills.p;
-    out->slot = ctx->d_iv_slot.p; out->pool = ctx->d_pool.p; out->pool_count = (size_t)ctx->pool_used;
-    out->valid = ctx->valid_ready ? ctx->d_valid.p : nullptr;
-    return RALA_HIP_OK;
-}
-
-int rala_hip_copy_device_state(rala_hip_ctx* ctx, const rala_hip_device_state* dst) {
-    if (!ctx || !dst) return RALA_HIP_EINVAL;
-    const bool per_read = dst->begin || dst->end || dst->median || dst->p10 || dst->alive || dst->n_pits ||
-                          dst->n_hills || dst->slot || dst->pool;
-    if (per_read && !ctx->initialized) return fail(ctx, RALA_HIP_EINVAL, "not initialized");
-    HIPCHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const uint64_t n = ctx->n_reads;
-    auto cp = [&](const void* to, const void* from, size_t bytes) -> hipError_t {
-        if (!to || bytes == 0) return hipSuccess;
-        return hipMemcpyAsync(const_cast<void*>(to), from, bytes, hipMemcpyDeviceToDevice, s);
-    };
-    HIPCHECK(cp(dst->begin, ctx->d_begin.p, n * 4));
-    HIPCHECK(cp(dst->end, ctx->d_end.p, n * 4));
-    HIPCHECK(cp(dst->median, ctx->d_median.p, n * 2));
-    HIPCHECK(cp(dst->p10, ctx->d_p10.p, n * 2));
-    HIPCHECK(cp(dst->alive, ctx->d_alive.p, n));
-    HIPCHECK(cp(dst->n_pits, ctx->d_n_pits.p, n * 4));
-    HIPCHECK(cp(dst->n_hills, ctx->d_n_hills.p, n * 4));
-    HIPCHECK(cp(dst->slot, ctx->d_iv_slot.p, n * 4));
-    if (dst->pool) {
-        if (dst->pool_count < (size_t)ctx->pool_used) return fail(ctx, RALA_HIP_ECAPACITY, "pool buffer too small");
-        HIPCHECK(cp(dst->pool, ctx->d_pool.p, (size_t)ctx->pool_used * sizeof(Interval)));
-    }
-    if (dst->valid) {
-        if (!ctx->valid_ready) return fail(ctx, RALA_HIP_EINVAL, "no validity bits on this context");
-        HIPCHECK(cp(dst->valid, ctx->d_valid.p, ctx->n_ovl));
-    }
-    HIPCHECK(stream_sync(ctx, s));
-    return RALA_HIP_OK;
-}
-
-int rala_hip_import_state_device(rala_hip_ctx* ctx, const rala_hip_device_state* in) {
-    if (!ctx || !in || !in->begin || !in->end || !in->median || !in->p10 || !in->alive || !in->n_pits ||
-        !in->n_hills || !in->slot) {
-        return RALA_HIP_EINVAL;
-    }
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_ovl && !in->valid) return fail(ctx, RALA_HIP_EINVAL, "valid bits required");
-    if (in->pool_count && !in->pool) return RALA_HIP_EINVAL;
-    HIPCHECK(hipSetDevice(ctx->device));
-    // (columns handed over with RALA_HIP_MEM_HOST_ASYNC leave inside rala_hip_initialize; a caller that installs the read state
-    // instead must not find them still on the host - advisor round 5)
-    { const int rcu = flush_upload(ctx); if (rcu != RALA_HIP_OK) return rcu; }
-    hipStream_t s = ctx->stream;
-    const uint64_t n = ctx->n_reads;
-    ctx->tm = rala_hip_timings();
-    ctx->overlaps.clear(); ctx->internals.clear();
-    if (in->pool_count > ctx->pool_cap) {
-        ctx->pool_cap = (uint32_t)in->pool_count + 1024;
-        HIPCHECK(ctx->d_pool.ensure(ctx->pool_cap));
-    }
-    const uint32_t small[8] = {(uint32_t)in->pool_count, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHECK(hipMemcpyAsync(ctx->d_small.p, small, sizeof(small), hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_begin.p, in->begin, n * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_end.p, in->end, n * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_median.p, in->median, n * 2, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_p10.p, in->p10, n * 2, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_alive.p, in->alive, n, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_n_pits.p, in->n_pits, n * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_n_hills.p, in->n_hills, n * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(ctx->d_iv_slot.p, in->slot, n * 4, hipMemcpyDeviceToDevice, s));
-    if (in->pool_count) {
-        HIPCHECK(hipMemcpyAsync(ctx->d_pool.p, in->pool, (size_t)in->pool_count * sizeof(Interval), hipMemcpyDeviceToDevice, s));
-    }
-    if (ctx->n_ovl) HIPCHECK(hipMemcpyAsync(ctx->d_valid.p, in->valid, ctx->n_ovl, hipMemcpyDeviceToDevice, s));
-    // host mirrors are fetched by the first getter; only the number of filtered reads is needed now
-    HIPCHECK(ctx->d_cc_flags.ensure(8));
-    HIPCHECK(hipMemsetAsync(ctx->d_cc_flags.p + 6, 0, 4, s));
-    launch_count_zero_u8(ctx->d_alive.p, (uint32_t)n, ctx->d_cc_flags.p + 6, s);
-    uint32_t n_dead = 0;
-    HIPCHECK(d2h_small(ctx, &n_dead, ctx->d_cc_flags.p + 6, 4, s));
-    HIPCHECK(stream_sync(ctx, s));
-    ctx->host_state_fresh = false;
-    ctx->pool_used = (uint32_t)in->pool_count;
-    ctx->n_prefiltered = n_dead;
-    ctx->initialized = true;
-    ctx->valid_ready = true;
-    ctx->constructed = false;
-    ctx->piles_resident = ctx->ev_ready = false;
-    ctx->tail_on_device = ctx->host_stale = ctx->marks_on_device = false;
-    if (ctx->n_prefiltered == n) return fail(ctx, RALA_HIP_EFILTERED, "filtered all sequences");
-    return RALA_HIP_OK;
-}
-
-int rala_hip_set_bound_tuples(rala_hip_ctx* ctx, const uint64_t* tuples, uint64_t n, int mem) {
-    if (!ctx || (n && !tuples)) return RALA_HIP_EINVAL;
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_EINVAL, "too many tuples");
-    HIPCHECK(hipSetDevice(ctx->device));
-    if (mem == RALA_HIP_MEM_DEVICE) {
-        ctx->tuples = (const uint2*)tuples;
-    } else {
-        HIPCHECK(ctx->d_tuple.ensure(n));
-        if (n) HIPCHECK(hipMemcpy(ctx->d_tuple.p, tuples, n * 8, hipMemcpyHostToDevice));
-        ctx->tuples = ctx->d_tuple.p;
-    }
-    ctx->n_tuples = n;
-    ctx->records = nullptr;
-    ctx->n_records = 0;
-    ctx->blocks_mode = false;
-    ctx->tuple_mode = true;
-    ctx->inputs_set = true;
-    ctx->n_ovl = 0;
-    ctx->ovl = OvlSoA();
-    HIPCHECK(ctx->d_ev.ensure(n + 8));
-    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(n, ctx->n_reads) + 2)));
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    return RALA_HIP_OK;
-}
-
-int rala_hip_set_bound_records(rala_hip_ctx* ctx, const uint64_t* records, uint64_t n, int mem) {
-    if (!ctx || (n && !records)) return RALA_HIP_EINVAL;
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (n >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_EINVAL, "too many records");
-    if (!rala_hip_bound_records_fit(ctx, 1)) return fail(ctx, RALA_HIP_EINVAL, "reads too long or too many for bound records");
-    HIPCHECK(hipSetDevice(ctx->device));
-    if (mem == RALA_HIP_MEM_DEVICE) {
-        ctx->records = records;
-    } else {
-        HIPCHECK(ctx->d_record.ensure(n + 8));
-        if (n) HIPCHECK(hipMemcpy(ctx->d_record.p, records, n * 8, hipMemcpyHostToDevice));
-        ctx->records = ctx->d_record.p;
-    }
-    if (!ctx->records) { HIPCHECK(ctx->d_record.ensure(8)); ctx->records = ctx->d_record.p; }   // (an empty share)
-    ctx->n_records = n;
-    ctx->tuples = nullptr;
-    ctx->n_tuples = 2 * n;              // (what the tuple paths would see)
-    ctx->blocks_mode = false;
-    ctx->tuple_mode = true;
-    ctx->inputs_set = true;
-    ctx->n_ovl = 0;
-    ctx->ovl = OvlSoA();
-    HIPCHECK(ctx->d_ev.ensure(2 * n + 8));
-    HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes(std::max<uint64_t>(2 * n, ctx->n_reads) + 2)));
-    ctx->initialized = ctx->constructed = ctx->ev_ready = false;
-    return RALA_HIP_OK;
-}
-
-int rala_hip_import_state(rala_hip_ctx* ctx, const uint8_t* valid, const uint32_t* begin, const uint32_t* end,
-                          const uint16_t* median, const uint16_t* p10, const uint8_t* alive,
-                          const uint64_t* pits_off, const uint32_t* pits_pairs, const uint32_t* pits_aux,
-                          const uint64_t* hills_off, const uint32_t* hills_pairs) {
-    if (!ctx || !begin || !end || !median || !p10 || !alive || !pits_off || !hills_off) return RALA_HIP_EINVAL;
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_ovl && !valid) return fail(ctx, RALA_HIP_EINVAL, "valid bits required");
-    HIPCHECK(hipSetDevice(ctx->device));
-    const uint64_t n = ctx->n_reads;
-    ctx->tm = rala_hip_timings();
-    ctx->overlaps.clear(); ctx->internals.clear();
-    std::vector<uint32_t> np(n), nh(n);
-    std::vector<uint32_t> slot(n, 0xFFFFFFFFu);
-    std::vector<Interval> pool;
-    for (uint64_t r = 0; r < n; ++r) {
-        const uint64_t a = pits_off[r + 1] - pits_off[r], b = hills_off[r + 1] - hills_off[r];
-        if (a > 0xFFFFFFFFull || b > 0xFFFFFFFFull) return fail(ctx, RALA_HIP_EINVAL, "too many intervals on a read");
-        np[r] = (uint32_t)a; nh[r] = (uint32_t)b;
-        if (a + b == 0) continue;
-        slot[r] = (uint32_t)pool.size();
-        for (uint64_t k = pits_off[r]; k < pits_off[r + 1]; ++k) {
-            Interval iv; iv.first = pits_pairs[2 * k]; iv.second = pits_pairs[2 * k + 1]; iv.aux = pits_aux[k];
-            pool.push_back(iv);
-        }
-        for (uint64_t k = hills_off[r]; k < hills_off[r + 1]; ++k) {
-            Interval iv; iv.first = hills_pairs[2 * k]; iv.second = hills_pairs[2 * k + 1]; iv.aux = 0;
-            pool.push_back(iv);
-        }
-    }
-    if (pool.size() > ctx->pool_cap) {
-        ctx->pool_cap = (uint32_t)pool.size() + 1024;
-        HIPCHECK(ctx->d_pool.ensure(ctx->pool_cap));
-    }
-    const uint32_t used = (uint32_t)pool.size();
-    uint32_t small[8] = {used, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHECK(hipMemcpy(ctx->d_small.p, small, sizeof(small), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_begin.p, begin, n * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_end.p, end, n * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_median.p, median, n * 2, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_p10.p, p10, n * 2, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_alive.p, alive, n, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_n_pits.p, np.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_n_hills.p, nh.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ctx->d_iv_slot.p, slot.data(), n * 4, hipMemcpyHostToDevice));
-    if (used) HIPCHECK(hipMemcpy(ctx->d_pool.p, pool.data(), (size_t)used * sizeof(Interval), hipMemcpyHostToDevice));
-    if (ctx->n_ovl) HIPCHECK(hipMemcpy(ctx->d_valid.p, valid, ctx->n_ovl, hipMemcpyHostToDevice));
-    const int rc = download_read_state(ctx);
-    if (rc != RALA_HIP_OK) return rc;
-    ctx->n_prefiltered = 0;
-    for (uint64_t r = 0; r < n; ++r) if (!ctx->h_alive[r]) ++ctx->n_prefiltered;
-    ctx->initialized = true;
-    ctx->valid_ready = true;
-    ctx->constructed = false;
-    ctx->piles_resident = ctx->ev_ready = false;
-    ctx->tail_on_device = ctx->host_stale = ctx->marks_on_device = false;
-    if (ctx->n_prefiltered == n) return fail(ctx, RALA_HIP_EFILTERED, "filtered all sequences");
-    return RALA_HIP_OK;
-}
-
 int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_t n_sens) {
     if (!ctx) return RALA_HIP_EINVAL;
     // (the state first, as construct_stages asks again: which error a caller gets does not depend on its sensitive overlaps)
@@ -3205,19 +2623,18 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
         // Graph::preprocess(sensitive overlaps) (graph.cpp:882-1054) works on the lists the chimera stage leaves on the
         // device: repeats annotated, the graph built from what is left
         rc = repeats_stage(ctx, ctx, nullptr, sens, n_sens);
-        if (rc != RALA_HIP_OK) ctx->constructed = false;
+        if (rc != RALA_HIP_OK) construct_failed(ctx);
         return rc;
     }
     // ---- the cross-check path (use_gpu_tail = 0): pass 2, then the tail on the host ----
-    ctx->have_repeats = false;
+    construct_begun(ctx);
     hipStream_t s = ctx->stream;
     const uint32_t n_reads = (uint32_t)ctx->n_reads;
     rc = pass2(ctx, nullptr);
     if (rc != RALA_HIP_OK) return rc;
     const uint32_t M = ctx->t_n0 + ctx->t_n1;
     const uint32_t n_surv[2] = {ctx->t_n0, ctx->t_n1};
-    ctx->tail_on_device = false;
-    ctx->host_stale = false;
+    tail_begun(ctx);
     // lists to the host
     std::vector<HostOvl>* lists[2] = {&ctx->overlaps, &ctx->internals};
     for (int f = 0; f < 8; ++f) {
@@ -3279,7 +2696,7 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
     HIPCHECK(hipMemcpyAsync(ctx->d_end.p, ctx->h_end.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(ctx->d_alive.p, ctx->h_alive.data(), (size_t)n_reads, hipMemcpyHostToDevice, s));
     HIPCHECK(stream_sync(ctx, s));
-    ctx->constructed = true;
+    constructed(ctx);
     return RALA_HIP_OK;
 }
 
@@ -3350,8 +2767,8 @@ int rala_hip_find_repetitive_hills(rala_hip_ctx* ctx, uint64_t read, uint32_t be
     ctx->h_rep_pool.resize(small[6]);
     if (small[6]) HIPCHECK(hipMemcpy(ctx->h_rep_pool.data(), ctx->d_rep_pool.p, (size_t)small[6] * sizeof(Interval), hipMemcpyDeviceToHost));
     ctx->n_rep_hills = small[6];
-    ctx->rep_host_stale = false;
-    ctx->have_repeats = true;
+    repeat_hills_fetched(ctx);
+    repeat_hills_found(ctx);
     return RALA_HIP_OK;
 }
 
@@ -3547,7 +2964,7 @@ int rala_hip_get_graph(rala_hip_ctx* ctx, uint32_t* node_read, uint32_t* src, ui
         HIPCHECK(hipSetDevice(ctx->device));
         ctx->e_mark.resize(ctx->t_n_edges);
         if (ctx->t_n_edges) HIPCHECK(hipMemcpy(ctx->e_mark.data(), ctx->d_tr_marks.p, ctx->t_n_edges, hipMemcpyDeviceToHost));
-        ctx->marks_on_device = false;
+        marks_fetched(ctx);
     }
     if (node_read) memcpy(node_read, ctx->node_read.data(), ctx->node_read.size() * 4);
     const size_t ne = ctx->e_src.size();

@@ -36,8 +36,8 @@
 #include <thread>
 
 #include "comm.h"
-#include "context.h"
 #include "ingest_formats.h"
+#include "lifecycle.h"
 #include "stages.h"
 
 using namespace rala_hip;
@@ -595,8 +595,7 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
         else if (!S_ISREG(st.st_mode)) rc = mg_fail(mg, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
         else file_n = (uint64_t)st.st_size;
     }
-    cs->inputs_set = false;
-    cs->n_ovl = 0;
+    inputs_dropped(cs);
     if (rc == RALA_HIP_OK) {
         // (a plain file: bytes [n me / P, n (me + 1) / P); a compressed one is text like any other unless the option says otherwise)
         PartKinds take;
