@@ -375,6 +375,45 @@ typedef struct rala_hip_sequence_slice_info {
     float copy_ms;                  /* of those: the packed bases device -> host */
 } rala_hip_sequence_slice_info;
 int rala_hip_get_sequence_slice_info(rala_hip_ctx* ctx, rala_hip_sequence_slice_info* out);
+/* ---- node bases as spans: a table of bases on the device, and the bytes that lists of spans of it spell ----------------
+ * The nodes of the assembly graph need no base between Graph::construct and the output (src/graph.cpp:133-170 concatenates
+ * strings for every unitig, :2042-2116 prints them): a node is a list of spans of reads, and its bytes are written once.
+ *
+ * The table belongs to the context and to nothing else in it: rala_hip_set_reads, rala_hip_initialize and rala_hip_construct
+ * neither need nor drop it, rala_hip_destroy frees it; one table per context.  Source s is bases[base_off[s] .. base_off[s + 1])
+ * - base_off always HOST memory (n_sources + 1 entries, kept by the context to check spans against), `bases` host
+ * (RALA_HIP_MEM_HOST) or device memory (RALA_HIP_MEM_DEVICE); either way the bytes are COPIED into the context.  The call
+ * replaces an earlier table; n_sources = 0 releases it.  RALA_HIP_EINVAL: offsets that decrease or do not begin at 0 - the
+ * table that was there stays; RALA_HIP_ENOMEM leaves no table.
+ * With the option "keep_bases" set, a successful rala_hip_slice_sequences leaves the packed bases it gathered on the device as
+ * this table - source k the whole read wanted[k], the offsets its base_off; its `bases` may then be NULL and nothing is copied
+ * to the host.  The windows' gather then writes into one buffer of the full size: RALA_HIP_ENOMEM for it is returned with
+ * nothing set (repeat the call without the option); *irregular != 0 leaves no table. */
+int rala_hip_set_bases(rala_hip_ctx* ctx, const uint8_t* bases, const uint64_t* base_off, uint64_t n_sources, int mem);
+/* Bytes [first, first + len) of source `source`: out[j] = B[first + j], or (rc = 1) out[j] = comp(B[first + len - 1 - j]) with
+ * comp A <-> T, C <-> G in upper case and every other byte unchanged (Sequence::create_reverse_complement, src/sequence.cpp).
+ * A span of length 0 spells nothing. */
+typedef struct rala_hip_span {
+    uint32_t source, first, len, rc;
+} rala_hip_span;
+/* out (host memory, out_bytes bytes) receives what the spans spell, one after the other; where one record ends and the next
+ * begins is the caller's business.  Checked on the host before anything is enqueued - a refused call touches nothing
+ * (RALA_HIP_EINVAL): there is a table, source < n_sources, first + len within the source (64-bit arithmetic), rc 0 or 1, the
+ * lengths sum to out_bytes; n_spans >= 2^32: RALA_HIP_ETOOLARGE.  n_spans = 0 or out_bytes = 0 enqueues nothing.  The output
+ * leaves the device in windows (option "spell_window_mb", 256; "debug_spell_window": bytes, rounded down to whole 16 KB tiles,
+ * one at least): one launch and one copy per window. */
+int rala_hip_spell(rala_hip_ctx* ctx, const rala_hip_span* spans, uint64_t n_spans, uint8_t* out, uint64_t out_bytes);
+/* The table, and the last rala_hip_spell. */
+typedef struct rala_hip_spell_info {
+    uint64_t sources, source_bytes; /* the table (0, 0: none) */
+    uint64_t spans, bytes;          /* the last call: spans taken, bytes spelled */
+    uint64_t windows, launches;
+    float upload_ms;                /* the spans and their output offsets to the device */
+    float kernel_ms;                /* the windows' kernels */
+    float copy_ms;                  /* the windows' bytes device -> host */
+    uint32_t from_slice;            /* 1: the table is what rala_hip_slice_sequences gathered (option "keep_bases") */
+} rala_hip_spell_info;
+int rala_hip_get_spell_info(rala_hip_ctx* ctx, rala_hip_spell_info* out);
 /* The CRC32 of n pieces laid end to end (no context, no device), from every piece's CRC REGISTER - started from zero, no final
  * inversion: zlib's crc32(piece) ^ crc32(as many zero bytes) - and its length: how the windowed inflater chains its windows. */
 uint32_t rala_hip_crc32_chain(const uint32_t* reg, const uint64_t* len, uint64_t n);

@@ -70,6 +70,9 @@ def build_hip(force=False, jobs=None):
     out = os.path.join(d, "librala_hip.so")
     srcs = _glob(d, (".hip",))
     hdrs = _glob(d, (".h", ".hpp")) + _glob(os.path.join(ROOT, "include"), (".h",))
+    # (a library newer than every source and header is current, whether or not the objects it was linked from are still there)
+    if not force and not _stale(out, srcs + hdrs):
+        return out
     obj_dir = os.path.join(PKG, "_build")
     os.makedirs(obj_dir, exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

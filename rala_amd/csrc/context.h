@@ -290,6 +290,19 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint8_t> d_gzip_hold, d_slice_out;
     rala_hip::DevBuf<uint64_t> d_slice_w[3];
     rala_hip_sequence_slice_info slice_info = {};
+    // the table of bases that spans speak of (spell.hip: rala_hip_set_bases, or what rala_hip_slice_sequences gathered with
+    // the option keep_bases) - the context's, whatever happens to its reads and piles - and what rala_hip_spell uploads and
+    // fills per call: the spans, their output offsets, a window of output
+    bool keep_bases = false;                    // option
+    uint32_t spell_window_mb = 256;             // option: what a window of spelled bytes may take
+    int64_t debug_spell_window = 0;             // tests: the window in bytes (whole tiles, one at least)
+    rala_hip::DevBuf<uint8_t> d_bases, d_spell_out;
+    rala_hip::DevBuf<uint64_t> d_base_off, d_spell_off;
+    rala_hip::DevBuf<rala_hip_span> d_spell_spans;
+    std::vector<uint64_t> h_base_off;           // n_base_sources + 1 entries; empty: no table
+    uint64_t n_base_sources = 0;
+    bool bases_from_slice = false;
+    rala_hip_spell_info spell_info = {};
 
     // overlaps
     uint64_t n_ovl = 0;

@@ -196,6 +196,9 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "debug_gzip_false_sync")) { ctx->debug_gzip_false_sync = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "pile_rows")) { ctx->pile_rows = value ? 1u : 0u; return RALA_HIP_OK; }
     if (!strcmp(key, "pile_rows_scratch_mb")) { ctx->pile_rows_scratch_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
+    if (!strcmp(key, "keep_bases")) { ctx->keep_bases = value != 0; return RALA_HIP_OK; }
+    if (!strcmp(key, "spell_window_mb")) { ctx->spell_window_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
+    if (!strcmp(key, "debug_spell_window")) { ctx->debug_spell_window = std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "pile_chunk_mb")) { ctx->pile_chunk_mb = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_ev_events")) { ctx->debug_ev_events = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_count_window")) { ctx->debug_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }

@@ -3,6 +3,7 @@
 #include <memory>
 
 #include "ingest_common.h"
+#include "spell.h"
 
 using namespace rala_hip;
 using namespace rala_hip::ingest;
@@ -360,9 +361,13 @@ int rala_hip_get_sequence_timings(rala_hip_ctx* ctx, rala_hip_ingest_timings* ou
 
 int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t* wanted, uint64_t n_wanted, const uint64_t* base_off,
                              uint8_t* bases, uint32_t threads, int* irregular) {
-    if (!ctx || !path || !irregular || !base_off || (n_wanted && !wanted) || (!bases && base_off[n_wanted])) return RALA_HIP_EINVAL;
+    if (!ctx || !path || !irregular || !base_off || (n_wanted && !wanted) || (!bases && base_off[n_wanted] && !ctx->keep_bases)) return RALA_HIP_EINVAL;
     *irregular = 0;
     ctx->slice_info = rala_hip_sequence_slice_info();
+    // option keep_bases: the packed bases stay on the device as the context's table of bases (spell.hip) - the windows'
+    // gather writes into it, a host copy is made only where one is asked for.  Whatever was the table is gone first.
+    const bool keep = ctx->keep_bases;
+    if (keep) bases_released(ctx);
     if (!ctx->seq_index_valid) { *irregular = 64; return RALA_HIP_OK; }
     HIPCHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -393,13 +398,19 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
     uint64_t file_n = 0;
     if (open_regular(ctx, path, file, &file_n) != RALA_HIP_OK || file_n != ctx->seq_file_n) { *irregular = 64; return RALA_HIP_OK; }
     if (!n_w) return RALA_HIP_OK;
+    if (keep && ctx->d_bases.ensure(n_bases) != hipSuccess) {
+        bases_released(ctx);
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the kept bases");
+    }
     // whatever way this call ends, the wanted reads, a window's bases and the source's buffers do not stay the context's
     struct Release {
         rala_hip_ctx* ctx;
+        bool kept = false;                  // the table of bases was adopted: it stays
         ~Release() {
             source_close(ctx);
             ctx->d_slice_out.release();
             for (int k = 0; k < 3; ++k) ctx->d_slice_w[k].release();
+            if (ctx->keep_bases && !kept) bases_released(ctx);
         }
     } release{ctx};
     for (int k = 0; k < 3; ++k) HIPCHECK(ctx->d_slice_w[k].ensure(n_w));
@@ -463,18 +474,19 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
                 if (out_hi < out_lo || out_hi > n_bases || out_hi - out_lo > w.n) { flags = kSeqSliceMismatch; break; }
                 const uint64_t out_n = out_hi - out_lo;
                 if (out_n) {
-                    if (ctx->d_slice_out.ensure(out_n) != hipSuccess) { rc = fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's bases"); break; }
+                    if (!keep && ctx->d_slice_out.ensure(out_n) != hipSuccess) { rc = fail(ctx, RALA_HIP_ENOMEM, "device memory for a window's bases"); break; }
+                    uint8_t* const d_out = keep ? ctx->d_bases.p + out_lo : ctx->d_slice_out.p;
                     SequenceGather G;
                     G.text = w.text; G.n = w.n; G.text_off = lo;
                     G.tile_stripped0 = ctx->d_seq_tile[1].p; G.stripped0 = n_stripped;
                     G.w_off = ctx->d_slice_w[0].p; G.w_end = ctx->d_slice_w[1].p; G.w_adj = ctx->d_slice_w[2].p;
                     G.k_lo = k_lo; G.k_hi = k_hi;
-                    G.out_lo = out_lo; G.out_n = out_n; G.out = ctx->d_slice_out.p; G.flags = ctx->d_seq_flags.p;
+                    G.out_lo = out_lo; G.out_n = out_n; G.out = d_out; G.flags = ctx->d_seq_flags.p;
                     const double tg = now_ms();
                     launch_sequence_gather(G, s);
                     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { rc = fail(ctx, RALA_HIP_EDEVICE, "the gather kernel failed"); break; }
                     const double tc = now_ms();
-                    if (hipMemcpyAsync(bases + out_lo, ctx->d_slice_out.p, out_n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    if ((bases && hipMemcpyAsync(bases + out_lo, d_out, out_n, hipMemcpyDeviceToHost, s) != hipSuccess) ||
                         hipMemcpyAsync(&flags, ctx->d_seq_flags.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
                         rc = fail(ctx, RALA_HIP_EDEVICE, "copying a window's bases failed");
                         break;
@@ -506,6 +518,11 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
                 (unsigned long)ctx->slice_info.bases, (unsigned long)n_wanted, S.ship_ms, kernel_ms, gather_ms, copy_ms, S.flag | flags);
     }
     if (S.flag || flags) *irregular = (int)(S.flag | flags);
+    if (keep && !*irregular) {
+        const int rck = bases_adopted(ctx, base_off, n_wanted, true);
+        if (rck != RALA_HIP_OK) return rck;
+        release.kept = true;
+    }
     return RALA_HIP_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gzip_types.h"
+#include "rala_hip.h"
 
 namespace rala_hip {
 
@@ -587,6 +588,24 @@ struct SequenceGather {
     uint32_t* flags;
 };
 void launch_sequence_gather(const SequenceGather& G, hipStream_t s);
+
+// ---- spans of a table of bases -> bytes (spell_kernels.hip) -----------------------------------
+// The table: source s is bases[base_off[s] .. base_off[s + 1]).  Span k ({source, first, len, rc}: rala_hip_span) spells
+// output bytes [out_off[k], out_off[k + 1]) - out_off the exclusive scan of the lengths, n_spans + 1 entries - forwards, or
+// (rc = 1) backwards and complemented.  One launch writes output bytes [lo, hi) to out (out[0] is byte lo; lo a multiple of
+// spell_tile_bytes(), out 16-byte aligned with room up to the next multiple of the tile behind hi - lo).  The caller has
+// checked every span against the table: the kernel reads where the spans say.
+struct SpellArgs {
+    const uint8_t* bases;
+    const uint64_t* base_off;
+    const rala_hip_span* spans;
+    const uint64_t* out_off;
+    uint32_t n_spans;
+    uint64_t lo, hi;
+    uint8_t* out;
+};
+uint32_t spell_tile_bytes();
+void launch_spell(const SpellArgs& A, hipStream_t s);
 
 // ---- BGZF members -> text (inflate_kernels.hip) ---------------------------------------------
 // one gzip member of a BGZF file: its raw-deflate bytes at comp + comp_off (deflate_len of them, then CRC32 and ISIZE), its

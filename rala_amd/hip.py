@@ -39,6 +39,7 @@ SYMBOLS = (
     "rala_hip_build_name_table", "rala_hip_get_name_table", "rala_hip_copy_name_table", "rala_hip_name_hash",
     "rala_hip_get_name_table_info",
     "rala_hip_slice_sequences", "rala_hip_get_sequence_slice_info", "rala_hip_crc32_chain",
+    "rala_hip_set_bases", "rala_hip_spell", "rala_hip_get_spell_info",
     "rala_hip_mg_destroy", "rala_hip_mg_last_error", "rala_hip_mg_set_reads", "rala_hip_mg_slice_cuts",
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
     "rala_hip_mg_owner_context",
@@ -117,6 +118,15 @@ class SequenceSliceInfo(ctypes.Structure):
     """rala_hip_sequence_slice_info"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("windows", "max_window_text_bytes", "bases")] + [(n, ctypes.c_float) for n in (
         "ship_ms", "kernel_ms", "gather_ms", "copy_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SpellInfo(ctypes.Structure):
+    """rala_hip_spell_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("sources", "source_bytes", "spans", "bytes", "windows", "launches")] + [(n, ctypes.c_float) for n in (
+        "upload_ms", "kernel_ms", "copy_ms")] + [("from_slice", ctypes.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -220,6 +230,9 @@ def lib(build=True):
         L.rala_hip_get_overlap_columns.argtypes = [vp, ctypes.POINTER(u64), vp, vp]
         L.rala_hip_slice_sequences.argtypes = [vp, ctypes.c_char_p, vp, u64, vp, vp, u32, ctypes.POINTER(i32)]
         L.rala_hip_get_sequence_slice_info.argtypes = [vp, ctypes.POINTER(SequenceSliceInfo)]
+        L.rala_hip_set_bases.argtypes = [vp, vp, vp, u64, i32]
+        L.rala_hip_spell.argtypes = [vp, vp, u64, vp, u64]
+        L.rala_hip_get_spell_info.argtypes = [vp, ctypes.POINTER(SpellInfo)]
         L.rala_hip_crc32_chain.argtypes = [vp, vp, u64]
         L.rala_hip_crc32_chain.restype = u32
         L.rala_hip_gzip_chain.argtypes = [vp] * 6 + [u64, u64, u32, u64, ctypes.POINTER(u64)] + [vp] * 4 + [ctypes.POINTER(GzipTimings), ctypes.POINTER(i32)]
@@ -437,20 +450,49 @@ class Context:
         out["strand"] = strand[:n.value]
         return out
 
-    def slice_sequences(self, path, wanted, length, threads=4):
+    def slice_sequences(self, path, wanted, length, threads=4, host_copy=True):
         """rala_hip_slice_sequences: the bases of the reads `wanted` (ascending records of the current index; length = the
         index's lengths) cut out of the file on the device -> (irregular, bases, base_off); bases (None when refused) is one
-        uint8 array, read wanted[k]'s bases are bases[base_off[k]:base_off[k + 1]]"""
+        uint8 array, read wanted[k]'s bases are bases[base_off[k]:base_off[k + 1]].  host_copy False (with the option
+        keep_bases): `bases` is NULL - the bases stay on the device as the table of bases - and None comes back"""
         wanted = np.ascontiguousarray(wanted, dtype=np.uint64)
         base_off = np.zeros(len(wanted) + 1, dtype=np.uint64)
         np.cumsum(np.asarray(length, dtype=np.uint64)[wanted.astype(np.int64)], out=base_off[1:])
-        bases = np.zeros(max(int(base_off[-1]), 1), dtype=np.uint8)
+        bases = np.zeros(max(int(base_off[-1]), 1), dtype=np.uint8) if host_copy else None
         irregular = ctypes.c_int(0)
         self._check(self.L.rala_hip_slice_sequences(self.h, os.fsencode(path), wanted.ctypes.data, len(wanted), base_off.ctypes.data,
-                                                    bases.ctypes.data, threads, ctypes.byref(irregular)))
-        if irregular.value:
+                                                    bases.ctypes.data if host_copy else None, threads, ctypes.byref(irregular)))
+        if irregular.value or not host_copy:
             return irregular.value, None, base_off
         return 0, bases[:int(base_off[-1])], base_off
+
+    # ---- node bases as spans: the table of bases and what spans of it spell ----
+    def set_bases(self, bases, base_off, device_ptr=None):
+        """rala_hip_set_bases: source s is bases[base_off[s]:base_off[s + 1]] (uint8 array; or device_ptr: the bytes lie in
+        device memory there); no sources: the table is released"""
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        n = max(len(base_off) - 1, 0)
+        if device_ptr is not None:
+            ptr, mem = device_ptr, MEM_DEVICE
+        else:
+            bases = np.zeros(0, dtype=np.uint8) if bases is None else np.ascontiguousarray(bases, dtype=np.uint8)
+            ptr, mem = (bases.ctypes.data if len(bases) else None), MEM_HOST
+        self._check(self.L.rala_hip_set_bases(self.h, ptr, base_off.ctypes.data if len(base_off) else None, n, mem))
+
+    def spell(self, spans, out=None, out_bytes=None):
+        """rala_hip_spell: spans an (n, 4) uint32 array of (source, first, len, rc) -> what they spell, one uint8 array (out: the
+        array to fill, out_bytes: what to tell the call it holds - the tests of the refusals)"""
+        spans = np.ascontiguousarray(spans, dtype=np.uint32).reshape(-1, 4)
+        total = int(spans[:, 2].astype(np.uint64).sum()) if out_bytes is None else int(out_bytes)
+        if out is None:
+            out = np.zeros(max(total, 1), dtype=np.uint8)
+        self._check(self.L.rala_hip_spell(self.h, spans.ctypes.data if len(spans) else None, len(spans), out.ctypes.data, total))
+        return out[:total]
+
+    def spell_info(self):
+        t = SpellInfo()
+        self._check(self.L.rala_hip_get_spell_info(self.h, ctypes.byref(t)))
+        return t.as_dict()
 
     def sequence_slice_info(self):
         t = SequenceSliceInfo()

@@ -20,6 +20,8 @@ namespace rala {
 
 void AssemblyGraph::add_sequence_nodes(uint64_t sequence_id, const std::string& name, const std::string& data,
     const std::string& reverse_complement) {
+    if (bases_ == Bases::kSpans) return;
+    bases_ = Bases::kStrings;
     for (int rc = 0; rc < 2; ++rc) {
         Node n;
         n.id = nodes_.size();
@@ -30,6 +32,40 @@ void AssemblyGraph::add_sequence_nodes(uint64_t sequence_id, const std::string& 
         n.alive = true;
         nodes_.push_back(std::move(n));
     }
+}
+
+bool AssemblyGraph::add_sequence_node_spans(uint64_t sequence_id, const std::string& name, uint32_t source, uint32_t first,
+    uint32_t len) {
+    if (bases_ == Bases::kStrings) return false;
+    bases_ = Bases::kSpans;
+    for (uint32_t rc = 0; rc < 2; ++rc) {
+        Node n;
+        n.id = nodes_.size();
+        n.name = name;
+        Span s;
+        s.source = source; s.first = first; s.len = len; s.rc = rc;
+        n.spans.assign(1, s);
+        n.size = len;
+        n.spanned = true;
+        n.sequence_ids.assign(1, sequence_id);
+        n.is_first_rc = n.is_last_rc = rc != 0;
+        n.alive = true;
+        nodes_.push_back(std::move(n));
+    }
+    return true;
+}
+
+int AssemblyGraph::spell(const std::vector<uint64_t>& ids, std::string& bytes, std::vector<uint64_t>& off) const {
+    std::vector<Span> spans;
+    off.assign(1, 0);
+    for (uint64_t id : ids) {
+        const Node& n = nodes_[id];
+        spans.insert(spans.end(), n.spans.begin(), n.spans.end());
+        off.push_back(off.back() + n.size);
+    }
+    bytes.assign(off.back(), '\0');
+    if (!speller_) return -1;
+    return speller_(spans.data(), spans.size(), (uint8_t*)&bytes[0], bytes.size());
 }
 
 void AssemblyGraph::add_edge(uint32_t begin_node, uint32_t end_node, uint32_t length) {
@@ -468,21 +504,42 @@ uint32_t AssemblyGraph::append_unitig(uint32_t begin_node, uint32_t end_node) {
     u.id = nodes_.size();
     u.alive = true;
     u.is_first_rc = nodes_[begin_node].is_first_rc;
+    u.spanned = span_mode();
+    // span mode: substr(0, p) of a span list - min(p, all) bytes (substr clamps; an edge's length may be beyond its node's),
+    // the span that is cut keeps its first q bytes: of a reverse span those are the LAST q of its source range
+    uint64_t spelled = 0;
+    auto take = [&](const Node& n, uint64_t p) {
+        uint64_t left = std::min<uint64_t>(p, n.size);
+        spelled += left;
+        for (const Span& s : n.spans) {
+            if (!left) break;
+            Span t = s;
+            if (s.len > left) {
+                t.len = (uint32_t)left;
+                if (s.rc) t.first = s.first + s.len - t.len;
+            }
+            u.spans.push_back(t);
+            left -= t.len;
+        }
+    };
     uint32_t node = begin_node;
     while (true) {
         const Edge& edge = edges_[nodes_[node].suffix_edges[0]];
-        u.data += nodes_[node].data.substr(0, edge.length);
+        if (u.spanned) take(nodes_[node], edge.length);
+        else u.data += nodes_[node].data.substr(0, edge.length);
         u.sequence_ids.insert(u.sequence_ids.end(), nodes_[node].sequence_ids.begin(), nodes_[node].sequence_ids.end());
         u.is_last_rc = nodes_[node].is_last_rc;
         node = edge.end_node;
         if (node == end_node) break;
     }
     if (begin_node != end_node) {
-        u.data += nodes_[end_node].data;
+        if (u.spanned) take(nodes_[end_node], nodes_[end_node].size);
+        else u.data += nodes_[end_node].data;
         u.sequence_ids.insert(u.sequence_ids.end(), nodes_[end_node].sequence_ids.begin(),
             nodes_[end_node].sequence_ids.end());
         u.is_last_rc = nodes_[end_node].is_last_rc;
     }
+    u.size = (uint32_t)spelled;
     nodes_.push_back(std::move(u));
     return (uint32_t)nodes_.size() - 1;
 }
@@ -654,12 +711,32 @@ void AssemblyGraph::write_gfa(FILE* graph_file) const {
     auto name_of = [&](const Node& n) -> const std::string& {
         return !n.name.empty() ? n.name : unitig_name[n.id];
     };
+    // span mode: the bytes of all segments with one call of the speller
+    std::string bytes;
+    std::vector<uint64_t> off;
+    if (span_mode()) {
+        std::vector<uint64_t> ids;
+        for (const auto& it : nodes) {
+            if (it.alive && !it.is_rc() && !(it.outdegree() == 0 && it.indegree() == 0)) ids.push_back(it.id);
+        }
+        if (spell(ids, bytes, off) != 0) {
+            fprintf(stderr, "[rala::Graph::print_gfa] error: the nodes' bases could not be spelled\n");
+            exit(1);
+        }
+    }
+    size_t segment = 0;
     for (const auto& it : nodes) {
         if (!it.alive || it.is_rc() || (it.outdegree() == 0 && it.indegree() == 0)) continue;
         if (it.name.empty()) {
             const std::string name = "Utg" + std::to_string(unitig_id++);
             unitig_name[it.id] = name;
             unitig_name[it.id ^ 1] = name;
+        }
+        if (span_mode()) {
+            fprintf(graph_file, "S\t%s\t%s\tLN:i:%zu\tRC:i:%lu\n", name_of(it).c_str(),
+                bytes.substr(off[segment], off[segment + 1] - off[segment]).c_str(), (size_t)it.size, it.sequence_ids.size());
+            ++segment;
+            continue;
         }
         fprintf(graph_file, "S\t%s\t%s\tLN:i:%zu\tRC:i:%lu\n", name_of(it).c_str(), it.data.c_str(), it.data.size(),
             it.sequence_ids.size());
@@ -669,7 +746,7 @@ void AssemblyGraph::write_gfa(FILE* graph_file) const {
         const auto& b = nodes[it.begin_node];
         const auto& e = nodes[it.end_node];
         fprintf(graph_file, "L\t%s\t%c\t%s\t%c\t%zuM\n", name_of(b).c_str(), b.is_rc() ? '-' : '+',
-            name_of(e).c_str(), e.is_rc() ? '-' : '+', b.data.size() - it.length);
+            name_of(e).c_str(), e.is_rc() ? '-' : '+', (span_mode() ? (size_t)b.size : b.data.size()) - it.length);
     }
 }
 

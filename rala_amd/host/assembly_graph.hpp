@@ -16,6 +16,11 @@
  * Index based: nodes and edges live in two vectors and refer to each other by position;
  * objects are created in pairs (forward, reverse complement), so the twin of object k is k ^ 1.
  * Plain host code - the graphs are small (about 1 % of the overlaps survive to here).
+ *
+ * A node's bases are held in one of two ways, one per graph: as a string (add_sequence_nodes), or as a list of SPANS of
+ * rows of a table of bases that somebody else keeps (add_sequence_node_spans) - nothing between construct and the output
+ * looks at a base, only at lengths, so a unitig is a list of spans and its bytes are written once, at the end, by the
+ * owner's speller.
  */
 
 #pragma once
@@ -33,17 +38,25 @@ namespace rala {
 
 class AssemblyGraph {
 public:
+    /*! @brief bytes [first, first + len) of row `source` of the table of bases; rc = 1: read backwards and complemented
+     *  (Sequence::create_reverse_complement's rule).  The layout of rala_hip_span. */
+    struct Span {
+        uint32_t source = 0, first = 0, len = 0, rc = 0;
+    };
     struct Node {
         uint64_t id = 0;
         std::string name;                   // empty for unitigs
-        std::string data;
+        std::string data;                   // string mode
+        std::vector<Span> spans;            // span mode: what the node spells, in order; `size` bytes in all
+        uint32_t size = 0;
+        bool spanned = false;
         std::vector<uint32_t> prefix_edges, suffix_edges;       // edge ids, insertion order
         std::vector<uint64_t> sequence_ids;
         bool is_first_rc = false, is_last_rc = false;
         bool alive = false;
 
         bool is_rc() const { return id & 1; }
-        uint32_t length() const { return (uint32_t)data.size(); }
+        uint32_t length() const { return spanned ? size : (uint32_t)data.size(); }
         uint32_t indegree() const { return (uint32_t)prefix_edges.size(); }
         uint32_t outdegree() const { return (uint32_t)suffix_edges.size(); }
         bool is_junction() const { return outdegree() > 1 || indegree() > 1; }
@@ -60,6 +73,18 @@ public:
     /*! @brief appends the node of a read and its reverse complement (ids 2k, 2k + 1) */
     void add_sequence_nodes(uint64_t sequence_id, const std::string& name, const std::string& data,
         const std::string& reverse_complement);
+    /*! @brief the same pair as spans {source, first, len, 0} and {source, first, len, 1}: no bytes are held here.  A graph
+     *  holds strings or spans, never both: false (and nothing added) where the other entry point was used before;
+     *  add_sequence_nodes adds nothing to a graph of spans either. */
+    bool add_sequence_node_spans(uint64_t sequence_id, const std::string& name, uint32_t source, uint32_t first, uint32_t len);
+    bool span_mode() const { return bases_ == Bases::kSpans; }
+    /*! @brief span mode: turns n spans into the sum of their lengths in bytes at out, in order; 0 on success.  Set by
+     *  whoever keeps the table of bases. */
+    typedef std::function<int(const Span* spans, uint64_t n, uint8_t* out, uint64_t out_bytes)> Speller;
+    void set_speller(Speller speller) { speller_ = std::move(speller); }
+    /*! @brief span mode: the bytes of the given nodes with ONE call of the speller - node ids[k]'s are
+     *  bytes[off[k] .. off[k + 1]); the speller's code where it refuses (-1 without a speller) */
+    int spell(const std::vector<uint64_t>& ids, std::string& bytes, std::vector<uint64_t>& off) const;
     /*! @brief appends one edge; edges must be added in twin pairs (ids 2k, 2k + 1) */
     void add_edge(uint32_t begin_node, uint32_t end_node, uint32_t length);
 
@@ -122,6 +147,9 @@ private:
     void attraction_lists(const std::vector<uint32_t>& component, const Local& local, std::vector<uint32_t>& adj_off,
         std::vector<uint32_t>& adj) const;
 
+    enum class Bases { kNone, kStrings, kSpans };
+    Bases bases_ = Bases::kNone;
+    Speller speller_;
     std::vector<Node> nodes_;
     std::vector<Edge> edges_;
     std::vector<uint32_t> marked_edges_;

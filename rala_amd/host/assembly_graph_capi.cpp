@@ -7,7 +7,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
+#include <vector>
 
 #include "assembly_graph.hpp"
 
@@ -19,6 +21,15 @@ uint64_t fnv1a(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
     return h;
 }
 
+// the bytes of one node, whichever way the graph holds them (span mode: through the graph's speller; empty where it refuses)
+std::string node_bytes(const rala::AssemblyGraph* g, uint64_t node) {
+    if (!g->span_mode()) return g->nodes()[node].data;
+    std::string bytes;
+    std::vector<uint64_t> off;
+    if (g->spell(std::vector<uint64_t>(1, node), bytes, off) != 0) bytes.clear();
+    return bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -28,6 +39,43 @@ void ag_destroy(void* h) { delete (rala::AssemblyGraph*)h; }
 
 void ag_add_node_pair(void* h, uint64_t sequence_id, const char* name, const char* data, const char* rc) {
     ((rala::AssemblyGraph*)h)->add_sequence_nodes(sequence_id, name, data, rc);
+}
+// span mode (tests/test_spans_cpu.py): the pair as spans of source `source`; 0, or -1 where the graph holds strings
+int ag_add_node_pair_spans(void* h, uint64_t sequence_id, const char* name, uint32_t source, uint32_t first, uint32_t len) {
+    return ((rala::AssemblyGraph*)h)->add_sequence_node_spans(sequence_id, name, source, first, len) ? 0 : -1;
+}
+// the table of bases of a span-mode graph, copied: source s is bases[base_off[s] .. base_off[s + 1]); installs a plain host
+// speller over it - the definition of a span, byte by byte, refusing what rala_hip_spell refuses
+void ag_set_sources(void* h, const uint8_t* bases, const uint64_t* base_off, uint64_t n) {
+    auto table = std::make_shared<std::pair<std::vector<uint8_t>, std::vector<uint64_t>>>();
+    table->second.assign(base_off, base_off + n + 1);
+    table->first.assign(bases, bases + base_off[n]);
+    ((rala::AssemblyGraph*)h)->set_speller([table](const rala::AssemblyGraph::Span* spans, uint64_t n_spans, uint8_t* out, uint64_t out_bytes) {
+        const std::vector<uint8_t>& B = table->first;
+        const std::vector<uint64_t>& off = table->second;
+        uint64_t at = 0;
+        for (uint64_t k = 0; k < n_spans; ++k) {
+            const auto& s = spans[k];
+            if ((uint64_t)s.source + 1 >= off.size() || s.rc > 1) return -2;
+            const uint64_t lo = off[s.source] + s.first, hi = lo + s.len;
+            if (hi > off[s.source + 1] || at + s.len > out_bytes) return -2;
+            for (uint64_t j = 0; j < s.len; ++j) {
+                uint8_t c = s.rc ? B[hi - 1 - j] : B[lo + j];
+                if (s.rc) c = c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
+                out[at + j] = c;
+            }
+            at += s.len;
+        }
+        return at == out_bytes ? 0 : -2;
+    });
+}
+// a node's spans, four words each (source, first, len, rc): returns their number, copies at most cap of them
+uint64_t ag_node_spans(void* h, uint64_t node, uint32_t* out, uint64_t cap) {
+    const auto& sp = ((rala::AssemblyGraph*)h)->nodes()[node].spans;
+    for (size_t k = 0; out && k < sp.size() && k < cap; ++k) {
+        out[4 * k] = sp[k].source; out[4 * k + 1] = sp[k].first; out[4 * k + 2] = sp[k].len; out[4 * k + 3] = sp[k].rc;
+    }
+    return sp.size();
 }
 void ag_add_edge(void* h, uint32_t begin_node, uint32_t end_node, uint32_t length) {
     ((rala::AssemblyGraph*)h)->add_edge(begin_node, end_node, length);
@@ -90,12 +138,24 @@ void ag_size(void* h, uint64_t* n_nodes, uint64_t* n_edges) {
 void ag_dump_nodes(void* h, uint8_t* alive, uint32_t* length, uint32_t* n_seq, uint64_t* data_hash, uint64_t* ids_hash,
                    uint8_t* first_rc, uint8_t* last_rc, uint32_t* indeg, uint32_t* outdeg, uint64_t* adj_hash) {
     auto* g = (rala::AssemblyGraph*)h;
+    // span mode: every live node's bytes with one call of the speller
+    std::string bytes;
+    std::vector<uint64_t> ids, off;
+    std::vector<int64_t> at(g->nodes().size(), -1);
+    if (g->span_mode()) {
+        for (size_t i = 0; i < g->nodes().size(); ++i) {
+            if (!g->nodes()[i].alive) continue;
+            at[i] = (int64_t)ids.size();
+            ids.push_back(i);
+        }
+        if (g->spell(ids, bytes, off) != 0) bytes.assign(bytes.size(), '?');
+    }
     for (size_t i = 0; i < g->nodes().size(); ++i) {
         const auto& n = g->nodes()[i];
         alive[i] = n.alive;
         length[i] = n.length();
         n_seq[i] = (uint32_t)n.sequence_ids.size();
-        data_hash[i] = fnv1a(n.data.data(), n.data.size());
+        data_hash[i] = at[i] >= 0 ? fnv1a(bytes.data() + off[at[i]], off[at[i] + 1] - off[at[i]]) : fnv1a(n.data.data(), n.data.size());
         ids_hash[i] = fnv1a(n.sequence_ids.data(), n.sequence_ids.size() * 8);
         first_rc[i] = n.is_first_rc; last_rc[i] = n.is_last_rc;
         indeg[i] = n.indegree(); outdeg[i] = n.outdegree();
@@ -137,7 +197,7 @@ uint64_t ag_print(void* h, int kind, char* dst, uint64_t cap) {
 }
 
 uint64_t ag_node_data(void* h, uint64_t node, char* dst, uint64_t cap) {
-    const auto& d = ((rala::AssemblyGraph*)h)->nodes()[node].data;
+    const std::string d = node_bytes((rala::AssemblyGraph*)h, node);
     if (dst && cap >= d.size()) memcpy(dst, d.data(), d.size());
     return d.size();
 }

@@ -695,8 +695,12 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
     rala_hip_get_graph(ctx_, node_read.data(), src.data(), dst.data(), len.data(), nullptr);
     std::vector<int64_t> read_to_node(n, -1);
     for (uint64_t k = 0; k < n_nodes; k += 2) read_to_node[node_read[k]] = (int64_t)k;
+    // io::device_contigs_wanted(): the nodes as spans of a table of bases on the device - no string per read here at all
+    const bool as_spans = io::device_contigs_wanted() && construct_node_spans(node_read, read_to_node, begin, end);
+    if (io::device_contigs_wanted() && !as_spans) fprintf(stderr, "[rala::Graph::construct] node bases on the host\n");
     // nodes in read order (graph.cpp:553-574): collect the trimmed sequences first
-    std::vector<std::string> node_name(n_nodes / 2), node_data(n_nodes / 2), node_rc(n_nodes / 2);
+    const uint64_t n_strings = as_spans ? 0 : n_nodes / 2;         // (span mode: none of what follows does anything)
+    std::vector<std::string> node_name(n_strings), node_data(n_strings), node_rc(n_strings);
     auto keep = [&](uint64_t i, const std::string& name, const std::string& data) {
         auto seq = createSequence(name, data);
         seq->trim(begin[i], end[i]);
@@ -705,8 +709,8 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         node_data[k] = seq->data();
         node_rc[k] = seq->reverse_complement();
     };
-    bool sliced = false;
-    if (!sequence_index_.empty()) {
+    bool sliced = as_spans;
+    if (!as_spans && !sequence_index_.empty()) {
         // the device indexed the file: the bases of the reads the graph keeps are cut out of it, nothing is parsed again
         std::vector<uint64_t> wanted;
         for (uint64_t i = 0; i < n; ++i) if (read_to_node[i] >= 0) wanted.push_back(i);
@@ -734,7 +738,7 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         if (i >= n || read_to_node[i] < 0) return;
         keep(i, name, data);
     });
-    for (uint64_t k = 0; k < n_nodes / 2; ++k) {
+    for (uint64_t k = 0; k < n_strings; ++k) {
         graph_.add_sequence_nodes(node_read[2 * k], node_name[k], node_data[k], node_rc[k]);
     }
     timer("[rala::Graph::construct] loaded sequences");
@@ -743,6 +747,73 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
     timer("[rala::Graph::construct] created assembly graph");
     fprintf(stderr, "[rala::Graph::construct] number of nodes = %zu\n", graph_.nodes().size());
     fprintf(stderr, "[rala::Graph::construct] number of edges = %zu\n", graph_.edges().size());
+}
+
+// The nodes of construct() as spans (assembly_graph.hpp): the bases of the reads the graph keeps become the context's table of
+// bases, the nodes name ranges of it, and graph_'s speller is rala_hip_spell.  A gzip index: the device slices the file and
+// keeps what it gathered (option keep_bases) - source k the whole read, the span its valid region; otherwise the bases come
+// from where they come today, packed trimmed into one buffer - no string and no reverse complement per read - and are handed
+// over.  false: no room on the device for the table (RALA_HIP_ENOMEM) - nothing was added, the string path runs whole.
+bool Graph::construct_node_spans(const std::vector<uint32_t>& node_read, const std::vector<int64_t>& read_to_node,
+    const std::vector<uint32_t>& begin, const std::vector<uint32_t>& end) {
+    static_assert(sizeof(AssemblyGraph::Span) == sizeof(rala_hip_span), "a span is a rala_hip_span");
+    const uint64_t n = read_len_.size();
+    std::vector<uint64_t> wanted;
+    for (uint64_t i = 0; i < n; ++i) if (read_to_node[i] >= 0) wanted.push_back(i);
+    std::vector<uint64_t> base_off(wanted.size() + 1, 0);
+    bool on_device = false, whole = false;
+    if (!sequence_index_.empty() && sequence_index_gzip_) {
+        for (size_t w = 0; w < wanted.size(); ++w) base_off[w + 1] = base_off[w] + sequence_index_.length[wanted[w]];
+        int irregular = 0;
+        check(ctx_, rala_hip_set_option(ctx_, "keep_bases", 1), "construct");
+        const int rc = rala_hip_slice_sequences(ctx_, sequences_path_.c_str(), wanted.data(), wanted.size(), base_off.data(), nullptr,
+                                                std::max(1u, num_threads_), &irregular);
+        check(ctx_, rala_hip_set_option(ctx_, "keep_bases", 0), "construct");
+        if (rc == RALA_HIP_ENOMEM) return false;
+        // (any other refusal - the file changed, the inflater gave up - is the host reader's, as it is today)
+        on_device = whole = rc == RALA_HIP_OK && !irregular;
+    }
+    if (!on_device) {
+        std::vector<int64_t> rank_of(n, -1);
+        for (size_t w = 0; w < wanted.size(); ++w) {
+            rank_of[wanted[w]] = (int64_t)w;
+            base_off[w + 1] = base_off[w] + (end[wanted[w]] - begin[wanted[w]]);
+        }
+        std::vector<uint8_t> packed(base_off.back() + 1);
+        auto keep = [&](uint64_t i, const std::string& data) {
+            if (begin[i] < data.size()) memcpy(packed.data() + base_off[rank_of[i]], data.data() + begin[i], std::min<uint64_t>(end[i], data.size()) - begin[i]);
+        };
+        bool sliced = false;
+        if (!sequence_index_.empty() && !sequence_index_gzip_) {
+            std::vector<std::string> bases;
+            sliced = io::slice_sequences(sequences_path_, sequence_index_, wanted, std::max(1u, num_threads_), bases);
+            for (size_t w = 0; sliced && w < wanted.size(); ++w) keep(wanted[w], bases[w]);
+        }
+        uint64_t seq_id = 0;
+        if (!sliced) read_sequences(sequences_path_, [&](const std::string&, const std::string& data) {
+            const uint64_t i = seq_id++;
+            if (i < n && read_to_node[i] >= 0) keep(i, data);
+        });
+        const int rc = rala_hip_set_bases(ctx_, packed.data(), base_off.data(), wanted.size(), RALA_HIP_MEM_HOST);
+        if (rc == RALA_HIP_ENOMEM) return false;
+        check(ctx_, rc, "construct");
+    }
+    // nodes in read order (graph.cpp:553-574)
+    std::vector<int64_t> source_of(n, -1);
+    for (size_t w = 0; w < wanted.size(); ++w) source_of[wanted[w]] = (int64_t)w;
+    for (uint64_t k = 0; k < node_read.size() / 2; ++k) {
+        const uint64_t i = node_read[2 * k];
+        graph_.add_sequence_node_spans(i, name_of(i), (uint32_t)source_of[i], whole ? begin[i] : 0, end[i] - begin[i]);
+    }
+    graph_.set_speller([this](const AssemblyGraph::Span* spans, uint64_t n_spans, uint8_t* out, uint64_t out_bytes) {
+        check(ctx_, rala_hip_spell(ctx_, (const rala_hip_span*)spans, n_spans, out, out_bytes), "spell");
+        return 0;
+    });
+    rala_hip_spell_info info;
+    rala_hip_get_spell_info(ctx_, &info);
+    fprintf(stderr, "[rala::Graph::construct] node bases on the device: %lu sources, %lu bytes%s\n", (unsigned long)info.sources,
+        (unsigned long)info.source_bytes, info.from_slice ? " (kept by the device's slice)" : "");
+    return true;
 }
 
 // reference src/graph.cpp:642-697; the layout of postprocess() runs on the GPU with a fixed seed
@@ -828,15 +899,30 @@ void Graph::extract_contigs(std::vector<std::unique_ptr<Sequence>>& dst, bool dr
     create_unitigs();
     uint32_t contig_id = 0;
     std::vector<uint32_t> contig_length;
+    // span mode: the contigs are chosen first, spelled with one call, and cut into records
+    std::vector<uint64_t> ids;
+    std::vector<std::string> contig_name;
     for (const auto& node : graph_.nodes()) {
         if (!node.alive || node.is_rc()) continue;
         if (drop_unassembled_sequences && (node.sequence_ids.size() < 6 || node.length() < 10000)) continue;
         contig_length.push_back(node.length());
         std::string name = "Ctg" + std::to_string(contig_id);
         name += " RC:i:" + std::to_string(node.sequence_ids.size());
-        name += " LN:i:" + std::to_string(node.data.size());
-        dst.emplace_back(createSequence(name, node.data));
+        name += " LN:i:" + std::to_string(graph_.span_mode() ? (size_t)node.size : node.data.size());
+        if (graph_.span_mode()) {
+            ids.push_back(node.id);
+            contig_name.push_back(name);
+        } else {
+            dst.emplace_back(createSequence(name, node.data));
+        }
         ++contig_id;
+    }
+    if (graph_.span_mode()) {
+        std::string bytes;
+        std::vector<uint64_t> off;
+        graph_.spell(ids, bytes, off);          // (a refusal is fatal inside)
+        for (size_t k = 0; k < ids.size(); ++k) dst.emplace_back(createSequence(contig_name[k], bytes.substr(off[k], off[k + 1] - off[k])));
+        fprintf(stderr, "[rala::Graph::extract_contigs] spelled %zu bytes on the device\n", bytes.size());
     }
     fprintf(stderr, "[rala::Graph::extract_contigs] number of contigs = %zu\n", contig_length.size());
     if (contig_length.empty()) return;
@@ -858,7 +944,15 @@ void Graph::extract_nodes(std::vector<std::unique_ptr<Sequence>>& dst) {
         for (uint32_t e : it.prefix_edges) node_ids.insert(edges[e].begin_node & ~1u);
         for (uint32_t e : it.suffix_edges) node_ids.insert(edges[e].end_node & ~1u);
     }
-    for (uint64_t id : node_ids) dst.emplace_back(createSequence(nodes[id].name, nodes[id].data));
+    if (graph_.span_mode()) {
+        std::string bytes;
+        std::vector<uint64_t> off;
+        const std::vector<uint64_t> ids(node_ids.begin(), node_ids.end());
+        graph_.spell(ids, bytes, off);          // (a refusal is fatal inside)
+        for (size_t k = 0; k < ids.size(); ++k) dst.emplace_back(createSequence(nodes[ids[k]].name, bytes.substr(off[k], off[k + 1] - off[k])));
+    } else {
+        for (uint64_t id : node_ids) dst.emplace_back(createSequence(nodes[id].name, nodes[id].data));
+    }
     fprintf(stderr, "[rala::Graph::extract_nodes] number of nodes = %zu\n", dst.size());
 }
 

@@ -100,6 +100,10 @@ private:
     std::string name_of(uint64_t i) const { return device_names_ ? std::string(name_arena_.data() + name_off_[i], name_len_[i]) : names_[i]; }
     void host_names(const std::string& overlaps_path);
 
+    // io::device_contigs_wanted(): the nodes as spans of the context's table of bases (false: no room there, the strings run)
+    bool construct_node_spans(const std::vector<uint32_t>& node_read, const std::vector<int64_t>& read_to_node,
+        const std::vector<uint32_t>& begin, const std::vector<uint32_t>& end);
+
     AssemblyGraph graph_;
     uint32_t layout_seed_ = 0;          // one fixed seed per layout round
 };

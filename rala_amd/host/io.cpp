@@ -107,6 +107,11 @@ bool device_sequences_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool device_contigs_wanted() {
+    const char* e = getenv("RALA_DEVICE_CONTIGS");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool device_names_wanted() {
     const char* e = getenv("RALA_DEVICE_NAMES");
     return e ? atoi(e) != 0 : false;

@@ -70,6 +70,12 @@ bool device_sequences_wanted();
  * "The name table from the device's index", for what was measured */
 bool device_names_wanted();
 
+/*! @brief do the nodes of the assembly graph hold their bases as spans of a table on the device (rala_hip_set_bases /
+ * rala_hip_slice_sequences' option "keep_bases") and are unitigs, contigs and GFA segments spelled there at the output
+ * (rala_hip_spell), instead of strings that are copied and concatenated on the host?  RALA_DEVICE_CONTIGS=1 says so; without
+ * it: no - the same bytes either way, see README.md, "Node bases as spans" */
+bool device_contigs_wanted();
+
 // ---- the second pass over the read file, from the device's sequence index ----------------------
 // Where every read's bases lie (rala_hip_get_sequence_index): the text [data_off, data_off + data_span) with every newline
 // and every carriage return in front of one taken out, `length` bases.  A BGZF file: offsets are offsets into its text, and
