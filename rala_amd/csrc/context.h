@@ -183,7 +183,7 @@ struct rala_hip_ctx {
     hipStream_t aux = nullptr;          // the pile chain's small kernels (long and event-dense reads), beside the first one
     bool use_side_stream = true;
     std::string err;
-    hipEvent_t ev[12] = {};
+    hipEvent_t ev[12] = {};                // (their names and roles: Event, slots.h)
     // RALA_HIP_MEM_HOST_ASYNC: the columns' host addresses until rala_hip_initialize has uploaded them (copy stream; events:
     // ids, b coordinates, a coordinates, lengths there)
     hipStream_t copy = nullptr;
@@ -331,7 +331,7 @@ struct rala_hip_ctx {
     bool use_fused_emit = true;
     rala_hip::DevBuf<uint32_t> d_shard_group, d_shard_part, d_shard_words, d_shard_tiles;
     bool dedupe_pending = false;
-    bool lists_pending = false;         // a sharded run's survivor lists are being gathered on the side stream (event ev[3])
+    bool lists_pending = false;         // a sharded run's survivor lists are being gathered on the side stream (event kEvGatherJoin)
     bool blocks_mode = false;
     const uint64_t* blocks_base = nullptr;
     const uint64_t* blocks_base_self = nullptr;
@@ -364,7 +364,7 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint8_t> d_alive;
     rala_hip::DevBuf<uint32_t> d_n_pits, d_n_hills;
     rala_hip::DevBuf<rala_hip::Interval> d_pool;
-    rala_hip::DevBuf<uint32_t> d_small;      // [0] pool_count [1] error [2] changed [3] tr pairs
+    rala_hip::DevBuf<uint32_t> d_small;      // counts and flags of every stage, sixteen words: who owns which, slots.h
     uint32_t pool_cap = 0;
     uint32_t pool_cap_first = 0;        // what set_reads derived from the option
     uint32_t rep_pool_cap = 0;          // repeat hills (sensitive pass); starts at pool_cap_first
@@ -377,7 +377,7 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint8_t> d_crec;           // compact ones (valid region + flags, 4 or 8 bytes per read)
     rala_hip::DevBuf<uint8_t> d_fate;           // per read after the containment scan: never dies | has hills << 1
     rala_hip::DevBuf<uint64_t> d_scan_state;    // tile states of the single-pass scans (scan_pass.h)
-    rala_hip::DevBuf<uint32_t> d_counts;        // small device counters of the second pass and the tail
+    rala_hip::DevBuf<uint32_t> d_counts;        // small device counters of the second pass and the tail (slots.h)
     rala_hip::DevBuf<uint32_t> d_surv_u32[8];
     rala_hip::DevBuf<uint8_t> d_surv_u8[2];
     rala_hip::DevBuf<uint8_t> d_list_block[2];  // sharded runs: this slice's packed survivors / all slices'

@@ -12,6 +12,7 @@
 #include "ctx_check.h"
 #include "lifecycle.h"
 #include "scan_pass.h"
+#include "slots.h"
 #include "stages.h"
 
 using namespace rala_hip;
@@ -44,13 +45,14 @@ int finish_install(rala_hip_ctx* ctx, uint64_t pool_count, bool valid_ready) {
     hipStream_t s = ctx->stream;
     ctx->tm = rala_hip_timings();
     ctx->overlaps.clear(); ctx->internals.clear();
-    const uint32_t small[8] = {(uint32_t)pool_count, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t small[kInstallSmallWords] = {};
+    small[kSmallPoolCount] = (uint32_t)pool_count;
     HIPCHECK(hipMemcpyAsync(ctx->d_small.p, small, sizeof(small), hipMemcpyHostToDevice, s));
-    HIPCHECK(ctx->d_cc_flags.ensure(8));
-    HIPCHECK(hipMemsetAsync(ctx->d_cc_flags.p + 6, 0, 4, s));
-    launch_count_zero_u8(ctx->d_alive.p, (uint32_t)ctx->n_reads, ctx->d_cc_flags.p + 6, s);
+    HIPCHECK(ctx->d_cc_flags.ensure(kCcFlagsWords));
+    HIPCHECK(hipMemsetAsync(ctx->d_cc_flags.p + kCcInstallDead, 0, 4, s));
+    launch_count_zero_u8(ctx->d_alive.p, (uint32_t)ctx->n_reads, ctx->d_cc_flags.p + kCcInstallDead, s);
     uint32_t n_dead = 0;
-    HIPCHECK(d2h_small(ctx, &n_dead, ctx->d_cc_flags.p + 6, 4, s));
+    HIPCHECK(d2h_small(ctx, &n_dead, ctx->d_cc_flags.p + kCcInstallDead, 4, s));
     HIPCHECK(stream_sync(ctx, s));                  // `small` is a local
     results_dropped(ctx);
     state_installed(ctx, n_dead, (uint32_t)pool_count, false, false, valid_ready);
@@ -146,7 +148,8 @@ int rala_hip_create(int device, rala_hip_ctx** out) {
               hipStreamCreateWithPriority(&ctx->side, hipStreamDefault, prio_greatest) == hipSuccess &&
               hipStreamCreate(&ctx->aux) == hipSuccess;
     for (auto& e : ctx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && ctx->d_small.ensure(16) == hipSuccess;
+    static_assert(sizeof(ctx->ev) / sizeof(ctx->ev[0]) == kEvCount, "one event per name of slots.h");
+    ok = ok && ctx->d_small.ensure(kSmallWords) == hipSuccess;
     if (!ok) {                                  // (rala_hip_destroy releases whatever was created)
         rala_hip_destroy(ctx);
         return RALA_HIP_EDEVICE;
@@ -514,7 +517,8 @@ int rala_hip_import_state(rala_hip_ctx* ctx, const uint8_t* valid, const uint32_
     }
     { const int rcp = grow_pool_to(ctx, pool.size()); if (rcp != RALA_HIP_OK) return rcp; }
     const uint32_t used = (uint32_t)pool.size();
-    uint32_t small[8] = {used, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t small[kInstallSmallWords] = {};
+    small[kSmallPoolCount] = used;
     HIPCHECK(hipMemcpy(ctx->d_small.p, small, sizeof(small), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ctx->d_begin.p, begin, n * 4, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ctx->d_end.p, end, n * 4, hipMemcpyHostToDevice));

@@ -74,7 +74,7 @@ inline void inputs_adopted(rala_hip_ctx* ctx, Inputs kind) {
 inline void upload_deferred(rala_hip_ctx* ctx) { ctx->upload_pending = true; }
 inline void upload_done(rala_hip_ctx* ctx) { ctx->upload_pending = false; }
 
-// duplicate removal of a sharded run's sender runs on the side stream (event ev[1]) / the second pass has joined it
+// duplicate removal of a sharded run's sender runs on the side stream (event kEvEmitDedupeDone) / the second pass has joined it
 inline void dedupe_forked(rala_hip_ctx* ctx) { ctx->dedupe_pending = true; }
 inline void dedupe_joined(rala_hip_ctx* ctx) { ctx->dedupe_pending = false; }
 

@@ -20,6 +20,7 @@
 #include "ctx_check.h"
 #include "lifecycle.h"
 #include "scan_pass.h"
+#include "slots.h"
 #include "stages.h"
 
 using namespace rala_hip;
@@ -40,10 +41,10 @@ int rala_hip::download_read_state(rala_hip_ctx* ctx) {
     HIPCHECK(hipMemcpyAsync(ctx->h_n_pits.data(), ctx->d_n_pits.p, n * 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(ctx->h_n_hills.data(), ctx->d_n_hills.p, n * 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(ctx->h_slot.data(), ctx->d_iv_slot.p, n * 4, hipMemcpyDeviceToHost, s));
-    uint32_t small[4];
-    HIPCHECK(d2h_small(ctx, small, ctx->d_small.p, sizeof(small), s));
+    uint32_t pool_count = 0;
+    HIPCHECK(d2h_small(ctx, &pool_count, ctx->d_small.p + kSmallPoolCount, 4, s));
     HIPCHECK(stream_sync(ctx, s));
-    const uint32_t used = std::min(small[0], ctx->pool_cap);
+    const uint32_t used = std::min(pool_count, ctx->pool_cap);
     ctx->pool_used = used;
     ctx->h_pool.resize(used);
     if (used) {
@@ -54,6 +55,12 @@ int rala_hip::download_read_state(rala_hip_ctx* ctx) {
 }
 
 namespace {
+
+// (defined behind their first use)
+TailList tail_list(rala_hip_ctx* ctx);
+int scan_space(rala_hip_ctx* ctx, uint32_t scans, uint64_t items, ScanSpace& sp, FillList* fills = nullptr);
+int tail_components(rala_hip_ctx* ctx, const TailList& L, uint32_t n_alive, bool touched_cleared = false);
+int gpu_tail_part_b(rala_hip_ctx* ctx);
 
 ReadState read_state(rala_hip_ctx* ctx) {
     ReadState rs;
@@ -66,6 +73,18 @@ ReadState read_state(rala_hip_ctx* ctx) {
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+struct Trace {
+    bool on;
+    double t;
+    Trace() : on(getenv("RALA_HIP_TRACE") != nullptr), t(now_ms()) {}
+    void operator()(const char* what, size_t k = 0) {
+        if (!on) return;
+        const double u = now_ms();
+        fprintf(stderr, "[trace] %-28s %8.3f ms  (%zu)\n", what, u - t, k);
+        t = u;
+    }
+};
 
 // ---- launch classes of the position-space kernel: reads grouped by LDS image size ------
 void build_classes(rala_hip_ctx* ctx, const std::vector<uint32_t>& reads, std::vector<uint32_t>& order) {
@@ -125,16 +144,21 @@ void build_classes(rala_hip_ctx* ctx, const std::vector<uint32_t>& reads, std::v
     }
 }
 
-// position-space kernel over `reads` (all of them, or the run kernel's overflow)
-// a.big_cap_reg != 0: with the region / interval lists in global memory at those sizes (a.big_space is set here)
-int run_position_kernel(rala_hip_ctx* ctx, PileArgs a, const std::vector<uint32_t>& reads) {
+// A position-space kernel (PileArgs or RepeatArgs) over `reads`, grouped by LDS image size, on stream st: one launch(a, grid,
+// in_lds) per class, a's order / n_items / lw / slab set.  big: with the region / interval lists in global memory at a's
+// sizes, words(..) words per workgroup (a.big_space is set here).  Nothing here waits for another stream; st is waited for.
+// who: the caller's name in the trace (null: no lines).
+template <class Args, class Launch>
+int launch_by_class(rala_hip_ctx* ctx, Args a, const std::vector<uint32_t>& reads, bool big, uint64_t (*words)(uint32_t, uint32_t, uint32_t),
+                    hipStream_t st, const char* who, Launch launch) {
     if (reads.empty()) return RALA_HIP_OK;
+    Trace trc;
     std::vector<uint32_t> order;
     build_classes(ctx, reads, order);
+    if (who) trc((std::string(who) + ": classes").c_str(), reads.size());
     HIPCHECK(ctx->d_order.ensure(order.size() + 1));
-    HIPCHECK(hipMemcpyAsync(ctx->d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    const bool big = a.big_cap_reg != 0;
-    const uint64_t big_words = big ? pile_big_words(a.big_cap_reg, a.big_cap_list, a.big_cap_raw) : 0;
+    HIPCHECK(hipMemcpyAsync(ctx->d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
+    const uint64_t big_words = big ? words(a.big_cap_reg, a.big_cap_list, a.big_cap_raw) : 0;
     for (const LaunchClass& c : ctx->classes) {
         uint32_t grid = c.count;
         if (!c.in_lds) grid = std::min<uint32_t>(c.count, 512);
@@ -148,60 +172,69 @@ int run_position_kernel(rala_hip_ctx* ctx, PileArgs a, const std::vector<uint32_
         a.n_items = c.count;
         a.lw = c.lw;
         a.slab = ctx->d_slab.p;
-        launch_pile_build_annotate(a, grid, c.in_lds, ctx->stream);
-        ++ctx->tm.pile_launches;
+        launch(a, grid, c.in_lds);
     }
-    HIPCHECK(stream_sync(ctx, ctx->stream));      // `order` is pageable host memory
+    // `order` is pageable host memory.  Not stream_sync: st may be a side stream, and this wait delivers no copy that
+    // d2h_small staged - none is pending at a caller today, and one queued in front of a call would wait for the next stream_sync
+    HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    if (who) trc((std::string(who) + ": kernels").c_str(), ctx->classes.size());
     return RALA_HIP_OK;
+}
+
+// the pile kernel in position space over `reads` (all of them, or the run kernel's overflow), on the main stream
+// a.big_cap_reg != 0: with the region / interval lists in global memory at those sizes
+int run_position_kernel(rala_hip_ctx* ctx, const PileArgs& a, const std::vector<uint32_t>& reads) {
+    hipStream_t s = ctx->stream;
+    return launch_by_class(ctx, a, reads, a.big_cap_reg != 0, pile_big_words, s, nullptr, [&](const PileArgs& c, uint32_t grid, bool in_lds) {
+        launch_pile_build_annotate(c, grid, in_lds, s);
+        ++ctx->tm.pile_launches;
+    });
 }
 
 // first sizes of the lists in global memory (the position-space kernels' LDS lists hold 192 regions per flag list and 64 raw
 // intervals); the option debug_big_caps = regions << 32 | raw intervals makes tests start lower
-void first_big_caps(const rala_hip_ctx* ctx, uint32_t& cap_reg, uint32_t& cap_list, uint32_t& cap_raw) {
+void first_big_caps(const rala_hip_ctx* ctx, uint32_t& cap_reg, uint32_t& cap_raw) {
     cap_reg = 1024; cap_raw = 4096;
     if (ctx->debug_big_caps) {
         cap_reg = std::max<uint32_t>(4, (uint32_t)((uint64_t)ctx->debug_big_caps >> 32));
         cap_raw = std::max<uint32_t>(4, (uint32_t)((uint64_t)ctx->debug_big_caps & 0xFFFFFFFFu));
     }
-    cap_list = 4 * cap_reg;
 }
 
-// The reads the position-space kernel noted in d_big_list[0] (*count_dev of them): once more, with the region lists and raw
+// The reads a position-space kernel noted in d_big_list[0] (`count` of them): once more, with the region lists and raw
 // intervals in global memory; lists that still do not fit are doubled for the reads concerned until they do (the reference
-// keeps them in vectors, pile.cpp:66, 359, 448).  a: the call's arguments (a.error keeps its pool-capacity bit).
-int run_unbounded_piles(rala_hip_ctx* ctx, PileArgs a, uint32_t count, uint32_t* count_dev) {
-    hipStream_t s = ctx->stream;
-    uint32_t cap_reg, cap_list, cap_raw;
-    first_big_caps(ctx, cap_reg, cap_list, cap_raw);
-    ctx->tm.pile_unbounded_reads += count;
+// keeps them in vectors, pile.cpp:66, 359, 448).  run(reads, note_in, cap_reg, cap_list, cap_raw) runs them on stream st and
+// waits for it; the reads that still do not fit are noted in note_in, *count_dev of them, with their bits in *status_dev
+// (which keeps its pool-capacity bit).  The first cap_list is list_factor * cap_reg.  Copies and clears are on st: the
+// caller's other streams go on beside.  what: the caller's word in the trace; left_text: its error text.
+template <class Run>
+int run_until_lists_fit(rala_hip_ctx* ctx, uint32_t count, uint32_t* count_dev, uint32_t* status_dev, uint32_t list_factor, hipStream_t st,
+                        const char* what, const char* left_text, Run run) {
+    uint32_t cap_reg, cap_raw;
+    first_big_caps(ctx, cap_reg, cap_raw);
+    uint32_t cap_list = list_factor * cap_reg;
     int from = 0;
     while (count) {
         std::vector<uint32_t> reads(count);
-        HIPCHECK(hipMemcpy(reads.data(), ctx->d_big_list[from].p, (size_t)count * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpyAsync(reads.data(), ctx->d_big_list[from].p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
         std::sort(reads.begin(), reads.end());
         HIPCHECK(ctx->d_big_list[from ^ 1].ensure(ctx->n_reads + 1));
-        uint32_t status = 0;
-        HIPCHECK(hipMemcpy(&status, a.error, 4, hipMemcpyDeviceToHost));
-        status &= kErrPoolCapacity;
-        HIPCHECK(hipMemcpyAsync(a.error, &status, 4, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemsetAsync(count_dev, 0, 4, s));
-        a.big_list = ctx->d_big_list[from ^ 1].p;
-        a.big_count = count_dev;
-        a.big_cap_reg = cap_reg; a.big_cap_list = cap_list; a.big_cap_raw = cap_raw;
-        a.n_items_dev = nullptr;
-        const int rc = run_position_kernel(ctx, a, reads);
+        // (the lists' bits of the status word start every round at zero; other kernels may be setting the pool's bit meanwhile)
+        launch_status_clear(status_dev, kErrRegionCapacity | kErrRawCapacity, count_dev, st);
+        const int rc = run(reads, ctx->d_big_list[from ^ 1].p, cap_reg, cap_list, cap_raw);
         if (rc != RALA_HIP_OK) return rc;
-        uint32_t left = 0;
-        HIPCHECK(hipMemcpy(&left, count_dev, 4, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(&status, a.error, 4, hipMemcpyDeviceToHost));
+        uint32_t left = 0, status = 0;
+        HIPCHECK(hipMemcpyAsync(&left, count_dev, 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(&status, status_dev, 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
         HIPCHECK(hipGetLastError());
         if (getenv("RALA_HIP_TRACE")) {
-            fprintf(stderr, "[trace] lists in global memory: %u reads at %u regions / %u raw intervals, %u left (status %u)\n", count, cap_reg,
-                    cap_raw, left, status);
+            fprintf(stderr, "[trace] %slists in global memory: %u reads at %u regions / %u raw intervals, %u left (status %u)\n", what, count,
+                    cap_reg, cap_raw, left, status);
         }
-        if (left && !(status & (kErrRegionCapacity | kErrRawCapacity))) {
-            return fail(ctx, RALA_HIP_EDEVICE, "position-space kernel: reads left without a reason");
-        }
+        if (left && !(status & (kErrRegionCapacity | kErrRawCapacity))) return fail(ctx, RALA_HIP_EDEVICE, left_text);
         if (status & kErrRegionCapacity) {
             if (cap_reg > (1u << 26)) return fail(ctx, RALA_HIP_ENOMEM, "slope-region lists beyond 2^26 entries");
             cap_reg *= 2; cap_list *= 2;
@@ -214,11 +247,22 @@ int run_unbounded_piles(rala_hip_ctx* ctx, PileArgs a, uint32_t count, uint32_t*
         from ^= 1;
     }
     // (the lists' bits are no error of the call any more)
-    uint32_t status = 0;
-    HIPCHECK(hipMemcpy(&status, a.error, 4, hipMemcpyDeviceToHost));
-    status &= kErrPoolCapacity;
-    HIPCHECK(hipMemcpy(a.error, &status, 4, hipMemcpyHostToDevice));
+    launch_status_clear(status_dev, kErrRegionCapacity | kErrRawCapacity, nullptr, st);
+    HIPCHECK(hipStreamSynchronize(st));
     return RALA_HIP_OK;
+}
+
+// the pile kernel's noted reads (initialize; a: the call's arguments), on the main stream
+int run_unbounded_piles(rala_hip_ctx* ctx, PileArgs a, uint32_t count, uint32_t* count_dev) {
+    ctx->tm.pile_unbounded_reads += count;
+    a.big_count = count_dev;
+    a.n_items_dev = nullptr;
+    return run_until_lists_fit(ctx, count, count_dev, a.error, 4, ctx->stream, "", "position-space kernel: reads left without a reason",
+                               [&](const std::vector<uint32_t>& reads, uint32_t* note_in, uint32_t cap_reg, uint32_t cap_list, uint32_t cap_raw) {
+                                   a.big_list = note_in;
+                                   a.big_cap_reg = cap_reg; a.big_cap_list = cap_list; a.big_cap_raw = cap_raw;
+                                   return run_position_kernel(ctx, a, reads);
+                               });
 }
 
 // ---- host tail helpers (Graph::preprocess, graph.cpp:699-880) --------------------------
@@ -331,13 +375,13 @@ int component_medians(rala_hip_ctx* ctx, std::vector<uint32_t>& members, std::ve
     HIPCHECK(hipMemcpyAsync(ctx->d_cc_edges.p, edges, 2 * m * 4, hipMemcpyHostToDevice, s));
     launch_cc_init(ctx->d_cc_label.p, (uint32_t)na, s);
     for (int round = 0;; ++round) {
-        HIPCHECK(hipMemsetAsync(ctx->d_small.p + 2, 0, 4, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_small.p + kCcChanged, 0, 4, s));
         for (int it = 0; it < 4; ++it) {          // several hook + jump steps per host round trip
-            launch_cc_hook(ctx->d_cc_edges.p, (uint32_t)m, 0, ctx->d_cc_label.p, ctx->d_small.p + 2, s);
+            launch_cc_hook(ctx->d_cc_edges.p, (uint32_t)m, 0, ctx->d_cc_label.p, ctx->d_small.p + kCcChanged, s);
             launch_cc_compress(ctx->d_cc_label.p, (uint32_t)na, s);
         }
         uint32_t changed = 0;
-        HIPCHECK(d2h_small(ctx, &changed, ctx->d_small.p + 2, 4, s));
+        HIPCHECK(d2h_small(ctx, &changed, ctx->d_small.p + kCcChanged, 4, s));
         HIPCHECK(stream_sync(ctx, s));
         if (!changed) break;
         if (round > 10000) return fail(ctx, RALA_HIP_EDEVICE, "connected components did not converge");
@@ -369,18 +413,6 @@ int component_medians(rala_hip_ctx* ctx, std::vector<uint32_t>& members, std::ve
     }
     return RALA_HIP_OK;
 }
-
-struct Trace {
-    bool on;
-    double t;
-    Trace() : on(getenv("RALA_HIP_TRACE") != nullptr), t(now_ms()) {}
-    void operator()(const char* what, size_t k = 0) {
-        if (!on) return;
-        const double u = now_ms();
-        fprintf(stderr, "[trace] %-28s %8.3f ms  (%zu)\n", what, u - t, k);
-        t = u;
-    }
-};
 
 int preprocess_chimeras(rala_hip_ctx* ctx) {
     Trace tr;
@@ -507,7 +539,7 @@ int preprocess_chimeras(rala_hip_ctx* ctx) {
     // one compaction at the end: what is dead or (overlaps only, :869-877) lost a read goes
     auto compact = [&](std::vector<HostOvl>& v, bool check_piles) {
         const unsigned T = ctx->pool->size();
-        std::vector<size_t> cnt(T + 1, 0);
+        std::vector<size_t> kept_to(T + 1, 0);
         auto keep = [&](const HostOvl& o) {
             return !o.dead && !(check_piles && (!ctx->h_alive[o.a] || !ctx->h_alive[o.b]));
         };
@@ -515,13 +547,13 @@ int preprocess_chimeras(rala_hip_ctx* ctx) {
         ctx->pool->chunks(v.size(), [&](unsigned t, size_t b0, size_t e0) {
             size_t c = 0;
             for (size_t k = b0; k < e0; ++k) c += keep(v[k]);
-            cnt[t + 1] = c;
+            kept_to[t + 1] = c;
         });
-        for (unsigned t = 0; t < T; ++t) cnt[t + 1] += cnt[t];
+        for (unsigned t = 0; t < T; ++t) kept_to[t + 1] += kept_to[t];
         std::vector<HostOvl>& out = ctx->scratch_ovl;      // capacity survives across calls
-        out.resize(single ? cnt[1] : cnt[T]);
+        out.resize(single ? kept_to[1] : kept_to[T]);
         ctx->pool->chunks(v.size(), [&](unsigned t, size_t b0, size_t e0) {
-            size_t w = single ? 0 : cnt[t];
+            size_t w = single ? 0 : kept_to[t];
             for (size_t k = b0; k < e0; ++k) if (keep(v[k])) out[w++] = v[k];
         });
         v.swap(out);
@@ -530,6 +562,46 @@ int preprocess_chimeras(rala_hip_ctx* ctx) {
     compact(ctx->overlaps, true);
     tr("compact", ctx->overlaps.size());
     return RALA_HIP_OK;
+}
+
+// ---- argument blocks ------------------------------------------------------------------------------------------------------
+// where the primary bound events are: in fixed slots (cnt: events per read) or behind the CSR d_ev_off (cnt null), which
+// counts in units of 1 << shift events.  rala_hip_initialize passes what it has just decided, later callers the context's.
+struct PrimaryEvents {
+    const uint32_t* ev;
+    const uint32_t* cnt;
+    uint32_t shift;
+};
+PrimaryEvents primary_events(rala_hip_ctx* ctx, bool fixed, uint32_t shift) {
+    return {fixed ? ctx->d_ev_fixed.p : ctx->d_ev.p, fixed ? ctx->d_cursor.p : nullptr, shift};
+}
+
+// what the pile kernels of initialize and of the sensitive pass share: the reads, their rows (none with pile_rows = 0), the
+// primary events, the per-read results; everything else zero
+PileArgs pile_args(rala_hip_ctx* ctx, const PrimaryEvents& pe) {
+    PileArgs a{};
+    a.read_len = ctx->d_read_len.p; a.pile_off = ctx->d_pile_off.p; a.pile = ctx->rowless ? nullptr : ctx->d_pile.p;
+    a.ev_off = ctx->d_ev_off.p; a.ev = pe.ev; a.ev_cnt = pe.cnt; a.ev_stride = kRunEventCapBig; a.ev_shift = pe.shift;
+    a.begin = ctx->d_begin.p; a.end = ctx->d_end.p; a.median = ctx->d_median.p; a.p10 = ctx->d_p10.p;
+    return a;
+}
+
+// the repeat-hill kernel's arguments on the context that holds the piles (ev_off / ev: the caller's)
+RepeatArgs repeat_args(rala_hip_ctx* cl) {
+    RepeatArgs a{};
+    a.read_len = cl->d_read_len.p; a.pile_off = cl->d_pile_off.p; a.pile = cl->d_pile.p;
+    a.begin = cl->d_begin.p; a.end = cl->d_end.p; a.median = cl->d_median.p; a.p10 = cl->d_p10.p;
+    a.dataset_median = cl->d_dataset_median.p; a.n_rep = cl->d_n_rep.p; a.rep_slot = cl->d_rep_slot.p;
+    a.pool = cl->d_rep_pool.p; a.pool_count = cl->d_small.p + kSensPoolCount; a.pool_cap = cl->rep_pool_cap;
+    a.error = cl->d_small.p + kSensStatus;
+    return a;
+}
+
+// the pool a stage needs when its kernels counted `used` entries into one of `cap`: that and an eighth more (the slots of
+// reads that ran twice are not handed back); 0: no size helps (the counter did not pass the capacity, or 2^32 entries)
+uint32_t grown_pool_size(uint32_t used, uint32_t cap) {
+    const uint64_t need = (uint64_t)used + used / 8 + 1024;
+    return used <= cap || need > 0xFFFFFFF0ull ? 0u : (uint32_t)need;
 }
 
 // ---- rows on demand (option pile_rows = 0; pile_rows_kernel.hip) -------------------------------------------------------
@@ -567,8 +639,8 @@ int materialize_rows(rala_hip_ctx* ctx, const uint32_t* reads, uint32_t first, u
     RowsArgs ra;
     ra.reads = reads ? ctx->d_rows_list.p : nullptr; ra.first = first; ra.n_items = count;
     ra.read_len = ctx->d_read_len.p; ra.dst_off = ctx->d_rows_off.p; ra.rows = ctx->d_rows_scratch.p;
-    ra.ev_off = ctx->d_ev_off.p; ra.ev = ctx->ev_fixed ? ctx->d_ev_fixed.p : ctx->d_ev.p;
-    ra.ev_cnt = ctx->ev_fixed ? ctx->d_cursor.p : nullptr; ra.ev_stride = kRunEventCapBig; ra.ev_shift = ctx->ev_shift;
+    const PrimaryEvents pe = primary_events(ctx, ctx->ev_fixed, ctx->ev_shift);
+    ra.ev_off = ctx->d_ev_off.p; ra.ev = pe.ev; ra.ev_cnt = pe.cnt; ra.ev_stride = kRunEventCapBig; ra.ev_shift = pe.shift;
     ra.sens_off = with_sens ? ctx->d_sens_off.p : nullptr; ra.sens_ev = with_sens ? ctx->d_sens_ev.p : nullptr;
     launch_pile_rows(ra, st);
     HIPCHECK(hipGetLastError());
@@ -577,7 +649,14 @@ int materialize_rows(rala_hip_ctx* ctx, const uint32_t* reads, uint32_t first, u
     return RALA_HIP_OK;
 }
 
-int run_repeats_classes_on_rows(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st);
+// position-space sensitive-pass kernel over `reads`, grouped by LDS image size, on stream st (the main stream, or the aux
+// stream beside a mode's run-space kernels: nothing here waits for another stream).  Mode 2, a.big_cap_reg != 0: with the
+// region lists and raw hills in global memory at those sizes.
+int run_repeats_classes_on_rows(rala_hip_ctx* ctx, const RepeatArgs& a, const std::vector<uint32_t>& reads, int mode, hipStream_t st) {
+    return launch_by_class(ctx, a, reads, mode == 2 && a.big_cap_reg != 0, repeats_big_words, st, "repeats",
+                           [&](const RepeatArgs& c, uint32_t grid, bool in_lds) { launch_pile_repeats(c, grid, in_lds, mode, st); });
+}
+
 // position-space sensitive-pass kernel over `reads` where the rows are: the resident ones, or - option pile_rows = 0 - batch
 // after batch of them rebuilt in the scratch, a.pile / a.pile_off pointing there (mode 1 works on top of the primary rows; mode
 // 2 reads them with the sensitive layers of this construct on top, as the resident rows hold them by then)
@@ -600,107 +679,37 @@ int run_repeats_classes(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint3
     return RALA_HIP_OK;
 }
 
-// position-space sensitive-pass kernel over `reads`, grouped by LDS image size, on stream st (the main stream, or the aux
-// stream beside a mode's run-space kernels: nothing here waits for another stream).  Mode 2: a read whose region lists or
-// raw hills outgrow the kernel's LDS lists is noted and runs again with the lists in global memory, doubled until the read
-// fits (as run_unbounded_piles).
-int run_repeats_classes_on_rows(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st) {
-    Trace trc;
-    std::vector<uint32_t> order;
-    build_classes(ctx, reads, order);
-    trc("repeats: classes", reads.size());
-    HIPCHECK(ctx->d_order.ensure(order.size() + 1));
-    HIPCHECK(hipMemcpyAsync(ctx->d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
-    const bool big = mode == 2 && a.big_cap_reg != 0;
-    const uint64_t big_words = big ? repeats_big_words(a.big_cap_reg, a.big_cap_list, a.big_cap_raw) : 0;
-    for (const LaunchClass& c : ctx->classes) {
-        uint32_t grid = c.count;
-        if (!c.in_lds) grid = std::min<uint32_t>(c.count, 512);
-        if (big) {
-            grid = std::min<uint32_t>(grid, 64);
-            HIPCHECK(ctx->d_big_space.ensure((size_t)(big_words * grid)));
-            a.big_space = ctx->d_big_space.p;
-        }
-        if (!c.in_lds) HIPCHECK(ctx->d_slab.ensure((size_t)grid * 3 * c.lw));
-        a.order = ctx->d_order.p + c.first;
-        a.n_items = c.count;
-        a.lw = c.lw;
-        a.slab = ctx->d_slab.p;
-        launch_pile_repeats(a, grid, c.in_lds, mode, st);
-    }
-    HIPCHECK(hipStreamSynchronize(st));              // (`order` is pageable host memory)
-    HIPCHECK(hipGetLastError());
-    trc("repeats: kernels", ctx->classes.size());
-    return RALA_HIP_OK;
-}
-
+// The repeat-hill kernel in position space over `reads`, on stream st (null: the main stream).  Mode 2: a read whose region
+// lists or raw hills outgrow the kernel's LDS lists is noted and runs again with the lists in global memory
+// (run_until_lists_fit, as the pile kernel's noted reads).
 int run_repeats_kernel(rala_hip_ctx* ctx, RepeatArgs a, const std::vector<uint32_t>& reads, int mode, hipStream_t st = nullptr) {
     if (reads.empty()) return RALA_HIP_OK;
     if (st == nullptr) st = ctx->stream;
     if (mode != 2) return run_repeats_classes(ctx, a, reads, mode, st);
-    uint32_t* const count_dev = ctx->d_small.p + 8;
+    uint32_t* const count_dev = ctx->d_small.p + kSensNotedReads;
     HIPCHECK(ctx->d_big_list[0].ensure(ctx->n_reads + 1));
     HIPCHECK(hipMemsetAsync(count_dev, 0, 4, st));
     a.big_list = ctx->d_big_list[0].p;
     a.big_count = count_dev;
     a.big_space = nullptr; a.big_cap_reg = a.big_cap_list = a.big_cap_raw = 0;
     a.force_big = ctx->debug_force_big ? 1u : 0u;
-    int rc = run_repeats_classes(ctx, a, reads, 2, st);
+    const int rc = run_repeats_classes(ctx, a, reads, 2, st);
     if (rc != RALA_HIP_OK) return rc;
-    // one look: how many reads were noted, the status word (copies on THIS stream - a blocking copy would wait for the
+    // one look: the status word and how many reads were noted (a copy on THIS stream - a blocking copy would wait for the
     // run-space kernels beside)
-    uint32_t look[2] = {0, 0};                  // [0] status (d_small[7]) [1] noted reads (d_small[8])
-    auto fetch = [&]() -> int {
-        HIPCHECK(hipMemcpyAsync(look, ctx->d_small.p + 7, 8, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        return (int)RALA_HIP_OK;
-    };
-    rc = fetch();
-    if (rc != RALA_HIP_OK) return rc;
-    uint32_t count = look[1];
-    if (count == 0) return RALA_HIP_OK;
-    uint32_t cap_reg, cap_list, cap_raw;
-    first_big_caps(ctx, cap_reg, cap_list, cap_raw);
-    cap_list = 2 * cap_reg;
-    ctx->tm.pile_unbounded_reads += count;
-    int from = 0;
-    while (count) {
-        std::vector<uint32_t> again(count);
-        HIPCHECK(hipMemcpyAsync(again.data(), ctx->d_big_list[from].p, (size_t)count * 4, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        std::sort(again.begin(), again.end());
-        HIPCHECK(ctx->d_big_list[from ^ 1].ensure(ctx->n_reads + 1));
-        // (the lists' bits of the status word start every round at zero; other kernels may be setting the pool's bit meanwhile)
-        launch_status_clear(a.error, kErrRegionCapacity | kErrRawCapacity, count_dev, st);
-        a.big_list = ctx->d_big_list[from ^ 1].p;
-        a.big_cap_reg = cap_reg; a.big_cap_list = cap_list; a.big_cap_raw = cap_raw;
-        rc = run_repeats_classes(ctx, a, again, 2, st);
-        if (rc != RALA_HIP_OK) return rc;
-        rc = fetch();
-        if (rc != RALA_HIP_OK) return rc;
-        const uint32_t left = look[1], status = look[0];
-        if (getenv("RALA_HIP_TRACE")) {
-            fprintf(stderr, "[trace] repeat hills, lists in global memory: %u reads at %u regions / %u raw intervals, %u left (status %u)\n",
-                    count, cap_reg, cap_raw, left, status);
-        }
-        if (left && !(status & (kErrRegionCapacity | kErrRawCapacity))) {
-            return fail(ctx, RALA_HIP_EDEVICE, "repeat-hill kernel: reads left without a reason");
-        }
-        if (status & kErrRegionCapacity) {
-            if (cap_reg > (1u << 26)) return fail(ctx, RALA_HIP_ENOMEM, "slope-region lists beyond 2^26 entries");
-            cap_reg *= 2; cap_list *= 2;
-        }
-        if (status & kErrRawCapacity) {
-            if (cap_raw > (1u << 28)) return fail(ctx, RALA_HIP_ENOMEM, "interval lists beyond 2^28 entries");
-            cap_raw *= 2;
-        }
-        count = left;
-        from ^= 1;
-    }
-    // (the lists' bits are no error of the call any more)
-    launch_status_clear(a.error, kErrRegionCapacity | kErrRawCapacity, nullptr, st);
+    uint32_t look[kSensLookWords] = {};
+    HIPCHECK(hipMemcpyAsync(look, ctx->d_small.p + kSensStatus, sizeof(look), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    return RALA_HIP_OK;
+    const uint32_t count = look[kSensNotedReads - kSensStatus];
+    if (count == 0) return RALA_HIP_OK;
+    ctx->tm.pile_unbounded_reads += count;
+    return run_until_lists_fit(ctx, count, count_dev, ctx->d_small.p + kSensStatus, 2, st, "repeat hills, ",
+                               "repeat-hill kernel: reads left without a reason",
+                               [&](const std::vector<uint32_t>& again, uint32_t* note_in, uint32_t cap_reg, uint32_t cap_list, uint32_t cap_raw) {
+                                   a.big_list = note_in;
+                                   a.big_cap_reg = cap_reg; a.big_cap_list = cap_list; a.big_cap_raw = cap_raw;
+                                   return run_repeats_classes(ctx, a, again, 2, st);
+                               });
 }
 
 // One mode of the sensitive pass over the reads of a device list (its length in *count_dev, at most `bound`): every read
@@ -728,38 +737,40 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
         std::sort(host.begin(), host.end());
         const int rc = run_repeats_kernel(ctx, ra, host, mode);
         if (rc != RALA_HIP_OK) return rc;
-        HIPCHECK(hipMemcpy(small16, ctx->d_small.p, 64, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(small16, ctx->d_small.p, kSmallWords * 4, hipMemcpyDeviceToHost));
         return RALA_HIP_OK;
     }
     HIPCHECK(ctx->d_overflow.ensure(ctx->n_reads + 1));
     HIPCHECK(ctx->d_overflow_mid.ensure(ctx->n_reads + 1));
-    HIPCHECK(ctx->d_chain_cnt.ensure(16));
-    // [0] handed on by the cap-512 kernels, [1] by the cap-1024 and cap-2048 kernels, [8 .. 12] the classes' sizes
+    HIPCHECK(ctx->d_chain_cnt.ensure(kChainWords));
+    // (what the cap-512 kernels hand on, what the cap-1024 and cap-2048 kernels hand on, the classes' sizes: slots.h)
+    uint32_t* const from_512 = ctx->d_chain_cnt.p + kChainFrom512;
+    uint32_t* const from_1024 = ctx->d_chain_cnt.p + kChainFrom1024;
     {
         FillList fills;
-        fills.add(ctx->d_chain_cnt.p, 0, 4 * 4);
-        fills.add(ctx->d_chain_cnt.p + 8, 0, 5 * 4);
+        fills.add(from_512, 0, kChainHandedWords * 4);
+        fills.add(ctx->d_chain_cnt.p + kChainClasses, 0, kChainClassWords * 4);
         HIPCHECK(fills.launch(s));
     }
-    HIPCHECK(ctx->d_sens_split.ensure(5 * ((size_t)bound + 1)));
+    HIPCHECK(ctx->d_sens_split.ensure(kChainClassWords * ((size_t)bound + 1)));
     SensSplitArgs sp;
     sp.read_len = pa.read_len; sp.ev_off = pa.ev_off; sp.ev_cnt = pa.ev_cnt; sp.ev_stride = pa.ev_stride; sp.ev_shift = pa.ev_shift;
     sp.sens_off = pa.sens_off; sp.begin = pa.begin; sp.end = pa.end;
-    for (int c = 0; c < 5; ++c) sp.out[c] = ctx->d_sens_split.p + (size_t)c * ((size_t)bound + 1);
-    sp.counts = ctx->d_chain_cnt.p + 8;
+    for (uint32_t c = 0; c < kChainClassWords; ++c) sp.out[c] = ctx->d_sens_split.p + (size_t)c * ((size_t)bound + 1);
+    sp.counts = ctx->d_chain_cnt.p + kChainClasses;
     launch_sens_split(list_dev, bound, count_dev, sp, s);
     // look 1: the classes' sizes, the list's length; the first reads of the position-space class ride along
     constexpr uint32_t kRestAhead = 16384;
     HIPCHECK(ctx->p_sens_rest.ensure(kRestAhead));
-    uint32_t cls[5] = {0, 0, 0, 0, 0}, count = 0;
-    HIPCHECK(d2h_small(ctx, cls, ctx->d_chain_cnt.p + 8, 20, s));
+    uint32_t cls[kChainClassWords] = {}, count = 0;
+    HIPCHECK(d2h_small(ctx, cls, ctx->d_chain_cnt.p + kChainClasses, sizeof(cls), s));
     HIPCHECK(d2h_small(ctx, &count, count_dev, 4, s));
-    HIPCHECK(hipMemcpyAsync(ctx->p_sens_rest.p, sp.out[4], (size_t)std::min<uint32_t>(bound, kRestAhead) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(ctx->p_sens_rest.p, sp.out[kClassPosition], (size_t)std::min<uint32_t>(bound, kRestAhead) * 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(stream_sync(ctx, s));
     HIPCHECK(hipGetLastError());
     *count_out = count;
     if (count == 0) {
-        HIPCHECK(hipMemcpy(small16, ctx->d_small.p, 64, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(small16, ctx->d_small.p, kSmallWords * 4, hipMemcpyDeviceToHost));
         return RALA_HIP_OK;
     }
     uint32_t* const handed_512 = ctx->d_overflow.p;            // -> cap 1024
@@ -770,27 +781,27 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
     hipStream_t aux = ctx->use_side_stream ? ctx->aux : s;
     hipStream_t pos = ctx->use_side_stream ? ctx->side : s;
     if (aux != s) {
-        HIPCHECK(hipEventRecord(ctx->ev[8], s));
-        HIPCHECK(hipStreamWaitEvent(aux, ctx->ev[8], 0));
-        HIPCHECK(hipStreamWaitEvent(pos, ctx->ev[8], 0));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvSensFork], s));
+        HIPCHECK(hipStreamWaitEvent(aux, ctx->ev[kEvSensFork], 0));
+        HIPCHECK(hipStreamWaitEvent(pos, ctx->ev[kEvSensFork], 0));
     }
     pa.n_items_dev = nullptr;
-    pa.order = sp.out[0]; pa.n_items = cls[0];
-    launch_pile_sens(pa, cls[0], 0, mode, handed_512, ctx->d_chain_cnt.p, s);
-    pa.order = sp.out[1]; pa.n_items = cls[1];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[1], 16384), 3, mode, handed_512, ctx->d_chain_cnt.p, s);
-    pa.order = sp.out[2]; pa.n_items = cls[2];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[2], 8192), 1, mode, handed_1024, ctx->d_chain_cnt.p + 1, aux);
-    if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[9], aux));
+    pa.order = sp.out[kClassCap512]; pa.n_items = cls[kClassCap512];
+    launch_pile_sens(pa, cls[kClassCap512], 0, mode, handed_512, from_512, s);
+    pa.order = sp.out[kClassCap512Long]; pa.n_items = cls[kClassCap512Long];
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap512Long], 16384), 3, mode, handed_512, from_512, s);
+    pa.order = sp.out[kClassCap1024]; pa.n_items = cls[kClassCap1024];
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap1024], 8192), 1, mode, handed_1024, from_1024, aux);
+    if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[kEvSensAuxDone], aux));
     // (the event-dense reads: run space at 2048 events, one wavefront per SIMD - 6 842 of C5's 281 k targets took as long in
     // position space as all the others in theirs; what this kernel hands on goes down the chain with the cap-1024 kernel's)
-    pa.order = sp.out[3]; pa.n_items = cls[3];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[3], 4096), 2, mode, handed_1024, ctx->d_chain_cnt.p + 1, pos);
-    if (cls[4]) {
-        std::vector<uint32_t> rest(ctx->p_sens_rest.p, ctx->p_sens_rest.p + std::min<uint32_t>(cls[4], kRestAhead));
-        if (cls[4] > kRestAhead) {
-            rest.resize(cls[4]);
-            HIPCHECK(hipMemcpyAsync(rest.data() + kRestAhead, sp.out[4] + kRestAhead, (size_t)(cls[4] - kRestAhead) * 4, hipMemcpyDeviceToHost, pos));
+    pa.order = sp.out[kClassCap2048]; pa.n_items = cls[kClassCap2048];
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap2048], 4096), 2, mode, handed_1024, from_1024, pos);
+    if (const uint32_t n_rest = cls[kClassPosition]) {
+        std::vector<uint32_t> rest(ctx->p_sens_rest.p, ctx->p_sens_rest.p + std::min<uint32_t>(n_rest, kRestAhead));
+        if (n_rest > kRestAhead) {
+            rest.resize(n_rest);
+            HIPCHECK(hipMemcpyAsync(rest.data() + kRestAhead, sp.out[kClassPosition] + kRestAhead, (size_t)(n_rest - kRestAhead) * 4, hipMemcpyDeviceToHost, pos));
             HIPCHECK(hipStreamSynchronize(pos));
         }
         std::sort(rest.begin(), rest.end());
@@ -799,32 +810,34 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
         trc("sens pass: position space beside", rest.size());
     }
     if (aux != s) {
-        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[9], 0));
-        if (cls[3] || cls[4]) {
-            HIPCHECK(hipEventRecord(ctx->ev[8], pos));
-            HIPCHECK(hipStreamWaitEvent(s, ctx->ev[8], 0));
+        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvSensAuxDone], 0));
+        if (cls[kClassCap2048] || cls[kClassPosition]) {
+            HIPCHECK(hipEventRecord(ctx->ev[kEvSensPosDone], pos));
+            HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvSensPosDone], 0));
         }
     }
-    pa.order = handed_512; pa.n_items = count; pa.n_items_dev = ctx->d_chain_cnt.p;
-    launch_pile_sens(pa, std::min<uint32_t>(count, 2048), 1, mode, handed_1024, ctx->d_chain_cnt.p + 1, s);
+    pa.order = handed_512; pa.n_items = count; pa.n_items_dev = from_512;
+    launch_pile_sens(pa, std::min<uint32_t>(count, 2048), 1, mode, handed_1024, from_1024, s);
     // look 2: what was handed on, and the call's counters
-    uint32_t cnt[2] = {0, 0};
-    HIPCHECK(d2h_small(ctx, cnt, ctx->d_chain_cnt.p, 8, s));
-    HIPCHECK(d2h_small(ctx, small16, ctx->d_small.p, 64, s));
+    uint32_t handed[kChainLookWords] = {};
+    HIPCHECK(d2h_small(ctx, handed, from_512, sizeof(handed), s));
+    HIPCHECK(d2h_small(ctx, small16, ctx->d_small.p, kSmallWords * 4, s));
     HIPCHECK(stream_sync(ctx, s));
     HIPCHECK(hipGetLastError());
     trc(mode == 1 ? "sens pass 1: run space" : "sens pass 2: run space", count);
     if (getenv("RALA_HIP_TRACE")) {
-        fprintf(stderr, "[trace] sens pass %d: classes %u / %u / %u / %u / %u, handed on %u + %u\n", mode, cls[0], cls[1], cls[2], cls[3], cls[4], cnt[0], cnt[1]);
+        fprintf(stderr, "[trace] sens pass %d: classes %u / %u / %u / %u / %u, handed on %u + %u\n", mode, cls[kClassCap512], cls[kClassCap512Long], cls[kClassCap1024],
+                cls[kClassCap2048], cls[kClassPosition], handed[kChainFrom512], handed[kChainFrom1024]);
     }
-    if (cnt[1] == 0) return RALA_HIP_OK;
-    std::vector<uint32_t> rest((size_t)cnt[1]);
-    HIPCHECK(hipMemcpy(rest.data(), handed_1024, (size_t)cnt[1] * 4, hipMemcpyDeviceToHost));
+    const uint32_t n_rest = handed[kChainFrom1024];
+    if (n_rest == 0) return RALA_HIP_OK;
+    std::vector<uint32_t> rest((size_t)n_rest);
+    HIPCHECK(hipMemcpy(rest.data(), handed_1024, (size_t)n_rest * 4, hipMemcpyDeviceToHost));
     std::sort(rest.begin(), rest.end());
     const int rc = run_repeats_kernel(ctx, ra, rest, mode);
     trc("sens pass: position space", rest.size());
     if (rc != RALA_HIP_OK) return rc;
-    HIPCHECK(hipMemcpy(small16, ctx->d_small.p, 64, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(small16, ctx->d_small.p, kSmallWords * 4, hipMemcpyDeviceToHost));
     return RALA_HIP_OK;
 }
 
@@ -843,7 +856,6 @@ bool is_valid_overlap(rala_hip_ctx* ctx, uint32_t r, uint32_t x, uint32_t y) {
     return true;
 }
 
-int materialize_host(rala_hip_ctx* ctx);
 // the repeat hills (sensitive pass) as the host getters want them
 int download_repeat_hills(rala_hip_ctx* ctx) {
     if (!ctx->rep_host_stale) return RALA_HIP_OK;
@@ -859,10 +871,6 @@ int download_repeat_hills(rala_hip_ctx* ctx) {
     repeat_hills_fetched(ctx);
     return RALA_HIP_OK;
 }
-void build_graph(rala_hip_ctx* ctx);
-TailList tail_list(rala_hip_ctx* ctx);
-int tail_components(rala_hip_ctx* ctx, const TailList& L, uint32_t n_alive, bool touched_cleared = false);
-int gpu_tail_part_b(rala_hip_ctx* ctx);
 
 // Graph::preprocess(overlaps, sensitive path) (graph.cpp:882-1054).  Sensitive records:
 // a = query (original read, untrimmed coordinates), b = target (trimmed read of the -p run).
@@ -934,8 +942,8 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     cs->rep_pool_cap = std::max(cs->rep_pool_cap, cs->pool_cap_first);
     HIPCHECK(cs->d_rep_pool.ensure(cs->rep_pool_cap));
     HIPCHECK(hipMemsetAsync(cs->d_n_rep.p, 0, n * 4, s));
-    HIPCHECK(hipMemsetAsync(cs->d_small.p + 6, 0, 8, s));           // [6] rep pool count [7] error
-    HIPCHECK(hipMemsetAsync(cs->d_small.p + 2, 0, 4, s));           // [2] bad sensitive record
+    HIPCHECK(hipMemsetAsync(cs->d_small.p + kSensPoolCount, 0, kSensPoolWords * 4, s));
+    HIPCHECK(hipMemsetAsync(cs->d_small.p + kSensBadRecord, 0, 4, s));
     // One context: the target bounds as ONE 8-byte record per overlap, bucketed by the partitioned path the owners' records
     // of a sharded run take (bucket_kernels.hip; no +-15 here) - where the set suits that path; two tuples per overlap through
     // count / scan / scatter otherwise (and in a sharded run, where the tuples travel first)
@@ -945,10 +953,10 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     if (sens_records) {
         HIPCHECK(cs->d_sens_rec.ensure(n_sens + 8));
         launch_sens_records(so, (uint32_t)n, cs->d_begin.p, cs->d_alive.p, cs->d_sens_tb[0].p, cs->d_sens_tb[1].p, cs->d_sens_rec.p,
-                            cs->d_small.p + 2, s);
+                            cs->d_small.p + kSensBadRecord, s);
     } else {
         launch_sens_tuples(so, (uint32_t)n, cs->d_begin.p, cs->d_alive.p, cs->d_sens_tb[0].p, cs->d_sens_tb[1].p,
-                           cs->d_sens_tuples.p, cs->d_small.p + 2, s);
+                           cs->d_sens_tuples.p, cs->d_small.p + kSensBadRecord, s);
     }
     const uint2* tuples = cs->d_sens_tuples.p;          // what the pile holder buckets: {its read, bound}
     uint64_t n_tuples = 2 * n_sens;
@@ -970,7 +978,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         HIPCHECK(hipMemcpyAsync(cur, off, P * 4, hipMemcpyHostToDevice, s));
         launch_partition_tuples(cs->d_sens_tuples.p, 2 * n_sens, P, 1, cur, cs->d_sens_part.p, s);
         // a bad record anywhere is everybody's error
-        if (comm->all_reduce_u32(cs->d_small.p + 2, 1, ReduceOp::kMax, s) != 0) return comm_fail("all-reduce of the record check");
+        if (comm->all_reduce_u32(cs->d_small.p + kSensBadRecord, 1, ReduceOp::kMax, s) != 0) return comm_fail("all-reduce of the record check");
         if (comm->host_all_gather(send_counts.data(), P, matrix.data(), s) != 0) return comm_fail("sensitive tuple counts");
         n_tuples = 0;
         for (uint32_t p = 0; p < P; ++p) { recv_counts[p] = matrix[(size_t)p * P + me]; n_tuples += recv_counts[p]; }
@@ -988,7 +996,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     // (one context: the record check comes back with the first look of the pass below - a record that is an error names no
     // read, nothing downstream trips over it; a sharded run has waited for its collectives anyway)
     uint32_t bad = 0;
-    HIPCHECK(d2h_small(cs, &bad, cs->d_small.p + 2, 4, s));
+    HIPCHECK(d2h_small(cs, &bad, cs->d_small.p + kSensBadRecord, 4, s));
     auto check_records = [&]() -> int {
         if (bad & 1u) return fail(ctx, RALA_HIP_EINVAL, "sensitive overlap names must resolve");
         if (bad & 2u) return fail(ctx, RALA_HIP_EINVAL, "sensitive overlap targets a read that did not survive");
@@ -1013,7 +1021,7 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     HIPCHECK(cl->d_rep_pool.ensure(cl->rep_pool_cap));
     if (sharded) {
         HIPCHECK(hipMemsetAsync(cl->d_n_rep.p, 0, nl * 4, sl));
-        HIPCHECK(hipMemsetAsync(cl->d_small.p + 6, 0, 8, sl));
+        HIPCHECK(hipMemsetAsync(cl->d_small.p + kSensPoolCount, 0, kSensPoolWords * 4, sl));
     }
     if (sens_records) {
         // (the first pass' bucketing buffers have served: the bound events themselves stay where initialize left them)
@@ -1036,11 +1044,11 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
     }
     // the targets: reads that received bounds - listed where the offsets are, the host learns how many
     HIPCHECK(cl->d_sens_list.ensure(nl + 1));
-    HIPCHECK(cl->d_chain_cnt.ensure(16));
-    HIPCHECK(hipMemsetAsync(cl->d_chain_cnt.p + 4, 0, 4, sl));
-    launch_list_targets(cl->d_sens_off.p, (uint32_t)nl, cl->d_sens_list.p, cl->d_chain_cnt.p + 4, sl);
+    HIPCHECK(cl->d_chain_cnt.ensure(kChainWords));
+    HIPCHECK(hipMemsetAsync(cl->d_chain_cnt.p + kChainTargets, 0, 4, sl));
+    launch_list_targets(cl->d_sens_off.p, (uint32_t)nl, cl->d_sens_list.p, cl->d_chain_cnt.p + kChainTargets, sl);
     uint32_t n_targets = 0;
-    uint32_t small[16] = {};
+    uint32_t small[kSmallWords] = {};
     // (rows on demand: for the rest of this pass a target's row has these bounds on top; for the getters once the pass has
     // succeeded - the CSR then stays until the next rala_hip_initialize)
     struct PassRunning {
@@ -1049,28 +1057,17 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         ~PassRunning() { c->sens_pass_running = false; }
     } pass_running(cl);
 
-    RepeatArgs a;
-    a.read_len = cl->d_read_len.p; a.pile_off = cl->d_pile_off.p; a.pile = cl->d_pile.p;
+    RepeatArgs a = repeat_args(cl);
     a.ev_off = cl->d_sens_off.p; a.ev = cl->d_sens_ev.p;
-    a.begin = cl->d_begin.p; a.end = cl->d_end.p; a.median = cl->d_median.p; a.p10 = cl->d_p10.p;
-    a.dataset_median = cl->d_dataset_median.p; a.n_rep = cl->d_n_rep.p; a.rep_slot = cl->d_rep_slot.p;
-    a.pool = cl->d_rep_pool.p; a.pool_count = cl->d_small.p + 6; a.pool_cap = cl->rep_pool_cap;
-    a.error = cl->d_small.p + 7;
-    a.order = nullptr; a.n_items = 0; a.lw = 0; a.slab = nullptr;
     // the same in run space: the primary events + the sensitive bounds
-    PileArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.read_len = cl->d_read_len.p; pa.pile_off = cl->d_pile_off.p; pa.pile = cl->rowless ? nullptr : cl->d_pile.p;
-    pa.ev_off = cl->d_ev_off.p; pa.ev = cl->ev_fixed ? cl->d_ev_fixed.p : cl->d_ev.p;
-    pa.ev_cnt = cl->ev_fixed ? cl->d_cursor.p : nullptr; pa.ev_stride = kRunEventCapBig; pa.ev_shift = cl->ev_shift;
+    PileArgs pa = pile_args(cl, primary_events(cl, cl->ev_fixed, cl->ev_shift));
     pa.stop_after = 99;
-    pa.begin = cl->d_begin.p; pa.end = cl->d_end.p; pa.median = cl->d_median.p; pa.p10 = cl->d_p10.p;
-    pa.error = cl->d_small.p + 7;
+    pa.error = a.error;
     pa.sens_off = cl->d_sens_off.p; pa.sens_ev = cl->d_sens_ev.p;
-    pa.dataset_median = cl->d_dataset_median.p; pa.n_rep = cl->d_n_rep.p; pa.rep_slot = cl->d_rep_slot.p;
-    pa.rep_pool = cl->d_rep_pool.p; pa.rep_pool_count = cl->d_small.p + 6; pa.rep_pool_cap = cl->rep_pool_cap;
+    pa.dataset_median = a.dataset_median; pa.n_rep = a.n_rep; pa.rep_slot = a.rep_slot;
+    pa.rep_pool = a.pool; pa.rep_pool_count = a.pool_count; pa.rep_pool_cap = a.pool_cap;
     // add_layers on top of the coverage + find_median for the targets (graph.cpp:941-969)
-    int rc = run_sens_pass(cl, pa, a, 1, cl->d_sens_list.p, (uint32_t)nl, cl->d_chain_cnt.p + 4, &n_targets, small);
+    int rc = run_sens_pass(cl, pa, a, 1, cl->d_sens_list.p, (uint32_t)nl, cl->d_chain_cnt.p + kChainTargets, &n_targets, small);
     if (!sharded) {
         // (the record check came back with the pass' first look; when the pass itself failed, a record that is an error is the
         // failure to report - the pass ran over what such records left behind: advisor round 5)
@@ -1123,9 +1120,9 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         // the members (reads with an overlap; of a sharded run this rank's, as the owner's local ids) are listed where the
         // data is; the host learns how many
         HIPCHECK(cl->d_sens_list.ensure(std::max<uint64_t>(nl, 1) + 1));
-        HIPCHECK(cs->d_chain_cnt.ensure(16));
-        HIPCHECK(hipMemsetAsync(cs->d_chain_cnt.p + 5, 0, 4, s));
-        launch_list_members(cs->d_alive_reads.p, cs->d_touched.p, n_alive, P, me, cl->d_sens_list.p, cs->d_chain_cnt.p + 5, s);
+        HIPCHECK(cs->d_chain_cnt.ensure(kChainWords));
+        HIPCHECK(hipMemsetAsync(cs->d_chain_cnt.p + kChainMembers, 0, 4, s));
+        launch_list_members(cs->d_alive_reads.p, cs->d_touched.p, n_alive, P, me, cl->d_sens_list.p, cs->d_chain_cnt.p + kChainMembers, s);
         if (sharded) HIPCHECK(stream_sync(cs, s));              // (the owner context's stream goes on from here)
         members_on_device = true;
     }
@@ -1139,43 +1136,42 @@ int preprocess_repeats(rala_hip_ctx* cs, rala_hip_ctx* cl, Comm* comm, const ral
         // (host tail: the members were listed on the host)
         const std::vector<uint32_t>& list = sharded ? mine : members;
         HIPCHECK(cl->d_sens_list.ensure(std::max<uint64_t>(list.size(), 1) + 1));
-        HIPCHECK(cs->d_chain_cnt.ensure(16));
+        HIPCHECK(cs->d_chain_cnt.ensure(kChainWords));
         const uint32_t n_list = (uint32_t)list.size();
         if (n_list) HIPCHECK(hipMemcpy(cl->d_sens_list.p, list.data(), (size_t)n_list * 4, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(cs->d_chain_cnt.p + 5, &n_list, 4, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(cs->d_chain_cnt.p + kChainMembers, &n_list, 4, hipMemcpyHostToDevice));
         member_bound = n_list;
     }
     for (;;) {
-        rc = run_sens_pass(cl, pa, a, 2, cl->d_sens_list.p, member_bound, cs->d_chain_cnt.p + 5, &n_members, small);
+        rc = run_sens_pass(cl, pa, a, 2, cl->d_sens_list.p, member_bound, cs->d_chain_cnt.p + kChainMembers, &n_members, small);
         if (rc != RALA_HIP_OK) { if (cl != cs) cs->err = cl->err; return rc; }
-        const uint32_t st[2] = {small[6], small[7]};
-        if (!(st[1] & kErrPoolCapacity)) break;
+        if (!(small[kSensStatus] & kErrPoolCapacity)) break;
         // more repeat hills than the pool holds: its counter holds what is needed - the pass once more (mode 2 neither
         // reads nor writes the rows) with a pool of that size
-        const uint64_t need = (uint64_t)st[0] + st[0] / 8 + 1024;
-        if (st[0] <= cl->rep_pool_cap || need > 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ENOMEM, "repeat-hill pool beyond 2^32 entries");
-        cl->rep_pool_cap = (uint32_t)need;
+        const uint32_t need = grown_pool_size(small[kSensPoolCount], cl->rep_pool_cap);
+        if (!need) return fail(ctx, RALA_HIP_ENOMEM, "repeat-hill pool beyond 2^32 entries");
+        cl->rep_pool_cap = need;
         HIPCHECK(cl->d_rep_pool.ensure(cl->rep_pool_cap));
         a.pool = cl->d_rep_pool.p; a.pool_cap = cl->rep_pool_cap;
         pa.rep_pool = cl->d_rep_pool.p; pa.rep_pool_cap = cl->rep_pool_cap;
         HIPCHECK(hipMemsetAsync(cl->d_n_rep.p, 0, nl * 4, sl));
-        HIPCHECK(hipMemsetAsync(cl->d_small.p + 6, 0, 8, sl));
+        HIPCHECK(hipMemsetAsync(cl->d_small.p + kSensPoolCount, 0, kSensPoolWords * 4, sl));
         ++cl->tm.pool_regrown;
     }
     trc("rep: component medians + repeat hills", n_members);
-    uint32_t n_hills = small[6];
+    uint32_t n_hills = small[kSensPoolCount];
     if (sharded) {
         // capacity errors are everybody's; then the hills of all owners, slots rebased onto the
         // concatenation of their pools
-        HIPCHECK(hipMemcpyAsync(cs->d_small.p + 7, &small[7], 4, hipMemcpyHostToDevice, s));
-        if (comm->all_reduce_u32(cs->d_small.p + 7, 1, ReduceOp::kMax, s) != 0) return comm_fail("all-reduce of the kernel status");
-        HIPCHECK(d2h_small(cs, &small[7], cs->d_small.p + 7, 4, s));
+        HIPCHECK(hipMemcpyAsync(cs->d_small.p + kSensStatus, &small[kSensStatus], 4, hipMemcpyHostToDevice, s));
+        if (comm->all_reduce_u32(cs->d_small.p + kSensStatus, 1, ReduceOp::kMax, s) != 0) return comm_fail("all-reduce of the kernel status");
+        HIPCHECK(d2h_small(cs, &small[kSensStatus], cs->d_small.p + kSensStatus, 4, s));
         HIPCHECK(stream_sync(cs, s));
     }
-    if (small[7] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow (repeat hills)");
-    if (small[7] & kErrPoolCapacity) return fail(ctx, RALA_HIP_EDEVICE, "repeat-hill pool exhausted");
+    if (small[kSensStatus] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow (repeat hills)");
+    if (small[kSensStatus] & kErrPoolCapacity) return fail(ctx, RALA_HIP_EDEVICE, "repeat-hill pool exhausted");
     if (sharded) {
-        const uint64_t mine = std::min<uint32_t>(small[6], cl->rep_pool_cap);
+        const uint64_t mine = std::min<uint32_t>(small[kSensPoolCount], cl->rep_pool_cap);
         std::vector<uint64_t> counts(P);
         if (comm->host_all_gather(&mine, 1, counts.data(), s) != 0) return comm_fail("repeat-hill counts");
         RankOffsets base;
@@ -1302,8 +1298,6 @@ void build_graph(rala_hip_ctx* ctx) {
 }
 
 // transitive-edge marking on device edge arrays; marks stay in ctx->d_tr_marks
-int scan_space(rala_hip_ctx* ctx, uint32_t scans, uint64_t items, ScanSpace& sp, FillList* fills = nullptr);
-
 int tr_mark_device(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const uint32_t* d_src, const uint32_t* d_dst,
                    const uint32_t* d_len, uint32_t* n_pairs, Comm* comm = nullptr) {
     *n_pairs = 0;
@@ -1314,10 +1308,10 @@ int tr_mark_device(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const 
     HIPCHECK(B[0].ensure(n_nodes + 2)); HIPCHECK(B[1].ensure(n_nodes + 2)); HIPCHECK(B[2].ensure(2 * (size_t)n_edges));
     HIPCHECK(ctx->d_tr_marks.ensure((size_t)n_edges + 8));
     HIPCHECK(ctx->d_scan_ws.ensure(scan_workspace_bytes((uint64_t)n_nodes + 2)));
-    HIPCHECK(hipEventRecord(ctx->ev[10], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvTrBegin], s));
     FillList fills;
     fills.add(ctx->d_tr_marks.p, 0, ((size_t)n_edges + 7) & ~(size_t)3);
-    fills.add(ctx->d_small.p + 2, 0, 8);                             // [2] bad endpoint flag [3] pairs
+    fills.add(ctx->d_small.p + kTrBadEndpoint, 0, kTrWords * 4);     // (the bad-endpoint flag and the pairs)
     fills.add(B[1].p, 0, (size_t)(n_nodes + 1) * 4);
     // CSR on the device: out-degree count -> scan -> fill.  The fill order is arbitrary; the
     // candidate a->c is the edge with the highest id, which is the reference's "last one
@@ -1328,7 +1322,7 @@ int tr_mark_device(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const 
         if (rc != RALA_HIP_OK) return rc;
     }
     HIPCHECK(fills.launch(s));
-    launch_tr_degree(d_src, d_dst, n_nodes, n_edges, B[1].p, ctx->d_small.p + 2, s);
+    launch_tr_degree(d_src, d_dst, n_nodes, n_edges, B[1].p, ctx->d_small.p + kTrBadEndpoint, s);
     // row offsets (and the fill cursors, a second copy of them) from the out-degrees: one launch
     HIPCHECK(B[3 + 3].ensure(n_nodes + 2));
     if (!launch_offsets_pass(B[1].p, B[0].p, B[6].p, n_nodes, sp, s)) return fail(ctx, RALA_HIP_EDEVICE, "scan space");
@@ -1345,15 +1339,15 @@ int tr_mark_device(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const 
             return RALA_HIP_EDEVICE;
         }
     }
-    launch_tr_count(ctx->d_tr_marks.p, n_edges, ctx->d_small.p + 3, s);
-    HIPCHECK(hipEventRecord(ctx->ev[11], s));
-    uint32_t res[2] = {0, 0};
-    HIPCHECK(d2h_small(ctx, res, ctx->d_small.p + 2, 8, s));
+    launch_tr_count(ctx->d_tr_marks.p, n_edges, ctx->d_small.p + kTrPairs, s);
+    HIPCHECK(hipEventRecord(ctx->ev[kEvTrEnd], s));
+    uint32_t res[kTrWords] = {};
+    HIPCHECK(d2h_small(ctx, res, ctx->d_small.p + kTrBadEndpoint, sizeof(res), s));
     HIPCHECK(stream_sync(ctx, s));
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.tr_ms, ctx->ev[10], ctx->ev[11]));
-    if (res[0]) return fail(ctx, RALA_HIP_EINVAL, "edge endpoint out of range");
-    *n_pairs = res[1];
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.tr_ms, ctx->ev[kEvTrBegin], ctx->ev[kEvTrEnd]));
+    if (res[kTrBadEndpoint - kTrBadEndpoint]) return fail(ctx, RALA_HIP_EINVAL, "edge endpoint out of range");
+    *n_pairs = res[kTrPairs - kTrBadEndpoint];
     return RALA_HIP_OK;
 }
 
@@ -1374,13 +1368,32 @@ int tr_mark_impl(rala_hip_ctx* ctx, uint32_t n_nodes, uint32_t n_edges, const ui
 }
 
 // ---- preprocess tail on the device (tail_kernels.hip) ---------------------------------------
+// the ten columns of the survivor lists (d_surv_u32[0..7], d_surv_u8[0..1], or host copies of them) in the order of
+// Survivors' members
+Survivors survivors_of(uint32_t* const c32[8], uint8_t* strand, uint8_t* type) {
+    return Survivors{c32[0], c32[1], c32[2], c32[3], c32[4], c32[5], c32[6], c32[7], strand, type};
+}
+Survivors survivors_view(rala_hip_ctx* ctx) {
+    uint32_t* c32[8];
+    for (int f = 0; f < 8; ++f) c32[f] = ctx->d_surv_u32[f].p;
+    return survivors_of(c32, ctx->d_surv_u8[0].p, ctx->d_surv_u8[1].p);
+}
+
+// item k of survivor columns on the host, as the host lists hold it
+HostOvl host_item(const Survivors& sv, size_t k) {
+    HostOvl o;
+    o.src = sv.src[k]; o.a = sv.a_id[k]; o.b = sv.b_id[k];
+    o.c.a_begin = sv.a_begin[k]; o.c.a_end = sv.a_end[k]; o.c.b_begin = sv.b_begin[k]; o.c.b_end = sv.b_end[k]; o.c.length = sv.length[k];
+    o.strand = sv.strand[k]; o.dead = 0; o.type = sv.type[k];
+    return o;
+}
+
 TailList tail_list(rala_hip_ctx* ctx) {
+    const Survivors sv = survivors_view(ctx);
     TailList L;
     L.n = ctx->t_n0 + ctx->t_n1;
-    L.src = ctx->d_surv_u32[0].p; L.a = ctx->d_surv_u32[1].p; L.b = ctx->d_surv_u32[2].p;
-    L.a_begin = ctx->d_surv_u32[3].p; L.a_end = ctx->d_surv_u32[4].p; L.b_begin = ctx->d_surv_u32[5].p;
-    L.b_end = ctx->d_surv_u32[6].p; L.length = ctx->d_surv_u32[7].p;
-    L.strand = ctx->d_surv_u8[0].p; L.type = ctx->d_surv_u8[1].p;
+    L.src = sv.src; L.a = sv.a_id; L.b = sv.b_id; L.a_begin = sv.a_begin; L.a_end = sv.a_end; L.b_begin = sv.b_begin;
+    L.b_end = sv.b_end; L.length = sv.length; L.strand = sv.strand; L.type = sv.type;
     L.state = ctx->d_t_state.p; L.round = ctx->d_t_round.p;
     return L;
 }
@@ -1422,12 +1435,12 @@ int tail_components(rala_hip_ctx* ctx, const TailList& L, uint32_t n_alive, bool
     }
     launch_cc_edges(L, ctx->d_rank.p, ctx->d_cc_edges.p, ctx->d_touched.p, ctx->d_cc_label.p, n_alive, s);
     for (int k = 0; k < 2; ++k) {                               // sampled rounds, see cc_hook_kernel
-        launch_cc_hook(ctx->d_cc_edges.p, M, 1, ctx->d_cc_label.p, ctx->d_cc_flags.p + 7, s);
+        launch_cc_hook(ctx->d_cc_edges.p, M, 1, ctx->d_cc_label.p, ctx->d_cc_flags.p + kCcTailChanged, s);
         launch_cc_compress(ctx->d_cc_label.p, n_alive, s);
     }
     // one launch over all edges finishes the components (cc_hook_kernel unites to the end); the last compression
     // counts the components' reads with an overlap
-    launch_cc_hook(ctx->d_cc_edges.p, M, 0, ctx->d_cc_label.p, ctx->d_cc_flags.p + 7, s);
+    launch_cc_hook(ctx->d_cc_edges.p, M, 0, ctx->d_cc_label.p, ctx->d_cc_flags.p + kCcTailChanged, s);
     launch_cc_compress_count(ctx->d_cc_label.p, n_alive, ctx->d_touched.p, component_median_sizes(ctx->d_med_tmp.p, n_alive), s);
     // median of the pile medians per component (graph.cpp:777-783)
     HIPCHECK(launch_component_medians(ctx->d_cc_label.p, ctx->d_touched.p, ctx->d_alive_reads.p, ctx->d_median.p, n_alive,
@@ -1447,7 +1460,6 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
     const uint32_t M = ctx->t_n0 + ctx->t_n1;
     // (how many reads are alive came back with the survivor counts of the second pass: no look from the host here)
     const uint32_t n_alive = ctx->t_n_alive;
-    const size_t big = (size_t)std::max<uint64_t>(n_reads, M) + 2;
     HIPCHECK(ctx->d_t_state.ensure(M)); HIPCHECK(ctx->d_t_round.ensure(M));
     HIPCHECK(ctx->d_dirty.ensure(n_reads)); HIPCHECK(ctx->d_n_pits0.ensure(n_reads));
     HIPCHECK(ctx->d_rank.ensure(n_reads)); HIPCHECK(ctx->d_alive_reads.ensure(n_reads));
@@ -1458,8 +1470,7 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
     HIPCHECK(ctx->d_cc_edges.ensure(2 * (size_t)M)); HIPCHECK(ctx->d_cc_label.ensure(n_alive));
     ctx->t_med_tmp = component_median_workspace(n_alive);
     HIPCHECK(ctx->d_med_tmp.ensure(ctx->t_med_tmp));
-    HIPCHECK(ctx->d_cc_flags.ensure(8));
-    (void)big;
+    HIPCHECK(ctx->d_cc_flags.ensure(kCcFlagsWords));
     // (the containment scans order the items by key = items * (1 + round of promotion) + index, 32 bits: checked below with the
     // rounds this data set took - two to four - and not with the 255 a round counter could hold; before round 5 that was a
     // limit of 16.6 M surviving overlaps, 2.2 times C5's)
@@ -1473,26 +1484,24 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
         if (rc != RALA_HIP_OK) return rc;
         HIPCHECK(fills.launch(s));
     }
-    // (d_counts: [4 .. 5] overlaps dropped per round of a batch, [8] reads left, [9] a containment scan that failed,
-    // [10 .. 13] the scans' killer counts, [14 .. 29] their barriers - launch_tail_contain; [32 .. 39] the second pass's)
-    HIPCHECK(ctx->d_counts.ensure(48));
+    // (d_counts: cleared by the second pass; the tail's words are TailCounts, slots.h)
+    HIPCHECK(ctx->d_counts.ensure(kCountsWords));
     for (int k = 0; k < 2; ++k) HIPCHECK(ctx->d_t_work[k].ensure(n_reads));
     HIPCHECK(ctx->d_t_fin.ensure(2 * (size_t)n_reads));
     HIPCHECK(ctx->d_t_mark.ensure(2 * (size_t)n_reads));
     for (int k = 0; k < 3; ++k) { HIPCHECK(ctx->d_kill[k].ensure((size_t)M + 1)); HIPCHECK(ctx->d_kill2[k].ensure((size_t)M + 1)); }
     HIPCHECK(ctx->d_fp_map.ensure(n_reads));
     HIPCHECK(ctx->d_fp_pack.ensure(fixed_point_pack_words()));
-    launch_tail_init(L, ctx->t_n0, R, ctx->d_n_pits0.p, n_reads, ctx->d_t_fin.p, ctx->d_t_mark.p, ctx->d_fp_map.p, ctx->d_counts.p + 9, s);
+    launch_tail_init(L, ctx->t_n0, R, ctx->d_n_pits0.p, n_reads, ctx->d_t_fin.p, ctx->d_t_mark.p, ctx->d_fp_map.p, ctx->d_counts.p + kTailContain, s);
     // ranks of the reads that survived the second pass (the component graph lives on them)
     if (!launch_rank_pass(ctx->d_alive.p, ctx->d_rank.p, ctx->d_alive_reads.p, n_reads, sp, s)) return fail(ctx, RALA_HIP_EDEVICE, "scan space");
     mark("tail: ranks", n_alive);
 
     // break over chimeric hills, first re-trim (graph.cpp:704-736; no promotion here)
-    HIPCHECK(ctx->d_counts.ensure(48));
-    uint32_t* dropped = ctx->d_counts.p + 4;                        // one word per round of a batch
+    uint32_t* dropped = ctx->d_counts.p + kTailDropped;             // one word per round of a batch
     launch_break_hills(R, n_reads, s);
     if (ctx->lists_pending) {           // (a sharded run's survivor lists, gathered beside the kernels above)
-        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[3], 0));
+        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvGatherJoin], 0));
         ctx->lists_pending = false;
     }
     launch_retrim(L, R, 0, 0, dropped, s);
@@ -1514,14 +1523,14 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
             fills.add(ctx->d_dirty.p, 0, n_reads);
             fills.add(ctx->d_touched.p, 0, n_alive);
             component_median_clear(ctx->d_med_tmp.p, n_alive, fills);
-            if (k == 0) fills.add(dropped, 0, 2 * 4);
+            if (k == 0) fills.add(dropped, 0, kTailDroppedWords * 4);
             HIPCHECK(fills.launch(s));
             const int rcc = tail_components(ctx, L, n_alive, true);
             if (rcc != RALA_HIP_OK) return rcc;
             launch_break_pits(R, ctx->d_alive_reads.p, ctx->d_touched.p, ctx->d_cmed.p, n_alive, s, gate);
             launch_retrim(L, R, 1, rounds + k, dropped + k, s, gate);
         }
-        uint32_t d[2] = {0, 0};
+        uint32_t d[kTailDroppedWords] = {};
         HIPCHECK(d2h_small(ctx, d, dropped, sizeof(d), s));
         HIPCHECK(stream_sync(ctx, s));
         mark("tail: pits + retrim", d[0] + d[1]);
@@ -1539,7 +1548,7 @@ int gpu_tail_part_a(rala_hip_ctx* ctx) {
         uint32_t* const work[4] = {ctx->d_t_death[0].p, ctx->d_t_death[1].p, ctx->d_t_work[0].p, ctx->d_t_work[1].p};
         uint32_t* const lists[6] = {ctx->d_kill[0].p, ctx->d_kill[1].p, ctx->d_kill[2].p, ctx->d_kill2[0].p, ctx->d_kill2[1].p,
                                     ctx->d_kill2[2].p};
-        HIPCHECK(launch_tail_contain(L, R, ctx->d_alive.p, lists, ctx->d_counts.p + 9, work, ctx->d_t_fin.p, ctx->d_t_mark.p, ctx->d_fp_map.p,
+        HIPCHECK(launch_tail_contain(L, R, ctx->d_alive.p, lists, ctx->d_counts.p + kTailContain, work, ctx->d_t_fin.p, ctx->d_t_mark.p, ctx->d_fp_map.p,
                                      ctx->d_fp_pack.p, n_reads, ctx->debug_fp_lds_limit, ctx->debug_fp_give_up, s));
     }
     mark("tail: containment scans", M);
@@ -1562,49 +1571,48 @@ int gpu_tail_part_b(rala_hip_ctx* ctx) {
     HIPCHECK(ctx->d_seg_base.ensure(2 * (size_t)n_seg + 4));
     HIPCHECK(ctx->d_node_read.ensure(2 * (size_t)ctx->t_n_alive + 2));
     for (int k = 0; k < 3; ++k) HIPCHECK(ctx->d_e[k].ensure(2 * (size_t)M + 2));
-    HIPCHECK(ctx->d_counts.ensure(48));
     ScanSpace sp;
     {
         FillList fills;
         const int rc = scan_space(ctx, n_seg + 1, std::max<uint64_t>(n_reads, M), sp, &fills);
         if (rc != RALA_HIP_OK) return rc;
         fills.add(ctx->d_seg_base.p, 0, (2 * (size_t)n_seg + 4) * 4);
-        fills.add(ctx->d_counts.p + 8, 0, 4);
+        fills.add(ctx->d_counts.p + kTailReadsLeft, 0, 4);
         HIPCHECK(fills.launch(s));
     }
     // nodes: two per surviving read (graph.cpp:553-574)
-    if (!launch_node_pass(ctx->d_alive.p, ctx->d_node_rank.p, ctx->d_node_read.p, ctx->d_counts.p + 8, n_reads, sp, s)) {
+    if (!launch_node_pass(ctx->d_alive.p, ctx->d_node_rank.p, ctx->d_node_read.p, ctx->d_counts.p + kTailReadsLeft, n_reads, sp, s)) {
         return fail(ctx, RALA_HIP_EDEVICE, "scan space");
     }
     // the final overlap list: originals in order, then the promoted ones round by round; the two edges of
     // every dovetail (graph.cpp:576-632) with it
     for (uint32_t seg = 0; seg < n_seg; ++seg) {
-        // (the last segment's sums - the totals - go next to the other counts the host fetches: d_counts[6 .. 7])
+        // (the last segment's sums - the totals - go next to the other counts the host fetches: kTailTotals)
         if (!launch_segment_pass(L, R, seg == 0 ? 1u : 3u, seg == 0 ? 0u : seg - 1, ctx->d_seg_base.p + 2 * seg,
-                                 seg + 1 == n_seg ? ctx->d_counts.p + 6 : ctx->d_seg_base.p + 2 * (seg + 1), ctx->d_kept_item.p,
+                                 seg + 1 == n_seg ? ctx->d_counts.p + kTailTotals : ctx->d_seg_base.p + 2 * (seg + 1), ctx->d_kept_item.p,
                                  ctx->d_node_rank.p, ctx->d_e[0].p,
                                  ctx->d_e[1].p, ctx->d_e[2].p, sp, s)) {
             return fail(ctx, RALA_HIP_EDEVICE, "scan space");
         }
     }
-    uint32_t four[4] = {0, 0, 0, 0};         // kept items, dovetails, reads left, a containment scan that failed
-    HIPCHECK(d2h_small(ctx, four, ctx->d_counts.p + 6, 16, s));
+    struct { uint32_t kept, dovetails, reads_left, scan_failed; } look = {};       // kTailTotals .. kTailContain, one copy
+    static_assert(sizeof(look) == kTailLookWords * 4, "one word per count");
+    HIPCHECK(d2h_small(ctx, &look, ctx->d_counts.p + kTailTotals, sizeof(look), s));
     HIPCHECK(stream_sync(ctx, s));
-    const uint32_t totals[2] = {four[0], four[1]}, left[2] = {four[2], four[3]};
     HIPCHECK(hipGetLastError());
     if (getenv("RALA_HIP_TRACE")) {
-        uint32_t kc[4] = {0, 0, 0, 0};
-        HIPCHECK(hipMemcpy(kc, ctx->d_counts.p + 10, 16, hipMemcpyDeviceToHost));
+        struct { uint32_t ov, in, ov_conditional, in_conditional; } killers = {};
+        static_assert(sizeof(killers) == kTailKillerWords * 4, "one word per count");
+        HIPCHECK(hipMemcpy(&killers, ctx->d_counts.p + kTailKillers, sizeof(killers), hipMemcpyDeviceToHost));
         fprintf(stderr, "[trace] tail containment killers: %u (%u conditional) among the overlaps, %u (%u) among the internals, of %u items\n",
-                kc[0], kc[2], kc[1], kc[3], M);
+                killers.ov, killers.ov_conditional, killers.in, killers.in_conditional, M);
     }
-    if (left[1]) {
+    if (look.scan_failed) {
         return fail(ctx, RALA_HIP_EDEVICE, "containment fixed point did not converge");
     }
-    const uint32_t n_final = left[0];
-    ctx->t_n_kept = totals[0];
-    ctx->t_n_nodes = 2 * n_final;
-    ctx->t_n_edges = 2 * totals[1];
+    ctx->t_n_kept = look.kept;
+    ctx->t_n_nodes = 2 * look.reads_left;
+    ctx->t_n_edges = 2 * look.dovetails;
     mark("tail: final list, nodes, edges", ctx->t_n_edges);
     tail_left_on_device(ctx);
     return RALA_HIP_OK;
@@ -1628,8 +1636,10 @@ int materialize_host(rala_hip_ctx* ctx) {
     const uint32_t M = ctx->t_n0 + ctx->t_n1;
     std::vector<uint32_t> h[8];
     std::vector<uint8_t> strand(M), type(M), state(M);
+    uint32_t* c32[8];
     for (int f = 0; f < 8; ++f) {
         h[f].resize(M);
+        c32[f] = h[f].data();
         if (M) HIPCHECK(hipMemcpyAsync(h[f].data(), ctx->d_surv_u32[f].p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
     }
     std::vector<uint32_t> kept(ctx->t_n_kept);
@@ -1653,16 +1663,10 @@ int materialize_host(rala_hip_ctx* ctx) {
     }
     HIPCHECK(stream_sync(ctx, s));
     ctx->e_mark.assign(ctx->t_n_edges, 0);
-    auto item = [&](uint32_t k) {
-        HostOvl o;
-        o.src = h[0][k]; o.a = h[1][k]; o.b = h[2][k];
-        o.c.a_begin = h[3][k]; o.c.a_end = h[4][k]; o.c.b_begin = h[5][k]; o.c.b_end = h[6][k]; o.c.length = h[7][k];
-        o.strand = strand[k]; o.dead = 0; o.type = type[k];
-        return o;
-    };
+    const Survivors sv = survivors_of(c32, strand.data(), type.data());
     ctx->overlaps.clear(); ctx->internals.clear();
-    for (uint32_t k : kept) ctx->overlaps.push_back(item(k));
-    for (uint32_t k = ctx->t_n0; k < M; ++k) if (state[k] == 2) ctx->internals.push_back(item(k));
+    for (uint32_t k : kept) ctx->overlaps.push_back(host_item(sv, k));
+    for (uint32_t k = ctx->t_n0; k < M; ++k) if (state[k] == 2) ctx->internals.push_back(host_item(sv, k));
     host_lists_fetched(ctx);
     return RALA_HIP_OK;
 }
@@ -1700,7 +1704,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
     };
 
     if (ctx->dedupe_pending) {          // (a sharded run's duplicate removal ran beside the emit, on the side stream)
-        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[1], 0));
+        HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvEmitDedupeDone], 0));
         dedupe_joined(ctx);
     }
     // ---- static part ----
@@ -1712,12 +1716,12 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
     HIPCHECK(ctx->d_kill_count.ensure(kCountRing + 4));
     KillList kl;
     kl.count = ctx->d_kill_count.p; kl.ovl = ctx->d_kill[0].p; kl.target = ctx->d_kill[1].p; kl.keeper = ctx->d_kill[2].p;
-    HIPCHECK(hipEventRecord(ctx->ev[4], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvPass2Begin], s));
     HIPCHECK(ctx->d_rec.ensure(n_reads));
     // compact per-read records (valid region + two flags): 4 bytes when no read is longer than 32767 bases
     const bool small_rec = ctx->max_read_len <= 32767u;
     HIPCHECK(ctx->d_crec.ensure((size_t)n_reads * compact_record_bytes(small_rec) + 16));
-    HIPCHECK(ctx->d_counts.ensure(48));
+    HIPCHECK(ctx->d_counts.ensure(kCountsWords));
     // one buffer: sure[n_reads] (min over sure killers = upper bound), lo[n_reads] (lower bound),
     // one status word - so that a sharded run needs ONE all-reduce (min) per round; up[] apart
     HIPCHECK(ctx->d_death_sure.ensure(2 * (size_t)n_reads + 8));
@@ -1732,7 +1736,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
         const int rc = scan_space(ctx, 1, pass2_chunks(N), chunk_scan, &fills);
         if (rc != RALA_HIP_OK) return rc;
         fills.add(ctx->d_kill_count.p, 0, (kCountRing + 4) * 4);
-        fills.add(ctx->d_counts.p, 0, 48 * 4);
+        fills.add(ctx->d_counts.p, 0, kCountsWords * 4);
         fills.add(sure, 0xFF, 2 * dbytes + 4);
         fills.add(ctx->d_fp_map.p, 0xFF, dbytes);               // (launch_fixed_point_finish leaves it that way; here for good measure)
         HIPCHECK(fills.launch(s));
@@ -1741,7 +1745,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
     if (ctx->debug_fail_construct) return fail(ctx, RALA_HIP_EDEVICE, "debug_fail_construct");
     launch_pack_reads(rs, n_reads, ctx->d_rec.p, ctx->d_crec.p, small_rec, sure, s);
     launch_classify(ctx->ovl, n_reads, ctx->d_valid.p, ctx->d_crec.p, small_rec, kl, lo, s);
-    HIPCHECK(hipEventRecord(ctx->ev[5], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvPass2Classified], s));
 
     // ---- in-order containment removal as a fixed point (death_decide_kernel) ----
     for (int k = 0; k < 3; ++k) HIPCHECK(ctx->d_kill2[k].ensure(kill_room));
@@ -1791,8 +1795,8 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
             HIPCHECK(ctx->d_t_work[0].ensure(n_reads));
             uint32_t* const work[4] = {up, lo, ctx->d_death[0].p, ctx->d_t_work[0].p};
             const FixedPointList rest = {klist[cur].ovl, klist[cur].target, klist[cur].keeper, klist[cur].count, ctx->debug_fp_lds_limit, ctx->debug_fp_give_up};
-            HIPCHECK(launch_fixed_point_finish(rest, sure, ctx->d_fp_map.p, ctx->d_fp_pack.p, work, ctx->d_counts.p + 32,
-                                               ctx->d_counts.p + 1, ctx->d_counts.p + 2, s));
+            HIPCHECK(launch_fixed_point_finish(rest, sure, ctx->d_fp_map.p, ctx->d_fp_pack.p, work, ctx->d_counts.p + kPass2Sync,
+                                               ctx->d_counts.p + kPass2Verdict, ctx->d_counts.p + kPass2FinishRounds, s));
             finished_on_device = true;
             return (int)RALA_HIP_OK;
         };
@@ -1860,7 +1864,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
         }
     }
     uint32_t* death = sure;
-    HIPCHECK(hipEventRecord(ctx->ev[6], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvPass2Decided], s));
 
     // ---- liveness, hill counters, survivors ----
     const uint32_t n_chunks = pass2_chunks(N);
@@ -1869,7 +1873,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
     uint64_t* mask_ov = (uint64_t*)ctx->d_cls.p;
     uint64_t* mask_in = mask_ov + mask_words;
     HIPCHECK(ctx->d_fate.ensure(n_reads));
-    launch_apply_death(death, ctx->d_alive.p, ctx->d_n_hills.p, ctx->d_fate.p, n_reads, ctx->d_counts.p + 0, s);
+    launch_apply_death(death, ctx->d_alive.p, ctx->d_n_hills.p, ctx->d_fate.p, n_reads, ctx->d_counts.p + kPass2ReadsAlive, s);
     launch_survivor_masks(ctx->ovl, n_reads, ctx->d_valid.p, ctx->d_fate.p, death, ctx->d_crec.p, small_rec, ctx->d_rec.p,
                           ctx->d_pool.p, mask_ov, mask_in, ctx->d_chunk[0].p, ctx->d_chunk[1].p, s);
     if (comm && ctx->pool_used) {
@@ -1881,23 +1885,22 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
         launch_hill_counts(rs, n_reads, ctx->d_t_tmp[0].p, 1, s);
     }
     // the chunks' places in the two survivor lists: one scan; its sums come back with the other counts
-    if (!launch_pair_offsets_pass(ctx->d_chunk[0].p, ctx->d_chunk[1].p, ctx->d_chunk[2].p, ctx->d_chunk[3].p, ctx->d_counts.p + 6,
+    if (!launch_pair_offsets_pass(ctx->d_chunk[0].p, ctx->d_chunk[1].p, ctx->d_chunk[2].p, ctx->d_chunk[3].p, ctx->d_counts.p + kPass2Survivors,
                                   n_chunks, chunk_scan, s)) {
         return fail(ctx, RALA_HIP_EDEVICE, "scan space");
     }
     uint32_t round_log[64];
     if (n_logged && !finished_on_device) HIPCHECK(d2h_small(ctx, round_log, ctx->d_round_log.p, n_logged * 4, s));
-    uint32_t counts8[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] reads alive, [1] the finishing kernel's verdict, [2] its rounds, [6 .. 7] survivors
-    HIPCHECK(d2h_small(ctx, counts8, ctx->d_counts.p + 0, 32, s));
+    uint32_t counts8[kPass2LookWords] = {};            // (Pass2Counts, slots.h)
+    HIPCHECK(d2h_small(ctx, counts8, ctx->d_counts.p, sizeof(counts8), s));
     HIPCHECK(stream_sync(ctx, s));
-    const uint32_t n_surv[2] = {counts8[6], counts8[7]};
-    const uint32_t* counts3 = counts8;
-    if (counts3[1]) {
+    const uint32_t n_surv[2] = {counts8[kPass2Survivors], counts8[kPass2Survivors + 1]};
+    if (counts8[kPass2Verdict]) {
         return fail(ctx, RALA_HIP_EDEVICE, "containment fixed point did not converge");
     }
-    ctx->t_n_alive = counts3[0];            // the reads that survived the second pass (the tail's rank space)
+    ctx->t_n_alive = counts8[kPass2ReadsAlive];        // the reads that survived the second pass (the tail's rank space)
     if (finished_on_device) {
-        ctx->tm.death_rounds = (uint32_t)list_size.size() + counts3[2];
+        ctx->tm.death_rounds = (uint32_t)list_size.size() + counts8[kPass2FinishRounds];
     } else {
         // rounds until the list was empty
         uint32_t at = 0;
@@ -1907,15 +1910,6 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
             if (sz == 0) { ctx->tm.death_rounds = (uint32_t)r + 1; break; }
         }
     }
-    auto tail_view = [&]() {
-        Survivors sv;
-        sv.src = ctx->d_surv_u32[0].p; sv.a_id = ctx->d_surv_u32[1].p; sv.b_id = ctx->d_surv_u32[2].p;
-        sv.a_begin = ctx->d_surv_u32[3].p; sv.a_end = ctx->d_surv_u32[4].p;
-        sv.b_begin = ctx->d_surv_u32[5].p; sv.b_end = ctx->d_surv_u32[6].p;
-        sv.length = ctx->d_surv_u32[7].p;
-        sv.strand = ctx->d_surv_u8[0].p; sv.type = ctx->d_surv_u8[1].p;
-        return sv;
-    };
     if (!comm) {
         // both survivor lists side by side in one device list: overlaps, then internals
         const uint32_t M = n_surv[0] + n_surv[1];
@@ -1923,7 +1917,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
         for (int f = 0; f < 8; ++f) HIPCHECK(ctx->d_surv_u32[f].ensure(M));
         for (int f = 0; f < 2; ++f) HIPCHECK(ctx->d_surv_u8[f].ensure(M));
         // trim in the gather re-derives the coordinates against the pass-1 piles
-        if (M) launch_gather_survivors(ctx->ovl, mask_ov, mask_in, ctx->d_crec.p, small_rec, ctx->d_chunk[2].p, ctx->d_chunk[3].p, n_surv[0], tail_view(), s);
+        if (M) launch_gather_survivors(ctx->ovl, mask_ov, mask_in, ctx->d_crec.p, small_rec, ctx->d_chunk[2].p, ctx->d_chunk[3].p, n_surv[0], survivors_view(ctx), s);
     } else {
         // this slice's survivors as one packed block, all blocks gathered, unpacked in rank order
         const uint32_t P = comm->world();
@@ -1957,17 +1951,17 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
         // kernel over the items.
         hipStream_t gs = ctx->use_side_stream ? ctx->side : s;
         if (gs != s) {
-            HIPCHECK(hipEventRecord(ctx->ev[2], s));
-            HIPCHECK(hipStreamWaitEvent(gs, ctx->ev[2], 0));
+            HIPCHECK(hipEventRecord(ctx->ev[kEvGatherFork], s));
+            HIPCHECK(hipStreamWaitEvent(gs, ctx->ev[kEvGatherFork], 0));
         }
         if (comm->all_gather_v(ctx->d_list_block[0].p, ctx->d_list_block[1].p, bytes.data(), 1, gs) != 0) return comm_fail("all-gather of the survivors");
-        if (M) launch_unpack_lists(ctx->d_list_block[1].p, lb, tail_view(), gs);
+        if (M) launch_unpack_lists(ctx->d_list_block[1].p, lb, survivors_view(ctx), gs);
         if (gs != s) {
-            HIPCHECK(hipEventRecord(ctx->ev[3], gs));
+            HIPCHECK(hipEventRecord(ctx->ev[kEvGatherJoin], gs));
             ctx->lists_pending = true;
         }
     }
-    HIPCHECK(hipEventRecord(ctx->ev[7], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvPass2End], s));
     HIPCHECK(hipGetLastError());
     return RALA_HIP_OK;
 }
@@ -1980,11 +1974,11 @@ int check_constructible(rala_hip_ctx* ctx) {
     return RALA_HIP_OK;
 }
 
-// pass 2's event times into ctx->tm (once the stream has passed ev[7])
+// pass 2's event times into ctx->tm (once the stream has passed kEvPass2End)
 int pass2_times(rala_hip_ctx* ctx) {
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[4], ctx->ev[5]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[5], ctx->ev[6]));
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[6], ctx->ev[7]));
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.classify_ms, ctx->ev[kEvPass2Begin], ctx->ev[kEvPass2Classified]));
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.death_ms, ctx->ev[kEvPass2Classified], ctx->ev[kEvPass2Decided]));
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.finish_ms, ctx->ev[kEvPass2Decided], ctx->ev[kEvPass2End]));
     return RALA_HIP_OK;
 }
 
@@ -2112,12 +2106,12 @@ int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* se
         HIPCHECK(ctx->d_dedupe_list.ensure(2 * (size_t)kMarks + 4));
         HIPCHECK(hipMemsetAsync(ctx->d_dedupe_list.p + 2 * (size_t)kMarks, 0, 4, s));
         bd.suspect = ctx->d_suspect.p; bd.valid = ctx->d_valid.p; bd.list_pos = ctx->d_dedupe_list.p; bd.list_query = ctx->d_dedupe_list.p + kMarks;
-        bd.list_cap = ctx->debug_dedupe_list_cap ? std::min(kMarks, ctx->debug_dedupe_list_cap) : kMarks; bd.list_count = ctx->d_dedupe_list.p + 2 * (size_t)kMarks; bd.counted = ctx->ev[0];
+        bd.list_cap = ctx->debug_dedupe_list_cap ? std::min(kMarks, ctx->debug_dedupe_list_cap) : kMarks; bd.list_count = ctx->d_dedupe_list.p + 2 * (size_t)kMarks; bd.counted = ctx->ev[kEvEmitCounted];
     } else if (ctx->use_side_stream) {
-        HIPCHECK(hipEventRecord(ctx->ev[0], s));
-        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[0], 0));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvEmitCounted], s));
+        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[kEvEmitCounted], 0));
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, ctx->side);
-        HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvEmitDedupeDone], ctx->side));
         dedupe_forked(ctx);
     } else {
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, s);
@@ -2130,9 +2124,9 @@ int rala_hip::shard_emit(rala_hip_ctx* ctx, const ShardGeometry& g, uint64_t* se
     HIPCHECK(launch_shard_emit(ctx->ovl, n_reads, g, ctx->d_shard_group.p, ctx->d_shard_part.p, send, ctx->d_shard_words.p,
                                ctx->n_compute_units, fills, s, counted ? &bd : nullptr));
     if (counted && ctx->n_ovl) {
-        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[0], 0));
+        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[kEvEmitCounted], 0));
         launch_dedupe_fix(ctx->ovl, n_reads, bd, ctx->side);
-        HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvEmitDedupeDone], ctx->side));
         dedupe_forked(ctx);
     }
     uint32_t h[64];
@@ -2193,9 +2187,9 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         if (ec != hipSuccess) HIPCHECK(ctx->d_pile.ensure(ctx->pile_elems + 8));
     }
     // (whatever a failed call may have left on the aux stream ends before the counters are reset)
-    HIPCHECK(hipEventRecord(ctx->ev[9], ctx->aux));
-    HIPCHECK(hipStreamWaitEvent(s, ctx->ev[9], 0));
-    HIPCHECK(hipEventRecord(ctx->ev[0], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvAuxDrained], ctx->aux));
+    HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvAuxDrained], 0));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvInitBegin], s));
     // RALA_HIP_MEM_HOST_ASYNC: the columns leave the host now, in the order the kernels want them; the kernels below wait for
     // the event of the column they read first (the copy stream is in order: a later event covers the earlier columns)
     const bool uploading = ctx->upload_pending;
@@ -2203,7 +2197,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         const size_t n4 = (size_t)ctx->n_ovl * 4;
         auto up = [&](int k) { return hipMemcpyAsync(ctx->d_ovl_u32[k].p, ctx->up_src[k], n4, hipMemcpyHostToDevice, ctx->copy); };
         // (a failed call may have left kernels that still read the columns: the copies behind them)
-        HIPCHECK(hipStreamWaitEvent(ctx->copy, ctx->ev[0], 0));
+        HIPCHECK(hipStreamWaitEvent(ctx->copy, ctx->ev[kEvInitBegin], 0));
         HIPCHECK(up(0)); HIPCHECK(up(1));
         HIPCHECK(hipEventRecord(ctx->ev_up[0], ctx->copy));
         HIPCHECK(up(4)); HIPCHECK(up(5));
@@ -2222,7 +2216,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     };
     // the call's counters and what the bucketing wants cleared: one fill (fill_kernels.hip)
     FillList fills;
-    fills.add(ctx->d_small.p, 0, 16 * 4);
+    fills.add(ctx->d_small.p, 0, kSmallWords * 4);
     // duplicate removal only feeds the second pass (every resolvable overlap adds its bounds,
     // valid or not): it runs on a second stream and the main stream joins it after the pile kernels.
     // Beside WHAT it runs: beside the single-pass bucketing, both reading the same columns while the
@@ -2239,7 +2233,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
     }
     if (!forked) {
         if (!ctx->tuple_mode) launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, s);
-        HIPCHECK(hipEventRecord(ctx->ev[1], s));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvInitDedupeDone], s));
     }
     // bucket bounds by read.  Fast path: one kernel into fixed slots of kRunEventCapBig events per
     // read (8 KB; 8 GB at a million reads - HBM is 288 GB); the position inside the slot is what the
@@ -2288,9 +2282,9 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         if (rcw != RALA_HIP_OK) return rcw;
     }
     if (dedupe_early && !dedupe_counted) {
-        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[0], 0));
+        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[kEvInitBegin], 0));
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, ctx->side);
-        HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvInitDedupeDone], ctx->side));
     }
     if (from_blocks) {
         const ShardGeometry& g = ctx->shard_geom;
@@ -2315,32 +2309,32 @@ static int initialize_stages(rala_hip_ctx* ctx) {
             if (dedupe_counted) HIPCHECK(ctx->d_dedupe_list.ensure(2 * (size_t)kMarks));
             BucketDedupe bd = {ctx->d_suspect.p, ctx->d_valid.p, ctx->d_dedupe_list.p, ctx->d_dedupe_list.p + kMarks,
                                ctx->debug_dedupe_list_cap ? std::min(kMarks, ctx->debug_dedupe_list_cap) : kMarks,
-                               ctx->d_small.p + 9, ctx->ev[8]};     // ([9]: zeroed with d_small above)
+                               ctx->d_small.p + kInitDedupeMarks, ctx->ev[kEvBucketCounted]};     // (the marks' count: zeroed with d_small above)
             if (fine_upload) { bd.ids = ctx->ev_up[0]; bd.b_coords = ctx->ev_up[1]; bd.a_coords = ctx->ev_up[2]; }
             HIPCHECK(launch_bucket_partitioned(ctx->ovl, n_reads, bt, ctx->d_bk_u32[0].p, ctx->d_bk_u32[2].p,
                                                ctx->d_bk_part.p, ctx->d_bk_group.p, ctx->d_bk_tiles.p, ctx->d_bk_rec[0].p,
                                                ctx->d_bk_rec[1].p, ctx->d_ev_off.p, ctx->d_ev.p, ctx->n_compute_units, fills, s,
                                                dedupe_counted ? &bd : nullptr, ev_shift));
             if (dedupe_counted) {
-                HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[8], 0));
+                HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[kEvBucketCounted], 0));
                 if (fine_upload) HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev_up[3], 0));      // (the lengths)
                 launch_dedupe_fix(ctx->ovl, n_reads, bd, ctx->side);
-                HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
+                HIPCHECK(hipEventRecord(ctx->ev[kEvInitDedupeDone], ctx->side));
             }
         }
     }
     if (fixed) {
         HIPCHECK(ctx->d_ev_fixed.ensure((size_t)n_reads * slot + 8));
-        HIPCHECK(ctx->d_cc_flags.ensure(8));
+        HIPCHECK(ctx->d_cc_flags.ensure(kCcFlagsWords));
         fills.add(ctx->d_cursor.p, 0, (size_t)(n_reads + 1) * 4);
         HIPCHECK(fills.launch(s));
         // (the slot-overflow flag and the count of dead reads below live in d_small, zeroed above and
         // fetched in one copy with the other results)
         if (ctx->tuple_mode) {
             launch_bucket_fixed_tuples(ctx->tuples, ctx->n_tuples, n_reads, slot, ctx->d_cursor.p,
-                                       ctx->d_ev_fixed.p, ctx->d_small.p + 6, s);
+                                       ctx->d_ev_fixed.p, ctx->d_small.p + kInitSlotOverflow, s);
         } else {
-            launch_bucket_fixed(ctx->ovl, n_reads, slot, ctx->d_cursor.p, ctx->d_ev_fixed.p, ctx->d_small.p + 6, s);
+            launch_bucket_fixed(ctx->ovl, n_reads, slot, ctx->d_cursor.p, ctx->d_ev_fixed.p, ctx->d_small.p + kInitSlotOverflow, s);
         }
         // the overflow flag is read together with the other results at the end of this call; a
         // set flag repeats the call on the exact path (no host round trip in the common case)
@@ -2363,30 +2357,26 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         launch_scatter_bounds(ctx->ovl, n_reads, ctx->d_ev_off.p, ctx->d_slot_rank[0].p, ctx->d_slot_rank[1].p, ctx->d_ev.p, s);
     }
     }
-    HIPCHECK(hipEventRecord(ctx->ev[2], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvInitBucketed], s));
     if (forked && !dedupe_early) {
-        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[2], 0));
+        HIPCHECK(hipStreamWaitEvent(ctx->side, ctx->ev[kEvInitBucketed], 0));
         launch_dedupe(ctx->ovl, n_reads, ctx->d_suspect.p, ctx->d_valid.p, ctx->side);
-        HIPCHECK(hipEventRecord(ctx->ev[1], ctx->side));
+        HIPCHECK(hipEventRecord(ctx->ev[kEvInitDedupeDone], ctx->side));
     }
 
-    PileArgs a;
-    a.read_len = ctx->d_read_len.p; a.pile_off = ctx->d_pile_off.p; a.pile = ctx->rowless ? nullptr : ctx->d_pile.p;
-    a.ev_off = ctx->d_ev_off.p; a.ev = fixed ? ctx->d_ev_fixed.p : ctx->d_ev.p;
-    a.ev_cnt = fixed ? ctx->d_cursor.p : nullptr; a.ev_stride = slot;
+    static_assert(slot == kRunEventCapBig, "pile_args' stride is the fixed slot");
     ctx->ev_shift = ev_shift;
-    a.ev_shift = ev_shift;
+    PileArgs a = pile_args(ctx, primary_events(ctx, fixed, ev_shift));
     a.rows_chunked = ctx->d_pile.reserved ? 1u : 0u;
-    a.add_to_existing = 0; a.slab = ctx->d_slab.p;
+    a.slab = ctx->d_slab.p;
     a.stop_after = (uint32_t)ctx->debug_pile_stop_after;
     a.variant = ctx->debug_pile_variant;
-    a.begin = ctx->d_begin.p; a.end = ctx->d_end.p; a.median = ctx->d_median.p; a.p10 = ctx->d_p10.p;
     a.alive = ctx->d_alive.p; a.n_pits = ctx->d_n_pits.p; a.n_hills = ctx->d_n_hills.p; a.iv_slot = ctx->d_iv_slot.p;
-    a.pool = ctx->d_pool.p; a.pool_count = ctx->d_small.p; a.pool_cap = ctx->pool_cap; a.error = ctx->d_small.p + 1;
-    a.n_items_dev = nullptr;
+    a.pool = ctx->d_pool.p; a.pool_count = ctx->d_small.p + kInitPoolCount; a.pool_cap = ctx->pool_cap;
+    a.error = ctx->d_small.p + kInitStatus;
     // (what outgrows the position-space kernel's LDS lists: noted, and dealt with after this call's one look from the host)
     HIPCHECK(ctx->d_big_list[0].ensure(n_reads + 1));
-    a.big_list = ctx->d_big_list[0].p; a.big_count = ctx->d_small.p + 8;
+    a.big_list = ctx->d_big_list[0].p; a.big_count = ctx->d_small.p + kInitNotedReads;
     a.force_big = ctx->debug_force_big ? 1u : 0u;
     if (ctx->use_run_kernel) {
         // Chain without host synchronisation.  Every read starts in the kernel that fits it, known
@@ -2410,10 +2400,10 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         uint32_t* list2 = ctx->d_overflow_mid.p;
         uint32_t* list3 = ctx->d_order.p;
         // (all four zeroed with d_small at the top of this call)
-        uint32_t* cnt_dense = ctx->d_small.p + 3;
-        uint32_t* cnt1 = ctx->d_small.p + 4;
-        uint32_t* cnt2 = ctx->d_small.p + 2;
-        uint32_t* cnt3 = ctx->d_small.p + 5;
+        uint32_t* cnt_dense = ctx->d_small.p + kInitDenseReads;
+        uint32_t* cnt1 = ctx->d_small.p + kInitToCap1024;
+        uint32_t* cnt2 = ctx->d_small.p + kInitToCap2048;
+        uint32_t* cnt3 = ctx->d_small.p + kInitToPosition;
         const uint32_t n_short = ctx->n_class[0], n_medium = ctx->n_class[1], n_long = ctx->n_class[2];
         const uint32_t* by_class = n_short != n_reads ? ctx->d_class_order.p : nullptr;
         // few longer reads: the first kernel goes over all reads without the indirection (2 % at C3)
@@ -2422,7 +2412,7 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         const bool short_by_list = by_class && (force_order || (uint64_t)(n_reads - n_short) * 8 > n_reads);
         static const bool no_aux = getenv("RALA_PILE_NO_AUX") != nullptr;       // measurements: everything on one stream
         hipStream_t aux = ctx->use_side_stream && !no_aux ? ctx->aux : s;
-        if (aux != s) HIPCHECK(hipStreamWaitEvent(aux, ctx->ev[2], 0));
+        if (aux != s) HIPCHECK(hipStreamWaitEvent(aux, ctx->ev[kEvInitBucketed], 0));
         a.lw = 0;
         a.skip_dense = 1;
         launch_pile_dense_list(a, n_reads, list_dense, cnt_dense, aux);
@@ -2439,11 +2429,11 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         a.order = by_class ? by_class + n_short + n_medium : nullptr;
         a.n_items = n_long;
         launch_pile_runs(a, std::min<uint32_t>(n_long, 20480), 4, list1, cnt1, aux);
-        if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[8], aux));
+        if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[kEvPileAuxDone], aux));
         a.order = short_by_list ? by_class : nullptr;
         a.n_items = short_by_list ? n_short : n_reads;
         launch_pile_runs(a, a.n_items, 0, list1, cnt1, s);
-        if (aux != s) HIPCHECK(hipStreamWaitEvent(s, ctx->ev[8], 0));
+        if (aux != s) HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvPileAuxDone], 0));
         a.n_items = n_reads;
         a.order = list1;
         a.n_items_dev = cnt1;
@@ -2467,13 +2457,13 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         const int rc2 = run_position_kernel(ctx, a, reads);
         if (rc2 != RALA_HIP_OK) return rc2;
     }
-    HIPCHECK(hipEventRecord(ctx->ev[3], s));
+    HIPCHECK(hipEventRecord(ctx->ev[kEvInitPilesDone], s));
     HIPCHECK(hipGetLastError());
-    if (forked) HIPCHECK(hipStreamWaitEvent(s, ctx->ev[1], 0));
+    if (forked) HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvInitDedupeDone], 0));
 
     // the per-read results stay on the device; host mirrors are fetched by the first getter
-    launch_count_zero_u8(ctx->d_alive.p, n_reads, ctx->d_small.p + 7, s);
-    uint32_t small[16];
+    launch_count_zero_u8(ctx->d_alive.p, n_reads, ctx->d_small.p + kInitDeadReads, s);
+    uint32_t small[kSmallWords];
     HIPCHECK(d2h_small(ctx, small, ctx->d_small.p, sizeof(small), s));
     HIPCHECK(stream_sync(ctx, s));
     if (uploading) {
@@ -2481,19 +2471,19 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         HIPCHECK(hipStreamSynchronize(ctx->copy));
         upload_done(ctx);
     }
-    const uint32_t slot_overflow = fixed ? small[6] : 0;
-    if (small[8] && !slot_overflow) {
+    const uint32_t slot_overflow = fixed ? small[kInitSlotOverflow] : 0;
+    if (small[kInitNotedReads] && !slot_overflow) {
         // reads whose region / interval lists outgrew the position-space kernel's LDS lists
-        const int rc_big = run_unbounded_piles(ctx, a, small[8], ctx->d_small.p + 8);
+        const int rc_big = run_unbounded_piles(ctx, a, small[kInitNotedReads], ctx->d_small.p + kInitNotedReads);
         if (rc_big != RALA_HIP_OK) return rc_big;
-        HIPCHECK(hipMemsetAsync(ctx->d_small.p + 7, 0, 4, s));
-        launch_count_zero_u8(ctx->d_alive.p, n_reads, ctx->d_small.p + 7, s);
-        const uint32_t noted = small[8];
+        HIPCHECK(hipMemsetAsync(ctx->d_small.p + kInitDeadReads, 0, 4, s));
+        launch_count_zero_u8(ctx->d_alive.p, n_reads, ctx->d_small.p + kInitDeadReads, s);
+        const uint32_t noted = small[kInitNotedReads];
         HIPCHECK(d2h_small(ctx, small, ctx->d_small.p, sizeof(small), s));
         HIPCHECK(stream_sync(ctx, s));
-        small[8] = noted;
+        small[kInitNotedReads] = noted;
     }
-    const uint32_t n_dead = small[7];
+    const uint32_t n_dead = small[kInitDeadReads];
     if (slot_overflow) {
         // some read has more events than a fixed slot holds: once more, through the exact path
         const int64_t keep = ctx->use_fixed_buckets;
@@ -2502,40 +2492,40 @@ static int initialize_stages(rala_hip_ctx* ctx) {
         ctx->use_fixed_buckets = keep;
         return rc_again;
     }
-    ctx->tm.pile_overflow_reads = ctx->use_run_kernel ? small[3] + small[4] : 0;      // event-dense + handed on
+    ctx->tm.pile_overflow_reads = ctx->use_run_kernel ? small[kInitDenseReads] + small[kInitToCap1024] : 0;      // event-dense + handed on
     if (getenv("RALA_HIP_TRACE") || getenv("RALA_HIP_TRACE_BUFFERS")) {
         fprintf(stderr, "[trace] buffers: events %p (CSR %p) slots %p counts %p piles %p a_id %p b_id %p b_begin %p\n", (void*)ctx->d_ev.p, (void*)ctx->d_ev_off.p, (void*)ctx->d_ev_fixed.p,
                 (void*)ctx->d_cursor.p, (void*)ctx->d_pile.p, (const void*)ctx->ovl.a_id, (const void*)ctx->ovl.b_id,
                 (const void*)ctx->ovl.b_begin);
         if (getenv("RALA_HIP_TRACE")) fprintf(stderr, "[trace] pile chain: %u reads listed as event-dense, %u handed on by the cap-512 kernels, %u on to cap 2048, %u to position space\n",
-                small[3], small[4], small[2], small[5]);
+                small[kInitDenseReads], small[kInitToCap1024], small[kInitToCap2048], small[kInitToPosition]);
     }
-    ctx->tm.pile_position_reads = ctx->use_run_kernel ? small[5] : n_reads;
+    ctx->tm.pile_position_reads = ctx->use_run_kernel ? small[kInitToPosition] : n_reads;
     // dedupe_ms: what duplicate removal adds to the critical path (it runs beside the bucketing
     // and the pile kernels; the main stream joins it after them)
     {
         float dd = 0, bk = 0, all = 0;
-        HIPCHECK(hipEventElapsedTime(&dd, ctx->ev[0], ctx->ev[1]));
-        HIPCHECK(hipEventElapsedTime(&bk, forked ? ctx->ev[0] : ctx->ev[1], ctx->ev[2]));
-        HIPCHECK(hipEventElapsedTime(&all, ctx->ev[0], ctx->ev[3]));
+        HIPCHECK(hipEventElapsedTime(&dd, ctx->ev[kEvInitBegin], ctx->ev[kEvInitDedupeDone]));
+        HIPCHECK(hipEventElapsedTime(&bk, forked ? ctx->ev[kEvInitBegin] : ctx->ev[kEvInitDedupeDone], ctx->ev[kEvInitBucketed]));
+        HIPCHECK(hipEventElapsedTime(&all, ctx->ev[kEvInitBegin], ctx->ev[kEvInitPilesDone]));
         ctx->tm.bucket_ms = bk;
         ctx->tm.dedupe_ms = forked ? std::max(0.0f, dd - all) : dd;
     }
-    HIPCHECK(hipEventElapsedTime(&ctx->tm.pile_ms, ctx->ev[2], ctx->ev[3]));
-    if (small[1] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow in the pile kernel");
-    if (small[1] & kErrPoolCapacity) {
+    HIPCHECK(hipEventElapsedTime(&ctx->tm.pile_ms, ctx->ev[kEvInitBucketed], ctx->ev[kEvInitPilesDone]));
+    if (small[kInitStatus] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow in the pile kernel");
+    if (small[kInitStatus] & kErrPoolCapacity) {
         // more pits and hills than the pool holds (interval_pool_per_read_x1000 is a hint): its counter holds what is needed -
         // once more with a pool of that size (and a little more: the slots of reads that ran twice are not handed back)
-        const uint64_t need = (uint64_t)small[0] + small[0] / 8 + 1024;
-        if (small[0] <= ctx->pool_cap || need > 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ENOMEM, "interval pool beyond 2^32 entries");
-        ctx->pool_cap = (uint32_t)need;
+        const uint32_t need = grown_pool_size(small[kInitPoolCount], ctx->pool_cap);
+        if (!need) return fail(ctx, RALA_HIP_ENOMEM, "interval pool beyond 2^32 entries");
+        ctx->pool_cap = need;
         HIPCHECK(ctx->d_pool.ensure(ctx->pool_cap));
         const uint32_t regrown = ctx->tm.pool_regrown + 1;
         const int rc_again = rala_hip_initialize(ctx);
         ctx->tm.pool_regrown = regrown;
         return rc_again;
     }
-    state_installed(ctx, n_dead, std::min(small[0], ctx->pool_cap), true, fixed, !ctx->tuple_mode);
+    state_installed(ctx, n_dead, std::min(small[kInitPoolCount], ctx->pool_cap), true, fixed, !ctx->tuple_mode);
     if (ctx->n_prefiltered == ctx->n_reads) return fail(ctx, RALA_HIP_EFILTERED, "filtered all sequences");
     return RALA_HIP_OK;
 }
@@ -2637,8 +2627,10 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
     tail_begun(ctx);
     // lists to the host
     std::vector<HostOvl>* lists[2] = {&ctx->overlaps, &ctx->internals};
+    uint32_t* c32[8];
     for (int f = 0; f < 8; ++f) {
         HIPCHECK(ctx->p_surv_u32[f].ensure(M));
+        c32[f] = ctx->p_surv_u32[f].p;
         if (M) HIPCHECK(hipMemcpyAsync(ctx->p_surv_u32[f].p, ctx->d_surv_u32[f].p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
     }
     for (int f = 0; f < 2; ++f) {
@@ -2646,6 +2638,7 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
         if (M) HIPCHECK(hipMemcpyAsync(ctx->p_surv_u8[f].p, ctx->d_surv_u8[f].p, M, hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(stream_sync(ctx, s));
+    const Survivors sv = survivors_of(c32, ctx->p_surv_u8[0].p, ctx->p_surv_u8[1].p);
     for (int k = 0; k < 2; ++k) {
         const uint32_t m = n_surv[k];
         const uint32_t off = k == 0 ? 0 : n_surv[0];
@@ -2654,18 +2647,8 @@ int rala_hip_construct(rala_hip_ctx* ctx, const rala_hip_overlaps* sens, uint64_
         lists[k]->reserve(k == 0 ? (size_t)M : (size_t)m);
         lists[k]->resize(m);
         std::vector<HostOvl>& dst = *lists[k];
-        uint32_t* hp[8];
-        for (int f = 0; f < 8; ++f) hp[f] = ctx->p_surv_u32[f].p + off;
-        const uint8_t* hs = ctx->p_surv_u8[0].p + off;
-        const uint8_t* ht = ctx->p_surv_u8[1].p + off;
         ctx->pool->chunks(m, [&](unsigned, size_t b0, size_t e0) {
-            for (size_t i = b0; i < e0; ++i) {
-                HostOvl& o = dst[i];
-                o.src = hp[0][i]; o.a = hp[1][i]; o.b = hp[2][i];
-                o.c.a_begin = hp[3][i]; o.c.a_end = hp[4][i]; o.c.b_begin = hp[5][i]; o.c.b_end = hp[6][i];
-                o.c.length = hp[7][i];
-                o.strand = hs[i]; o.dead = 0; o.type = ht[i];
-            }
+            for (size_t i = b0; i < e0; ++i) dst[i] = host_item(sv, off + i);
         });
     }
     // refreshed read state: liveness after the scan, hill counters in the pool
@@ -2719,7 +2702,7 @@ int rala_hip_find_repetitive_hills(rala_hip_ctx* ctx, uint64_t read, uint32_t be
     HIPCHECK(ctx->d_rep_pool.ensure(ctx->rep_pool_cap));
     if (!ctx->have_repeats) {
         HIPCHECK(hipMemsetAsync(ctx->d_n_rep.p, 0, n * 4, s));
-        HIPCHECK(hipMemsetAsync(ctx->d_small.p + 6, 0, 8, s));
+        HIPCHECK(hipMemsetAsync(ctx->d_small.p + kSensPoolCount, 0, kSensPoolWords * 4, s));
         ctx->h_n_rep.assign(n, 0); ctx->h_rep_slot.assign(n, 0); ctx->h_rep_pool.clear();
     }
     // the valid region as it stands (the host mirrors are authoritative after a host tail)
@@ -2728,45 +2711,39 @@ int rala_hip_find_repetitive_hills(rala_hip_ctx* ctx, uint64_t read, uint32_t be
     HIPCHECK(hipMemcpyAsync(ctx->d_median.p + read, &ctx->h_median[read], 2, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(ctx->d_p10.p + read, &ctx->h_p10[read], 2, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(ctx->d_dataset_median.p + read, &dataset_median, 2, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(ctx->d_small.p + 7, 0, 4, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_small.p + kSensStatus, 0, 4, s));
     HIPCHECK(stream_sync(ctx, s));
-    RepeatArgs a;
-    a.read_len = ctx->d_read_len.p; a.pile_off = ctx->d_pile_off.p; a.pile = ctx->d_pile.p;
+    RepeatArgs a = repeat_args(ctx);
     a.ev_off = ctx->d_ev_off.p; a.ev = ctx->d_ev.p;
-    a.begin = ctx->d_begin.p; a.end = ctx->d_end.p; a.median = ctx->d_median.p; a.p10 = ctx->d_p10.p;
-    a.dataset_median = ctx->d_dataset_median.p; a.n_rep = ctx->d_n_rep.p; a.rep_slot = ctx->d_rep_slot.p;
-    a.pool = ctx->d_rep_pool.p; a.pool_count = ctx->d_small.p + 6; a.pool_cap = ctx->rep_pool_cap;
-    a.error = ctx->d_small.p + 7;
-    a.order = nullptr; a.n_items = 0; a.lw = 0; a.slab = nullptr;
     const std::vector<uint32_t> one(1, (uint32_t)read);
-    uint32_t small[8];
+    uint32_t small[kSensStatus + 1];            // d_small up to the status
     for (;;) {
         uint32_t used_before = 0;
-        HIPCHECK(hipMemcpy(&used_before, ctx->d_small.p + 6, 4, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&used_before, ctx->d_small.p + kSensPoolCount, 4, hipMemcpyDeviceToHost));
         const int rc = run_repeats_kernel(ctx, a, one, 2);
         if (rc != RALA_HIP_OK) return rc;
         HIPCHECK(hipMemcpy(small, ctx->d_small.p, sizeof(small), hipMemcpyDeviceToHost));
-        if (!(small[7] & kErrPoolCapacity)) break;
+        if (!(small[kSensStatus] & kErrPoolCapacity)) break;
         // the pool (it keeps the hills of earlier calls) is too small for this read's: a larger one, the call once more
-        const uint64_t need = (uint64_t)small[6] + small[6] / 8 + 1024;
-        if (small[6] <= ctx->rep_pool_cap || need > 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ENOMEM, "repeat-hill pool beyond 2^32 entries");
+        const uint32_t need = grown_pool_size(small[kSensPoolCount], ctx->rep_pool_cap);
+        if (!need) return fail(ctx, RALA_HIP_ENOMEM, "repeat-hill pool beyond 2^32 entries");
         rala_hip::DevBuf<Interval> larger;
         HIPCHECK(larger.ensure(need));
         if (used_before) HIPCHECK(hipMemcpy(larger.p, ctx->d_rep_pool.p, (size_t)used_before * sizeof(Interval), hipMemcpyDeviceToDevice));
         std::swap(larger.p, ctx->d_rep_pool.p);
         std::swap(larger.n, ctx->d_rep_pool.n);
-        ctx->rep_pool_cap = (uint32_t)need;
+        ctx->rep_pool_cap = need;
         a.pool = ctx->d_rep_pool.p; a.pool_cap = ctx->rep_pool_cap;
-        const uint32_t reset[2] = {used_before, 0};
-        HIPCHECK(hipMemcpy(ctx->d_small.p + 6, reset, 8, hipMemcpyHostToDevice));
+        const uint32_t reset[kSensPoolWords] = {used_before, 0};                // (the pool's count as it was, no status)
+        HIPCHECK(hipMemcpy(ctx->d_small.p + kSensPoolCount, reset, sizeof(reset), hipMemcpyHostToDevice));
     }
-    if (small[7] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow (repeat hills)");
+    if (small[kSensStatus] & (kErrRegionCapacity | kErrRawCapacity)) return fail(ctx, RALA_HIP_EDEVICE, "slope-region list overflow (repeat hills)");
     ctx->h_n_rep.resize(n); ctx->h_rep_slot.resize(n);
     HIPCHECK(hipMemcpy(&ctx->h_n_rep[read], ctx->d_n_rep.p + read, 4, hipMemcpyDeviceToHost));
     HIPCHECK(hipMemcpy(&ctx->h_rep_slot[read], ctx->d_rep_slot.p + read, 4, hipMemcpyDeviceToHost));
-    ctx->h_rep_pool.resize(small[6]);
-    if (small[6]) HIPCHECK(hipMemcpy(ctx->h_rep_pool.data(), ctx->d_rep_pool.p, (size_t)small[6] * sizeof(Interval), hipMemcpyDeviceToHost));
-    ctx->n_rep_hills = small[6];
+    ctx->h_rep_pool.resize(small[kSensPoolCount]);
+    if (small[kSensPoolCount]) HIPCHECK(hipMemcpy(ctx->h_rep_pool.data(), ctx->d_rep_pool.p, (size_t)small[kSensPoolCount] * sizeof(Interval), hipMemcpyDeviceToHost));
+    ctx->n_rep_hills = small[kSensPoolCount];
     repeat_hills_fetched(ctx);
     repeat_hills_found(ctx);
     return RALA_HIP_OK;

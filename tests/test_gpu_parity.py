@@ -206,7 +206,7 @@ def test_containment_fixed_point_variants(hip_ctx_factory, n, g, seed, opts):
 
 @pytest.mark.parametrize("n,g,seed", [(3000, 600_000, 21), (2000, 1_200_000, 33), (600, 60_000, 9)])
 def test_host_tail_cross_check(hip_ctx_factory, n, g, seed):
-    """use_gpu_tail = 0: Graph::preprocess on the host (the path the sensitive pass uses)."""
+    """use_gpu_tail = 0: Graph::preprocess on the host (the cross-check of the device tail)."""
     ds = Dataset(n, g, seed)
     st = parity.oracle_stages(ds)
     ctx = hip_ctx_factory()
@@ -295,13 +295,23 @@ def test_sensitive_pass_with_pools_that_grow(hip_ctx_factory, gpu_tail, run_kern
 
 
 @pytest.mark.parametrize("gpu_tail", [1, 0])
+def test_sensitive_pass_with_lists_that_double(hip_ctx_factory, gpu_tail):
+    """every read of the position-space kernels takes the way of the lists in global memory (debug_force_big), which start at
+    four regions / four raw intervals (debug_big_caps): the repeat hills' second mode notes its reads and doubles the lists
+    until they fit - pile_unbounded_reads grows inside construct"""
+    _check_sensitive(hip_ctx_factory, Dataset(5000, 1_000_000, 7), gpu_tail, run_kernel=0, expect_hills=True,
+                     options={"debug_force_big": 1, "debug_big_caps": (4 << 32) | 4}, lists_must_double=True)
+
+
+@pytest.mark.parametrize("gpu_tail", [1, 0])
 def test_sensitive_overlaps_in_device_memory(hip_ctx_factory, gpu_tail):
     """option sensitive_in_device_memory: the sensitive set handed to rala_hip_construct as device pointers (what
     bench.py's c3s / c5s workloads do: resident in HBM like the primary set)"""
     _check_sensitive(hip_ctx_factory, Dataset(5000, 1_000_000, 7), gpu_tail, 1, expect_hills=True, in_device=True)
 
 
-def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in_device=False, small_pools=False, options=None):
+def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in_device=False, small_pools=False, options=None,
+                     lists_must_double=False):
     from oracle.oracle import Oracle
 
     n = ds.n_reads
@@ -331,6 +341,7 @@ def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in
     ctx.set_reads(ds.read_len)
     ctx.set_overlaps(ds.overlaps)
     ctx.initialize()
+    unbounded_before = ctx.timings()["pile_unbounded_reads"]
     if in_device:
         from rala_amd import hip
         ctx.set_option("sensitive_in_device_memory", 1)
@@ -342,6 +353,8 @@ def _check_sensitive(hip_ctx_factory, ds, gpu_tail, run_kernel, expect_hills, in
         ctx.construct(sens)
     if small_pools:
         assert len(want_rep[1]) > 16 and ctx.timings()["pool_regrown"] >= 1, (len(want_rep[1]), ctx.timings())
+    if lists_must_double:
+        assert ctx.timings()["pile_unbounded_reads"] > unbounded_before, (unbounded_before, ctx.timings())
     offs, pairs, flags = ctx.intervals(2)
     parity.assert_same("rep.offsets", offs, want_rep[0])
     parity.assert_same("rep.pairs", pairs, want_rep[1])
