@@ -43,8 +43,9 @@ def oracle_stages(ds, n_threads=8, ref=False, with_tr=True, n_data=64, data_of=(
 _crafted = {}
 
 
-def crafted_stages(case, n_threads=8):
-    """The oracle on a case of tests/compcase.py: the first pass, then every read's crafted row in place of its pile, and the
+def crafted_stages(case, n_threads=8, row_of=None):
+    """The oracle on a case of tests/compcase.py or tests/containcase.py (rows: row_of(case, r), else the case's own row_of, else
+    compcase's): the first pass, then every read's crafted row in place of its pile, and the
     per-pile annotation of Graph::initialize (graph.cpp:387-403) on it: find_valid_region - which leaves a live read's region
     [0, length) as it is, no value of its row is below 4, and takes the pile of a read that is to be dead, whose row is all zero -
     find_median, find_chimeric_hills, find_chimeric_pits.  Then the snapshot rala_hip_import_state takes, then the stages of
@@ -52,10 +53,11 @@ def crafted_stages(case, n_threads=8):
     import compcase
     if case.name in _crafted:
         return _crafted[case.name]
+    row_of = row_of or getattr(case, "row_of", None) or compcase.row_of
     o = Oracle(case.read_len, case.overlaps, n_threads=n_threads)
     o.pass1()
     for r in range(case.n_reads):
-        o.set_pile_state(r, compcase.row_of(case, r), 0, int(case.read_len[r]))
+        o.set_pile_state(r, row_of(case, r), 0, int(case.read_len[r]))
     st = {"init_rc": o.annotate()}    # (the oracle itself, with every row, is let go when this returns)
     assert st["init_rc"] == 0
     st["valid"] = o.valid()
@@ -63,6 +65,7 @@ def crafted_stages(case, n_threads=8):
     st["pits0"] = o.all_intervals(0)
     st["hills0"] = o.all_intervals(1)
     o.pass2()
+    st["alive_pass2"] = o.piles()["alive"]
     st["ov_pass2"] = o.overlap_list(0)
     st["int_pass2"] = o.overlap_list(1)
     o.preprocess_chimeras()
