@@ -341,7 +341,7 @@ struct rala_hip_ctx {
 
     // bound CSR
     rala_hip::DevBuf<uint32_t> d_ev_off, d_cursor, d_ev, d_slot_rank[2], d_ev_fixed;
-    uint32_t pile_chunk_mb = 1024;      // the rows' buffer as physical chunks of this size (0: one hipMalloc) - pipeline.hip
+    uint32_t pile_chunk_mb = 1024;      // the rows' buffer as physical chunks of this size (0: one hipMalloc) - initialize.hip
     // Rows on demand (option pile_rows = 0; pile_rows_kernel.hip): initialize allocates no rows and its kernels store none; a row
     // is rebuilt from the read's events - which stay where initialize left them - into d_rows_scratch when somebody asks
     uint32_t pile_rows = 1;             // the option (read by the next rala_hip_initialize)

@@ -1,7 +1,7 @@
 // librala_hip: the front of the C ABI (include/rala_hip.h) - a context made and destroyed, its options, its inputs (reads;
 // overlaps, or bounds as tuples, records or a sharded run's blocks), per-read state installed from outside and handed out.
 // Host code around copies: no kernel of the hot path is launched here.  What these calls mean for the context's life is in
-// lifecycle.h; the stages and the getters are in pipeline.hip.
+// lifecycle.h; the stages are in initialize.hip, construct.hip, sensitive.hip and transitive.hip, the getters in getters.hip.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>

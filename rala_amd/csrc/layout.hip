@@ -1,5 +1,5 @@
 // rala_hip_layout_batch: the force-directed layout of all components of a round in one call (reference rvaser/rala
-// src/graph.cpp:1132-1226, once per component of the loop at :1106).  rala_hip_layout (pipeline.hip) costs four copies, one
+// src/graph.cpp:1132-1226, once per component of the loop at :1106).  rala_hip_layout (at the end of this file) costs four copies, one
 // launch per step, two copies and a wait PER COMPONENT; a graph with repeats, low-coverage breaks and plasmids has hundreds
 // of small components per round and five rounds.  Here: one packed upload, one launch per size class for the components a
 // workgroup can hold (layout_fused_kernel), one launch per step for all larger ones together (layout_batch_step_kernel),
@@ -140,5 +140,33 @@ int rala_hip_layout_batch(rala_hip_ctx* ctx, uint32_t n_components, const uint32
 int rala_hip_get_layout_info(rala_hip_ctx* ctx, rala_hip_layout_info* out) {
     if (!ctx || !out) return RALA_HIP_EINVAL;
     *out = ctx->layout_info;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_layout(rala_hip_ctx* ctx, uint32_t n, double* x, double* y, const uint32_t* adj_off, const uint32_t* adj,
+                    uint32_t iterations, double k, double t, double dt) {
+    if (!ctx || (n && (!x || !y || !adj_off))) return RALA_HIP_EINVAL;
+    if (n == 0) return RALA_HIP_OK;
+    const uint32_t n_adj = adj_off[n];
+    if (n_adj && !adj) return RALA_HIP_EINVAL;
+    HIPCHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (int b = 0; b < 4; ++b) HIPCHECK(ctx->d_layout[b].ensure(n));
+    HIPCHECK(ctx->d_layout_adj[0].ensure(n + 1)); HIPCHECK(ctx->d_layout_adj[1].ensure(n_adj + 1));
+    HIPCHECK(hipMemcpyAsync(ctx->d_layout[0].p, x, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_layout[1].p, y, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_layout_adj[0].p, adj_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
+    if (n_adj) HIPCHECK(hipMemcpyAsync(ctx->d_layout_adj[1].p, adj, (size_t)n_adj * 4, hipMemcpyHostToDevice, s));
+    int cur = 0;
+    for (uint32_t it = 0; it < iterations; ++it) {
+        launch_layout_step(n, ctx->d_layout[2 * cur].p, ctx->d_layout[2 * cur + 1].p, ctx->d_layout[2 * (cur ^ 1)].p,
+                           ctx->d_layout[2 * (cur ^ 1) + 1].p, ctx->d_layout_adj[0].p, ctx->d_layout_adj[1].p, k, t, s);
+        cur ^= 1;
+        t -= dt;
+    }
+    HIPCHECK(hipMemcpyAsync(x, ctx->d_layout[2 * cur].p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(y, ctx->d_layout[2 * cur + 1].p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(stream_sync(ctx, s));
+    HIPCHECK(hipGetLastError());
     return RALA_HIP_OK;
 }

@@ -20,7 +20,7 @@
 //       few piles whose regions actually interact, reading coverage through a
 //       run cursor
 // Every read starts in the instantiation that fits its length class and its event
-// count (pipeline.hip: both are known before the first kernel runs); what still
+// count (initialize.hip: both are known before the first kernel runs); what still
 // does not fit - region lists, event caps - is appended to an overflow list for the
 // next kernel in the chain (larger kCap, then the position-space kernel of
 // pile_kernels.hip); the chain needs no host synchronisation.
@@ -655,7 +655,7 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
     // instantiation), plain otherwise.  History: with the reads as launched `nt` was 18 % slower (round 5: the L2 was what put
     // neighbouring rows' lines together); on top of the XCD ranges it was 3 % faster where one hipMalloc had put the rows well
     // and 4 % slower where it had not (3.70 against 3.82, 4.26 against 4.11) - not a default; with the rows in chunks of 1 GB
-    // (pipeline.hip), where the placement is the good one every time: **3.51 - 3.57 ms against 3.71 - 3.80** in eight processes on
+    // (initialize.hip), where the placement is the good one every time: **3.51 - 3.57 ms against 3.71 - 3.80** in eight processes on
     // three boxes, C5 15.2 against 16.2 - the default there.
     constexpr int kRowStoreMod = (int)((kVar >> 16) & 3u);
     constexpr bool kSingleItem = kOne && kWaves > 1 && !(kVar & 1u);
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
             given_e = A.end[r];
         }
         // the first kernel of the first pass: longer reads start in their own length class's kernel
-        // (pipeline.hip), no hand-over through the list
+        // (initialize.hip), no hand-over through the list
         if constexpr (kPlain) {
             // (one test over everything that was loaded: a branch on the length alone would have the offsets' loads wait
             // behind it)

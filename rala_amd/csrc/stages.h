@@ -1,4 +1,4 @@
-// Stage functions of librala_hip shared by the single-GPU entry points (pipeline.hip) and the
+// Stage functions of librala_hip shared by the single-GPU entry points (the stage files; what only those share: orchestration.h) and the
 // sharded runner (sharded.hip).  A non-null Comm makes a stage collective: every rank of the
 // group calls it with its own slice of the overlaps and the same per-read state.
 #pragma once
@@ -78,6 +78,6 @@ int pile_row_to_host(rala_hip_ctx* cl, uint64_t read, uint16_t* data);
 hipError_t stream_sync(rala_hip_ctx* ctx, hipStream_t s);
 hipError_t d2h_small(rala_hip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 int flush_upload(rala_hip_ctx* ctx);       // (context.hip) RALA_HIP_MEM_HOST_ASYNC columns not uploaded yet: now
-int download_read_state(rala_hip_ctx* ctx);     // (pipeline.hip) the per-read state into the host's vectors
+int download_read_state(rala_hip_ctx* ctx);     // (getters.hip) the per-read state into the host's vectors
 
 }  // namespace rala_hip

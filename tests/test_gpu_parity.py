@@ -73,6 +73,50 @@ def test_bucketing_variants(hip_ctx_factory, n, g, seed):
         parity.check_initialize(ctx, st, ds)
 
 
+def _bound_events(ds):
+    """events per read as the bucketing counts them: every overlap whose two names resolve puts a begin and an end on each
+    of its reads"""
+    ov, n = ds.overlaps, ds.n_reads
+    ok = (ov.a_id < n) & (ov.b_id < n)
+    return 2 * np.bincount(ov.a_id[ok], minlength=n) + 2 * np.bincount(ov.b_id[ok], minlength=n)
+
+
+def test_fixed_slot_overflow_runs_again_on_the_exact_path(hip_ctx_factory):
+    """A read with more bound events than a fixed slot holds (2048) on the fixed-slot path: rala_hip_initialize notices with
+    its one look and runs once more through the exact CSR.  The smallest generated set of this family with such a read (one,
+    2120 events: the assertion below guards that thin margin); every stage against the oracle, then a second call on the
+    same context, then a set without such a read.  Parity cannot tell the exact path from the fixed slots, so this shows that
+    the retry and what follows it on the context compute the right thing - not which path the later calls took."""
+    ds = Dataset(520, 8_000, 5)
+    ev = _bound_events(ds)
+    assert (ev > 2048).sum() >= 1 and ev.max() < 2200, (int((ev > 2048).sum()), int(ev.max()))
+    st = parity.oracle_stages(ds)
+    ctx = hip_ctx_factory()
+    ctx.set_option("use_partitioned_buckets", 0)
+    ctx.set_reads(ds.read_len)
+    ctx.set_overlaps(ds.overlaps)
+    ctx.initialize()
+    parity.check_initialize(ctx, st, ds)
+    ctx.construct()
+    parity.check_construct(ctx, st)
+    parity.check_tr(ctx, st)
+    ctx.initialize()
+    parity.check_initialize(ctx, st, ds)
+    ctx.construct()
+    parity.check_construct(ctx, st)
+    parity.check_tr(ctx, st)
+    small = Dataset(400, 20_000, 5)
+    assert _bound_events(small).max() <= 2048
+    st2 = parity.oracle_stages(small)
+    ctx.set_reads(small.read_len)
+    ctx.set_overlaps(small.overlaps)
+    ctx.initialize()
+    parity.check_initialize(ctx, st2, small)
+    ctx.construct()
+    parity.check_construct(ctx, st2)
+    parity.check_tr(ctx, st2)
+
+
 @pytest.mark.parametrize("shift", [12, 13, 14])
 @pytest.mark.parametrize("n,g,seed", [(40_000, 8_000_000, 13), (9000, 1_800_000, 4)])
 def test_first_level_partition_sizes(hip_ctx_factory, n, g, seed, shift):
