@@ -814,7 +814,7 @@ void launch_partition_rest(const PartitionBuffers& B, uint32_t n_reads, const ui
 }  // namespace
 
 bool bucket_count_can_dedupe(const OvlSoA& o, const uint8_t* valid) {
-    return (((uintptr_t)o.a_id | (uintptr_t)o.b_id) & 15u) == 0 && ((uintptr_t)valid & 3u) == 0 && getenv("RALA_DEDUPE_APART") == nullptr;
+    return (((uintptr_t)o.a_id | (uintptr_t)o.b_id) & 15u) == 0 && ((uintptr_t)valid & 3u) == 0;
 }
 
 // dedupe (may be null): the counting pass does duplicate removal's first pass on the way (group_count_dedupe_kernel) -
@@ -866,14 +866,12 @@ hipError_t launch_bucket_partitioned(const OvlSoA& o, uint32_t n_reads, const Bu
     hipLaunchKernelGGL(l1_scatter_kernel, dim3(tiles1), dim3(kBlockP), stage_lds_bytes(B.n_part), s, o, n_reads, B.n_part, B.shift, part_cursor, rec1,
                        acount);
     launch_partition_rest(B, n_reads, acount, rec1, rec2, ev_off, ev, s, ev_shift);
-    // (overlaps per thread: two - 1.27 against 1.31 ms for the stage at C3 in two of three alternations, four: the same as one;
-    // RALA_QUERY_PER for the measurement)
+    // (overlaps per thread: two - 1.27 against 1.31 ms for the stage at C3 in two of three alternations, four: the same as one)
+    constexpr uint32_t kQueryPer = 2;
     e = wait_for(dedupe ? dedupe->a_coords : nullptr);
     if (e != hipSuccess) return e;
-    static const int q_per = getenv("RALA_QUERY_PER") ? atoi(getenv("RALA_QUERY_PER")) : 2;
-    if (q_per == 4) hipLaunchKernelGGL(query_side_kernel<4>, dim3((uint32_t)((o.n + 1023) / 1024)), dim3(256), 0, s, o, n_reads, (const uint32_t*)ev_off, written, ev, ev_shift);
-    else if (q_per == 2) hipLaunchKernelGGL(query_side_kernel<2>, dim3((uint32_t)((o.n + 511) / 512)), dim3(256), 0, s, o, n_reads, (const uint32_t*)ev_off, written, ev, ev_shift);
-    else hipLaunchKernelGGL(query_side_kernel<1>, dim3((uint32_t)((o.n + 255) / 256)), dim3(256), 0, s, o, n_reads, (const uint32_t*)ev_off, written, ev, ev_shift);
+    hipLaunchKernelGGL(query_side_kernel<kQueryPer>, dim3((uint32_t)((o.n + 256 * kQueryPer - 1) / (256 * kQueryPer))), dim3(256), 0, s, o, n_reads,
+                       (const uint32_t*)ev_off, written, ev, ev_shift);
     return hipGetLastError();
 }
 

@@ -180,7 +180,7 @@ int pass2(rala_hip_ctx* ctx, Comm* comm) {
             undecided = 0xFFFFFFFFu - st;                        // the largest list of any rank
         }
         list_size.push_back(undecided);
-        if (getenv("RALA_HIP_TRACE")) fprintf(stderr, "[trace] containment round %d: %u undecided\n", (int)list_size.size(), undecided);
+        if (trace_on()) fprintf(stderr, "[trace] containment round %d: %u undecided\n", (int)list_size.size(), undecided);
         if (undecided == 0) break;
         if (list_size.size() > 100000) return fail(ctx, RALA_HIP_EDEVICE, "containment fixed point did not converge");
         if (!gathered) HIPCHECK(hipMemcpyAsync(up, sure, dbytes, hipMemcpyDeviceToDevice, s));

@@ -64,10 +64,9 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
-    // chunk_bytes per physical allocation; order 1: chunk i lies at slot (i * stride) mod n_chunks of the range (neighbours in
-    // the range are not neighbours in the order of allocation)
+    // chunk_bytes per physical allocation, mapped in the order of allocation
     // fail_at (tests, option debug_chunk_fail): the mapping fails at chunk fail_at (the caller falls back); negative: never
-    hipError_t ensure_chunked(size_t count, size_t chunk_bytes, int order, int device, int64_t fail_at = -1) {
+    hipError_t ensure_chunked(size_t count, size_t chunk_bytes, int device, int64_t fail_at = -1) {
         if (count <= n && p) return hipSuccess;
         release();
         hipMemAllocationProp prop = {};
@@ -87,12 +86,6 @@ struct DevBuf {
         p = (T*)base;
         reserved = bytes;
         chunk_size = chunk_bytes;
-        size_t stride = 1;
-        if (order == 1 && n_chunks > 2) {
-            stride = (size_t)((double)n_chunks * 0.6180339887) | 1u;
-            auto gcd = [](size_t a, size_t b) { while (b) { const size_t t = a % b; a = b; b = t; } return a; };
-            while (gcd(stride, n_chunks) != 1) stride += 2;
-        }
         for (size_t i = 0; i < n_chunks && e == hipSuccess; ++i) {
             hipMemGenericAllocationHandle_t h;
             if (fail_at >= 0 && (size_t)fail_at == i) { e = hipErrorOutOfMemory; break; }
@@ -100,7 +93,7 @@ struct DevBuf {
             if (e != hipSuccess) break;
             chunks.push_back(h);
             mapped.push_back(nullptr);
-            void* at = (char*)base + ((i * stride) % n_chunks) * chunk_bytes;
+            void* at = (char*)base + i * chunk_bytes;
             e = hipMemMap(at, chunk_bytes, 0, h, 0);
             if (e == hipSuccess) mapped.back() = at;
         }
@@ -200,7 +193,6 @@ struct rala_hip_ctx {
     std::unique_ptr<rala_hip::HostPool> pool;
     bool use_run_kernel = true;
     bool debug_fail_construct = false;          // tests: pass 2 fails on this context
-    uint32_t debug_pile_variant = 0;            // measurements: PileArgs::variant
     uint32_t debug_dedupe_list_cap = 0;         // tests: duplicate removal's mark list holds this many marks (0 = 2^20); more: the pass over all overlaps
     uint32_t debug_fp_lds_limit = 0xFFFFFFFFu;  // tests: containment fixed points with more killers than this take the long lists' kernel
     uint32_t debug_fp_give_up = 0;              // tests: the long lists' workgroups do not meet (FixedPointList::debug_give_up: 1 or 2)

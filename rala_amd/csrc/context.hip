@@ -132,7 +132,6 @@ int rala_hip_create(int device, rala_hip_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return RALA_HIP_EDEVICE;
     rala_hip_ctx* ctx = new rala_hip_ctx;
     ctx->device = device;
-    if (const char* mb = getenv("RALA_HIP_PILE_CHUNK_MB")) ctx->pile_chunk_mb = (uint32_t)std::max(0, atoi(mb));      // (measurements: the option's default)
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
@@ -206,7 +205,6 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "debug_ev_events")) { ctx->debug_ev_events = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_count_window")) { ctx->debug_count_window = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_part_shift")) { ctx->debug_part_shift = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
-    if (!strcmp(key, "debug_pile_variant")) { ctx->debug_pile_variant = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_dedupe_list_cap")) { ctx->debug_dedupe_list_cap = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_fp_lds_limit")) { ctx->debug_fp_lds_limit = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "debug_fp_give_up")) { ctx->debug_fp_give_up = value == 2 ? 2u : value != 0 ? 1u : 0u; return RALA_HIP_OK; }
@@ -265,12 +263,8 @@ int rala_hip_set_reads(rala_hip_ctx* ctx, const uint32_t* read_len, uint64_t n_r
     // Rows start on 128-byte boundaries (64 elements): a row's first and last cache line are then its own, not shared
     // with the neighbouring rows, which other wavefronts write at other times.  Round 4, one box, pile kernel at C3:
     // 16-byte boundaries (rounds 1 - 3: what the 16-byte stores need) 4.26 ms, 128 bytes 4.17, 1 KB 4.18, 4 KB 4.21
-    // (docs/history/gpurun/r4_rowalign.sh; RALA_PILE_ROW_ALIGN=<elements, a power of two >= 8> for the experiment).
-    static const uint64_t row_align = [] {
-        uint64_t want = getenv("RALA_PILE_ROW_ALIGN") ? (uint64_t)atoll(getenv("RALA_PILE_ROW_ALIGN")) : 64ull, a = 8;
-        while (a * 2 <= want && a < (1ull << 20)) a *= 2;           // a power of two, 8 elements at least
-        return a;
-    }();
+    // (round 4, r4_rowalign.sh under docs/history).
+    constexpr uint64_t row_align = 64;
     uint64_t off = 0;
     for (uint64_t r = 0; r < n_reads; ++r) {
         ctx->h_pile_off[r] = off;

@@ -34,7 +34,7 @@ int tokenise_text(rala_hip_ctx* ctx, const uint8_t* text, uint64_t n, uint64_t n
     hipStream_t s = ctx->stream;
     const uint32_t chunk = paf_chunk_bytes();
     const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    const bool trace = getenv("RALA_HIP_TRACE") != nullptr;
+    const bool trace = trace_on();
     double tc = t1, tp0 = t1, tp1 = t1;
     uint32_t n_lines = 0;
     if (n_chunks) {
@@ -262,7 +262,7 @@ int rala_hip::overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_
     ctx->inflate_tm.inflate_ms = X.bg.inflate_ms;
     ctx->inflate_tm.compressed_bytes = X.bg.shipped;
     ctx->inflate_tm.members = X.bg.jobs.size();
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] device inflate: part %u of %u, bytes [%lu, %lu) of %lu: %lu BGZF members, %.3f GB compressed shipped (index and "
                 "ship %.1f ms), %.3f GB of text inflated in %.2f ms\n", part, parts, (unsigned long)P.begin, (unsigned long)P.end,
                 (unsigned long)F, (unsigned long)X.bg.jobs.size(), X.bg.shipped / 1e9, X.bg.ship_ms, X.bg.text_n / 1e9, X.bg.inflate_ms);
@@ -383,14 +383,14 @@ static int set_overlaps_from_text(rala_hip_ctx* ctx, const char* path, bool mhap
         ctx->inflate_tm.inflate_ms = bg.inflate_ms;
         ctx->inflate_tm.compressed_bytes = bg.shipped;
         ctx->inflate_tm.members = bg.jobs.size();
-        if (getenv("RALA_HIP_TRACE")) {
+        if (trace_on()) {
             fprintf(stderr, "[trace] device inflate: %lu BGZF members, %.3f GB compressed shipped (index and ship %.1f ms), %.3f GB of text "
                     "inflated in %.2f ms\n", (unsigned long)bg.jobs.size(), bg.shipped / 1e9, bg.ship_ms, bg.text_n / 1e9, bg.inflate_ms);
         }
     }
     if (X.kind == kTextGzip) {
         ctx->ingest_tm.ship_ms += X.gz.ship_ms;
-        if (getenv("RALA_HIP_TRACE")) trace_gzip(X.gz, 0, 0);
+        if (trace_on()) trace_gzip(X.gz, 0, 0);
     }
     release.now();              // (not held while rala_hip_set_overlaps makes its buffers)
     if (R.flags) {

@@ -9,7 +9,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <chrono>
 #include <functional>
 #include <string>
 #include <vector>
@@ -17,16 +16,13 @@
 #include "ctx_check.h"
 #include "ingest_formats.h"
 #include "kernels.h"
+#include "orchestration.h"      // now_ms, trace_on
 #include "stages.h"
 
 namespace rala_hip {
 namespace ingest {
 
 constexpr size_t kBlockBytes = 32u << 20;       // one staging block
-
-inline double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 struct Fd {                                         // (closed on every way out - ADVICE round 4)
     int fd = -1;

@@ -276,7 +276,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     if (S.gz) {
         ctx->gzip_tm = S.gz->tm;
         if (rc == RALA_HIP_OK && !S.flag && !gzip_walk_proven(*S.gz)) S.flag = 8;
-        if (getenv("RALA_HIP_TRACE")) trace_gzip(*S.gz, S.gz->windows, S.gz->window);
+        if (trace_on()) trace_gzip(*S.gz, S.gz->windows, S.gz->window);
         if (rc == RALA_HIP_OK && !S.flag) ctx->gzip_members_last = S.gz->members;
     }
     if (S.flag) flags = 8;
@@ -306,7 +306,7 @@ int rala_hip_index_sequences(rala_hip_ctx* ctx, const char* path, int format, ui
     ctx->seq_tm.tokenize_ms = (float)kernel_ms;
     ctx->seq_tm.bytes = R.text_n;
     ctx->seq_tm.lines = R.n_records;
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] device sequence index: %.2f GB of text shipped in %.1f ms, %lu records indexed in %.2f ms (flags %u)\n", R.text_n / 1e9,
                 ship_ms, (unsigned long)R.n_records, kernel_ms, flags);
     }
@@ -512,7 +512,7 @@ int rala_hip_slice_sequences(rala_hip_ctx* ctx, const char* path, const uint64_t
     ctx->slice_info.kernel_ms = (float)kernel_ms;
     ctx->slice_info.gather_ms = (float)gather_ms;
     ctx->slice_info.copy_ms = (float)copy_ms;
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] device sequence slice: %lu windows of at most %.3f GB of text, %lu bases of %lu reads, ship %.1f ms, device %.2f ms "
                 "(gather %.2f ms, bases to the host %.2f ms) (flags %u)\n", (unsigned long)S.windows, S.max_window / 1e9,
                 (unsigned long)ctx->slice_info.bases, (unsigned long)n_wanted, S.ship_ms, kernel_ms, gather_ms, copy_ms, S.flag | flags);

@@ -107,13 +107,11 @@ int plan_initialize(rala_hip_ctx* ctx, bool exact_buckets, InitPlan& plan) {
     // beside them costs them its whole stand-alone time (0.26 ms at C3: pile kernel 4.63 ms with it,
     // 4.37 without); the partitioned bucketing streams and has issue slots to spare - beside it the
     // duplicate removal costs 0.14 ms (round 4, docs/history/gpurun/r4_dedupe_early.sh: step 8.08 -> 7.99 ms).
-    // RALA_DEDUPE_LATE keeps it beside the pile kernels.
-    static const bool dedupe_late = getenv("RALA_DEDUPE_LATE") != nullptr;
     if (plan.input != Inputs::kOverlaps) {
         plan.dedupe = DedupeAt::kNone;
     } else if (!ctx->use_side_stream) {
         plan.dedupe = DedupeAt::kMainInFront;
-    } else if (plan.bucketing != Bucketing::kPartitionedOverlaps || dedupe_late) {
+    } else if (plan.bucketing != Bucketing::kPartitionedOverlaps) {
         plan.dedupe = DedupeAt::kSideBesidePiles;
     } else if (bucket_count_can_dedupe(ctx->ovl, ctx->d_valid.p)) {
         // (round 5) ... and inside the bucketing's counting pass where that pass can take it: both read the two id columns of every
@@ -140,13 +138,10 @@ int place_rows(rala_hip_ctx* ctx) {
     // 3.81) - its stores, a wavefront per row, 7 000 rows open at a time, are the only access pattern of the path that feels it.
     // hipMalloc's single block landed anywhere in that range; chunks of 1 GB mapped in order: 3.73 - 3.86 in 25 placements of 25,
     // the bench line 7.19 - 7.22 ms in five processes against 7.36 - 7.55 alternating with them.
-    // Option pile_chunk_mb (0 = one hipMalloc; RALA_HIP_PILE_CHUNK_ORDER=1, measurements: the chunks permuted).  Falls back
-    // to hipMalloc where the driver refuses the mapping calls.
-    static const char* chunk_order = getenv("RALA_HIP_PILE_CHUNK_ORDER");
+    // Option pile_chunk_mb (0 = one hipMalloc).  Falls back to hipMalloc where the driver refuses the mapping calls.
     hipError_t ec = hipErrorNotSupported;
     if (ctx->pile_chunk_mb > 0 && (ctx->pile_elems + 8) * sizeof(uint16_t) >= ((size_t)ctx->pile_chunk_mb << 20)) {
-        ec = ctx->d_pile.ensure_chunked(ctx->pile_elems + 8, (size_t)ctx->pile_chunk_mb << 20, chunk_order ? atoi(chunk_order) : 0, ctx->device,
-                                        ctx->debug_chunk_fail);
+        ec = ctx->d_pile.ensure_chunked(ctx->pile_elems + 8, (size_t)ctx->pile_chunk_mb << 20, ctx->device, ctx->debug_chunk_fail);
         if (ec != hipSuccess) (void)hipGetLastError();
     }
     if (ec != hipSuccess) HIPCHECK(ctx->d_pile.ensure(ctx->pile_elems + 8));
@@ -306,7 +301,6 @@ int first_pass_args(rala_hip_ctx* ctx, const InitPlan& plan, PileArgs& a) {
     a.rows_chunked = ctx->d_pile.reserved ? 1u : 0u;
     a.slab = ctx->d_slab.p;
     a.stop_after = (uint32_t)ctx->debug_pile_stop_after;
-    a.variant = ctx->debug_pile_variant;
     a.alive = ctx->d_alive.p; a.n_pits = ctx->d_n_pits.p; a.n_hills = ctx->d_n_hills.p; a.iv_slot = ctx->d_iv_slot.p;
     a.pool = ctx->d_pool.p; a.pool_count = ctx->d_small.p + kInitPoolCount; a.pool_cap = ctx->pool_cap;
     a.error = ctx->d_small.p + kInitStatus;
@@ -350,10 +344,8 @@ int run_pile_chain(rala_hip_ctx* ctx, PileArgs& a) {
     const uint32_t* by_class = n_short != n_reads ? ctx->d_class_order.p : nullptr;
     // few longer reads: the first kernel goes over all reads without the indirection (2 % at C3)
     // and leaves at once for a longer one
-    static const bool force_order = getenv("RALA_PILE_FORCE_ORDER") != nullptr;
-    const bool short_by_list = by_class && (force_order || (uint64_t)(n_reads - n_short) * 8 > n_reads);
-    static const bool no_aux = getenv("RALA_PILE_NO_AUX") != nullptr;       // measurements: everything on one stream
-    hipStream_t aux = ctx->use_side_stream && !no_aux ? ctx->aux : s;
+    const bool short_by_list = by_class && (uint64_t)(n_reads - n_short) * 8 > n_reads;
+    hipStream_t aux = ctx->use_side_stream ? ctx->aux : s;
     if (aux != s) HIPCHECK(hipStreamWaitEvent(aux, ctx->ev[kEvInitBucketed], 0));
     a.lw = 0;
     a.skip_dense = 1;
@@ -361,28 +353,26 @@ int run_pile_chain(rala_hip_ctx* ctx, PileArgs& a) {
     a.order = list_dense;
     a.n_items = n_reads;
     a.n_items_dev = cnt_dense;
-    launch_pile_runs(a, std::min<uint32_t>(n_reads, 8192), 1, list2, cnt2, aux);
+    launch_pile_runs(a, std::min<uint32_t>(n_reads, 8192), PileTier::kCap1024, list2, cnt2, aux);
     a.n_items_dev = nullptr;
     a.order = by_class ? by_class + n_short : nullptr;
     a.n_items = n_medium;
-    // (measurements: RALA_PILE_ANYLEN_FROM=1 sends this class to the any-length kernel, too)
-    static const int anylen_from = getenv("RALA_PILE_ANYLEN_FROM") ? atoi(getenv("RALA_PILE_ANYLEN_FROM")) : 3;
-    launch_pile_runs(a, std::min<uint32_t>(n_medium, 16384), anylen_from <= 1 ? 4 : 3, list1, cnt1, aux);
+    launch_pile_runs(a, std::min<uint32_t>(n_medium, 16384), PileTier::kUpTo32k, list1, cnt1, aux);
     a.order = by_class ? by_class + n_short + n_medium : nullptr;
     a.n_items = n_long;
-    launch_pile_runs(a, std::min<uint32_t>(n_long, 20480), 4, list1, cnt1, aux);
+    launch_pile_runs(a, std::min<uint32_t>(n_long, 20480), PileTier::kAnyLength, list1, cnt1, aux);
     if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[kEvPileAuxDone], aux));
     a.order = short_by_list ? by_class : nullptr;
     a.n_items = short_by_list ? n_short : n_reads;
-    launch_pile_runs(a, a.n_items, 0, list1, cnt1, s);
+    launch_pile_runs(a, a.n_items, PileTier::kCap512First, list1, cnt1, s);
     if (aux != s) HIPCHECK(hipStreamWaitEvent(s, ctx->ev[kEvPileAuxDone], 0));
     a.n_items = n_reads;
     a.order = list1;
     a.n_items_dev = cnt1;
-    launch_pile_runs(a, std::min<uint32_t>(n_reads, 8192), 1, list2, cnt2, s);
+    launch_pile_runs(a, std::min<uint32_t>(n_reads, 8192), PileTier::kCap1024, list2, cnt2, s);
     a.order = list2;
     a.n_items_dev = cnt2;
-    launch_pile_runs(a, std::min<uint32_t>(n_reads, 2048), 2, list3, cnt3, s);
+    launch_pile_runs(a, std::min<uint32_t>(n_reads, 2048), PileTier::kCap2048, list3, cnt3, s);
     a.order = list3;
     a.n_items_dev = cnt3;
     const uint32_t max_len = ctx->max_read_len;
@@ -442,11 +432,11 @@ int settle(rala_hip_ctx* ctx, const InitPlan& plan, const uint32_t (&small)[kSma
     }
     const uint32_t n_dead = small[kInitDeadReads];
     ctx->tm.pile_overflow_reads = ctx->use_run_kernel ? small[kInitDenseReads] + small[kInitToCap1024] : 0;      // event-dense + handed on
-    if (getenv("RALA_HIP_TRACE") || getenv("RALA_HIP_TRACE_BUFFERS")) {
+    if (trace_on() || getenv("RALA_HIP_TRACE_BUFFERS")) {
         fprintf(stderr, "[trace] buffers: events %p (CSR %p) slots %p counts %p piles %p a_id %p b_id %p b_begin %p\n", (void*)ctx->d_ev.p, (void*)ctx->d_ev_off.p, (void*)ctx->d_ev_fixed.p,
                 (void*)ctx->d_cursor.p, (void*)ctx->d_pile.p, (const void*)ctx->ovl.a_id, (const void*)ctx->ovl.b_id,
                 (const void*)ctx->ovl.b_begin);
-        if (getenv("RALA_HIP_TRACE")) fprintf(stderr, "[trace] pile chain: %u reads listed as event-dense, %u handed on by the cap-512 kernels, %u on to cap 2048, %u to position space\n",
+        if (trace_on()) fprintf(stderr, "[trace] pile chain: %u reads listed as event-dense, %u handed on by the cap-512 kernels, %u on to cap 2048, %u to position space\n",
                 small[kInitDenseReads], small[kInitToCap1024], small[kInitToCap2048], small[kInitToPosition]);
     }
     ctx->tm.pile_position_reads = ctx->use_run_kernel ? small[kInitToPosition] : n_reads;

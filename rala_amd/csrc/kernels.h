@@ -79,7 +79,6 @@ struct PileArgs {
     // first pass: reads with more than kRunEventCap events are listed beforehand
     // (launch_pile_dense_list) and start in the cap-1024 kernel; the cap-512 kernels pass them over
     uint32_t skip_dense = 0;
-    uint32_t variant = 0;          // measurements (a library built with -DRALA_PILE_AB): which variant of the first kernel runs
 };
 
 uint32_t pile_lds_bytes(uint32_t lw);
@@ -118,8 +117,8 @@ void launch_pile_row_digests(const uint16_t* pile, const uint64_t* pile_off, con
 // run-space kernel (pile_runs_kernel.hip): one wavefront per read; reads with more bound
 // events than the instantiation's cap (or, with args.skip_dense, only those whose region lists do
 // not fit) are appended to overflow_list instead (args.order may be null = identity).  Event caps
-// 512 / 1024 / 2048 (tiers 0, 1, 2): the larger ones keep longer lists in LDS and run at lower
-// occupancy; cap 512 comes in three layouts by read length (tiers 0 / 3 / 4, below).
+// 512 / 1024 / 2048: the larger ones keep longer lists in LDS and run at lower occupancy; cap 512
+// comes in three layouts by read length (PileTier, below).
 constexpr uint32_t kRunEventCap = 512;
 constexpr uint32_t kRunEventCapMid = 1024;
 constexpr uint32_t kRunEventCapBig = 2048;
@@ -128,14 +127,21 @@ constexpr uint32_t kRunEventCapBig = 2048;
 // half wavefronts per SIMD, was 3 % faster than that kernel on 50 kb reads - not kept.)
 constexpr uint32_t kPileClasses = 3;
 constexpr uint32_t kPileClassBases[kPileClasses - 1] = {16384u, 32768u};
-// tier 0: cap 512 (one workgroup per read where the grid allows: reads of up to 16384 bases only),
-// 3: cap 512 for reads of up to 32768 bases, 4: cap 512 for any length, 1: cap 1024, 2: cap 2048
+// Which kernel of the chain a launch asks for (the launch table at the end of pile_runs_kernel.hip).
+enum class PileTier {
+    kCap512First,   // cap 512; one workgroup per read where the grid covers the items (the first kernel of a chain: reads of up
+                    // to 16384 bases only), otherwise the looped kernel of kAnyLength
+    kCap1024,       // cap 1024
+    kCap2048,       // cap 2048
+    kUpTo32k,       // cap 512 for reads of up to 32768 bases
+    kAnyLength,     // cap 512 for reads of any length
+};
 void launch_pile_dense_list(const PileArgs& args, uint32_t n_reads, uint32_t* list, uint32_t* count, hipStream_t stream);
-void launch_pile_runs(const PileArgs& args, uint32_t grid, int tier, uint32_t* overflow_list, uint32_t* overflow_count,
+void launch_pile_runs(const PileArgs& args, uint32_t grid, PileTier tier, uint32_t* overflow_list, uint32_t* overflow_count,
                       hipStream_t stream);
-// the sensitive pass in run space (tier 0: cap 512, tier 1: cap 1024; reads of up to 16384 bases); the others are appended to
+// the sensitive pass in run space (reads of up to 32768 bases); the others are appended to
 // overflow_list for the position-space kernel below
-void launch_pile_sens(const PileArgs& args, uint32_t grid, int tier, int mode, uint32_t* overflow_list,
+void launch_pile_sens(const PileArgs& args, uint32_t grid, PileTier tier, int mode, uint32_t* overflow_list,
                       uint32_t* overflow_count, hipStream_t stream);
 
 // sensitive pass (pile_repeats_kernel.hip): mode 1 = add layers on top + median for the

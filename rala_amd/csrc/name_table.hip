@@ -59,7 +59,7 @@ int rala_hip_build_name_table(rala_hip_ctx* ctx, uint64_t* n_buckets, uint64_t* 
     ctx->n_name_buckets = cap;
     ctx->n_name_arena_bytes = bytes;
     ctx->name_table_info = info;
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] device name table: %lu names, %lu distinct, in %lu buckets in %.3f ms (longest probe path %u slots)\n",
                 (unsigned long)n, (unsigned long)info.distinct, (unsigned long)cap, info.device_ms, info.longest_probe);
     }

@@ -23,10 +23,13 @@ inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// RALA_HIP_TRACE: read at every call - a process may set it late
+inline bool trace_on() { return getenv("RALA_HIP_TRACE") != nullptr; }
+
 struct Trace {
     bool on;
     double t;
-    Trace() : on(getenv("RALA_HIP_TRACE") != nullptr), t(now_ms()) {}
+    Trace() : on(trace_on()), t(now_ms()) {}
     void operator()(const char* what, size_t k = 0) {
         if (!on) return;
         const double u = now_ms();
@@ -124,7 +127,7 @@ int run_until_lists_fit(rala_hip_ctx* ctx, uint32_t count, uint32_t* count_dev, 
         HIPCHECK(hipMemcpyAsync(&status, status_dev, 4, hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
         HIPCHECK(hipGetLastError());
-        if (getenv("RALA_HIP_TRACE")) {
+        if (trace_on()) {
             fprintf(stderr, "[trace] %slists in global memory: %u reads at %u regions / %u raw intervals, %u left (status %u)\n", what, count,
                     cap_reg, cap_raw, left, status);
         }

@@ -803,7 +803,7 @@ __global__ __launch_bounds__(kBlock) void survivor_masks_kernel(OvlSoA o, uint32
                                                                 const uint4* __restrict__ rec, Interval* pool,
                                                                 uint64_t* __restrict__ mask_ov, uint64_t* __restrict__ mask_in,
                                                                 uint32_t* __restrict__ chunk_ov,
-                                                                uint32_t* __restrict__ chunk_in, uint32_t probe) {
+                                                                uint32_t* __restrict__ chunk_in) {
     constexpr uint32_t kPer = kClassifyChunk / kBlock, kWaves = kBlock / 64;
     __shared__ uint32_t s_ov, s_in;
     __shared__ uint16_t s_list[kWaves][kPer * 64];
@@ -834,13 +834,13 @@ __global__ __launch_bounds__(kBlock) void survivor_masks_kernel(OvlSoA o, uint32
 #pragma unroll
     for (uint32_t u = 0; u < kPer; ++u) {
         const uint32_t ra = a[u] < n_reads ? a[u] : 0u;
-        fa[u] = probe & 2u ? a[u] & 3u : fate[ra];
+        fa[u] = fate[ra];
         const uint64_t i = (uint64_t)blockIdx.x * kClassifyChunk + u * kBlock + threadIdx.x;
         ok[u] = ok[u] && death[ra] >= (uint32_t)(o.base + i) + 1u;
     }
 #pragma unroll
     for (uint32_t u = 0; u < kPer; ++u) {
-        fb[u] = !ok[u] ? 0u : probe & 2u ? b[u] & 3u : fate[b[u] < n_reads ? b[u] : 0u];
+        fb[u] = !ok[u] ? 0u : fate[b[u] < n_reads ? b[u] : 0u];
     }
     uint32_t cnt = 0;           // candidates of this wavefront (the same in every lane)
 #pragma unroll
@@ -853,7 +853,6 @@ __global__ __launch_bounds__(kBlock) void survivor_masks_kernel(OvlSoA o, uint32
         cnt += (uint32_t)__popcll(m);
     }
     wave_lds_sync();
-    if (probe & 1u) cnt = 0;
     for (uint32_t k = lane; k < cnt; k += 64) {
         const uint32_t e = s_list[wave][k];
         const uint32_t u = e >> 6, l = e & 63u;
@@ -1151,8 +1150,7 @@ void launch_classify(const OvlSoA& o, uint32_t n_reads, const uint8_t* valid, co
     // (16-byte loads want the columns on 16-byte boundaries: a sharded run's slice may start anywhere in them)
     const uintptr_t bits = (uintptr_t)o.a_id | (uintptr_t)o.b_id | (uintptr_t)o.a_begin | (uintptr_t)o.a_end | (uintptr_t)o.b_begin |
                            (uintptr_t)o.b_end | (uintptr_t)o.strand * 4 | (uintptr_t)valid * 4;
-    static const bool no_vec = getenv("RALA_CLASSIFY_NO_VEC") != nullptr;       // (measurements)
-    const bool vec = (bits & 15u) == 0 && !no_vec;
+    const bool vec = (bits & 15u) == 0;
     if (small_records) {
         if (vec) hipLaunchKernelGGL((classify_kernel<true, true>), grid, dim3(kBlock), 0, s, o, n_reads, valid, (const uint32_t*)crec, kl, lo);
         else hipLaunchKernelGGL((classify_kernel<true, false>), grid, dim3(kBlock), 0, s, o, n_reads, valid, (const uint32_t*)crec, kl, lo);
@@ -1188,12 +1186,11 @@ void launch_survivor_masks(const OvlSoA& o, uint32_t n_reads, const uint8_t* val
     if (!o.n) return;
     const dim3 grid(pass2_chunks(o.n));
     if (small_records) {
-        static const uint32_t probe = getenv("RALA_MASKS_PROBE") ? (uint32_t)atoi(getenv("RALA_MASKS_PROBE")) : 0u;   // measurements only
         hipLaunchKernelGGL(survivor_masks_kernel<true>, grid, dim3(kBlock), 0, s, o, n_reads, valid, fate, death, (const uint32_t*)crec, rec, pool,
-                           mask_ov, mask_in, chunk_ov, chunk_in, probe);
+                           mask_ov, mask_in, chunk_ov, chunk_in);
     } else {
         hipLaunchKernelGGL(survivor_masks_kernel<false>, grid, dim3(kBlock), 0, s, o, n_reads, valid, fate, death, (const uint2*)crec, rec, pool,
-                           mask_ov, mask_in, chunk_ov, chunk_in, 0u);
+                           mask_ov, mask_in, chunk_ov, chunk_in);
     }
 }
 void launch_death_status(const uint32_t* count, uint32_t* status, hipStream_t s) {

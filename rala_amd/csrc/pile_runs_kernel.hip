@@ -28,6 +28,7 @@
 // Reference behaviour followed: rvaser/rala src/pile.cpp:64-455.
 #include <hip/hip_runtime.h>
 
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -382,33 +383,25 @@ __device__ __forceinline__ uint32_t ffbl_or_minus1(uint32_t v) {
 // compiler prefers a 64-bit address per lane: two more registers per store in flight, and at this
 // kernel's register budget that meant spill reloads inside the store loop - a scratch load is a
 // vector memory operation, and the wait for it is a wait for every row store issued so far.
-// (RALA_ROW_STORE_MOD: cache-policy bits of the row stores, for measurements - "sc1", "sc0 sc1", "nt"; round 5)
-#ifndef RALA_ROW_STORE_MOD
-#define RALA_ROW_STORE_MOD ""
-#endif
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// (kMod, measurements inside one process - bits 16 - 17 of a kernel variant: 1 non-temporal, 2 sc1, 3 sc0 sc1)
-template <int kMod = 0>
+// kNonTemporal: the stores' cache policy, `nt` or none.  (Measured with the rows in one hipMalloc and not kept there: 1 % at C3 and
+// 3 % more write traffic at the memory; for the bucketing's scattered 8-byte stores, which need the cache to merge them, it cost
+// 40 %.  Kept where the rows lie in mapped chunks: the kernel's comment below.  sc1 and sc0 sc1, and the reads of the expansion
+// zero-extended: docs/history/experiments/r20_pile_ab_variants.patch.)
+// (s_nop: a store of more than 8 bytes reads its data registers over the following cycles; the
+// compiler's hazard recogniser keeps vector writes to them away from its own stores, not from this one)
+template <bool kNonTemporal>
 __device__ __forceinline__ void store16(const char* base, uint32_t off, const uint4& v) {
     const u32x4 d = {v.x, v.y, v.z, v.w};
-    if constexpr (kMod == 1) { asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory"); return; }
-    if constexpr (kMod == 2) { asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory"); return; }
-    if constexpr (kMod == 3) { asm volatile("global_store_dwordx4 %0, %1, %2 sc0 sc1\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory"); return; }
-    // (Measured and not kept: the `nt` modifier - streaming stores gave 1 % at C3 inside one gpurun call and 3 %
-    // more write traffic at the memory; for the bucketing's scattered 8-byte stores, which need the cache to
-    // merge them, it cost 40 %.)
-    // (s_nop: a store of more than 8 bytes reads its data registers over the following cycles; the
-    // compiler's hazard recogniser keeps vector writes to them away from its own stores, not from this one)
-    asm volatile("global_store_dwordx4 %0, %1, %2 " RALA_ROW_STORE_MOD "\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory");
+    if constexpr (kNonTemporal) asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, %2 \n\ts_nop 1" : : "v"(off), "v"(d), "s"(base) : "memory");
 }
 // (the same with an immediate offset: the lane offset is then a loop constant)
-template <int kImm, int kMod = 0>
+template <int kImm, bool kNonTemporal>
 __device__ __forceinline__ void store16_imm(const char* base, uint32_t off, const uint4& v) {
     const u32x4 d = {v.x, v.y, v.z, v.w};
-    if constexpr (kMod == 1) { asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory"); return; }
-    if constexpr (kMod == 2) { asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory"); return; }
-    if constexpr (kMod == 3) { asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc0 sc1\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory"); return; }
-    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 " RALA_ROW_STORE_MOD "\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory");
+    if constexpr (kNonTemporal) asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 \n\ts_nop 1" : : "v"(off), "v"(d), "s"(base), "n"(kImm) : "memory");
 }
 
 // kShort: the first kernel of the chain takes only reads of up to 16384 bases (the others go to the
@@ -492,7 +485,7 @@ struct Layout {
 // stored exactly once.  (Before: every changed group went through the list, a walk and a table of
 // finished groups, once per chunk of 256 groups - 700 of the expansion's 900 vector instructions
 // per read.)
-template <class L, int kMod = 0>
+template <class L, bool kNonTemporal>
 __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t* rv, uint16_t* pile, uint64_t row_off,
                                                    uint32_t nv, uint32_t lane, bool store) {
     const uint32_t* bm = sm + L::X;
@@ -536,7 +529,7 @@ __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t*
                 w2 = bitfield_insert(change_mask(x, 2), f, w2);
                 w3 = bitfield_insert(change_mask(x, 3), f, w3);
             } while (inner);
-            if (store) store16<kMod>(base, g * 16u, make_uint4(w0, w1, w2, w3));
+            if (store) store16<kNonTemporal>(base, g * 16u, make_uint4(w0, w1, w2, w3));
         }
         wave_sync();
         cnt = 0;
@@ -563,11 +556,7 @@ __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t*
             // its alignment is not one access.)
             // (the byte selectors below take bytes 0, 1 of each only: no extension of the 16-bit LDS reads - the compiler puts a
             // v_and behind a zero-extending one)
-#ifdef RALA_EXPAND_EXTEND           // (measurements: the reads zero-extended, as before)
-            const uint32_t v0 = rvm1[k], v1 = rvm1[k + 1];
-#else
             const uint32_t v0 = low_half_only(rvm1[k]), v1 = low_half_only(rvm1[k + 1]);
-#endif
             const uint32_t b7 = (bits[u] >> sh1) & 0x7Fu;                      // run starts at positions 1 .. 7
             const uint32_t gl = 64u * u + lane;
             const bool in = kFull || g0 + gl < nv;
@@ -588,10 +577,10 @@ __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t*
                 cnt += more;
             }
             if (in && !multi && store) {
-                if (u == 0) store16_imm<0, kMod>(base, voff, out);
-                else if (u == 1) store16_imm<1024, kMod>(base, voff, out);
-                else if (u == 2) store16_imm<2048, kMod>(base, voff, out);
-                else store16_imm<3072, kMod>(base, voff, out);
+                if (u == 0) store16_imm<0, kNonTemporal>(base, voff, out);
+                else if (u == 1) store16_imm<1024, kNonTemporal>(base, voff, out);
+                else if (u == 2) store16_imm<2048, kNonTemporal>(base, voff, out);
+                else store16_imm<3072, kNonTemporal>(base, voff, out);
             }
         }
     };
@@ -628,39 +617,39 @@ __device__ __forceinline__ void expand_from_bitmap(uint32_t* sm, const uint16_t*
 // its own stretch of LDS and synchronises with itself only; what they have in common is their place: the rows of
 // neighbouring reads are written from one compute unit (tools/fill_bench4.hip: four rows per workgroup fill at 5.4 TB/s
 // where one row per workgroup fills at 5.0).
-// kVar: measurement variants of the product instantiation, chosen per launch (PileArgs::variant, option "debug_pile_variant") so
-// that two builds of the kernel are compared INSIDE one process, on the same allocations, step by step - a library built with
-// -DRALA_PILE_AB carries them (round 6: two processes with the same binary differed by 12 % in this kernel's time, two binaries in
-// alternating processes by less).  What is kept are the variants behind profiles/r06_c3_pile_sensitivity.txt: bit 0 the loop over the
-// items as it was, bit 1 the events by ordinary loads, bit 2 the arguments fetched where they are first used (8195 = bits 0, 1, 13 =
-// round 5's kernel); bits 8 - 10 work ADDED behind the expansion, for the sensitivity of the kernel's time to each kind of it - 1: 128
-// independent vector instructions, 2: 128 scalar ones, 3: 1024 cycles asleep, 4: 32 LDS reads and their wait, 5: 512 vector
-// instructions; bit 13 the reads as launched instead of XCD ranges; bits 16 - 17 the row stores' cache policy (1 nt, 2 sc1, 3 sc0 sc1).
-// The others round 6 measured - s_nop pads, sleeps and work in front of the first load, one / four reads per workgroup, priorities,
-// non-temporal event loads, the XCC_ID probe, the expansion's look-ups one group ahead, XCDs taking chunks in turn - are a patch:
-// docs/history/experiments/r6_pile_kernel_variants.patch (their results: docs/history/r6_pile_kernel_notebook.md).
+// kNtRows (with kPlain): the row stores are non-temporal.
+// (Round 6 compared variants of the product instantiation INSIDE one process, on the same allocations, step by step - two processes
+// with the same binary differed by 12 % in this kernel's time.  What it found is in the constants below; the machinery - a variant
+// word, padding work behind the expansion, the option that picked a variant per launch - and every variant that lost are patches:
+// docs/history/experiments/r20_pile_ab_variants.patch and r6_pile_kernel_variants.patch, their results in
+// docs/history/r6_pile_kernel_notebook.md and profiles/r06_c3_pile_sensitivity.txt.)
 // kRows = false (option pile_rows = 0, PileArgs::pile null): no row is stored - the expansion is left out at compile time, the
-// annotations are the same (rows on demand: pile_rows_kernel.hip).  The default is the kernel as it was.
-template <uint32_t kCap, bool kDiag, int kSens, bool kOne = false, uint32_t kBases = 16384, uint32_t kWaves = 1, bool kPlain = false, uint32_t kVar = 0,
-          bool kRows = true>
-__global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases > 16384 ? 4 : 5) void pile_runs_kernel(PileArgs A, uint32_t* overflow_list, uint32_t* overflow_count) {
+// annotations are the same (rows on demand: pile_rows_kernel.hip).
+//
+// K: one row of the launch table at the end of this file (PileKernel), which names these parameters.
+template <class K>
+__global__ __launch_bounds__(64 * K::kWaves, K::kOne ? 7 : K::kBases > 32768 ? 2 : K::kBases > 16384 ? 4 : 5) void pile_runs_kernel(PileArgs A, uint32_t* overflow_list, uint32_t* overflow_count) {
+    constexpr uint32_t kCap = K::kCap, kBases = K::kBases, kWaves = K::kWaves;
+    constexpr int kSens = K::kSens;
+    constexpr bool kDiag = K::kDiag, kOne = K::kOne, kPlain = K::kPlain, kRows = K::kRows;
     static_assert(kWaves == 1 || kOne, "several reads per workgroup: the first kernel of a chain only");
     static_assert(kSens == 0 || !kDiag, "the sensitive pass has no diagnostic instantiation");
     static_assert(!kOne || kCap <= 512, "the short layout belongs to the first kernel of a chain");
     static_assert(kBases == 16384 || !kOne, "the bigger bitmap belongs to the chain's second kernel");
+    static_assert(kPlain || !K::kNtRows, "non-temporal row stores: the product instantiation only");
     // (round 5: the sensitive pass's cap-1024 kernels too - their reads have at most 16384 bases; 14 296 -> 9 840 B of LDS, sixteen
     // workgroups per compute unit instead of eleven, and at C5 this is the kernel nearly every target starts in)
-    constexpr bool kXcdRanges = kOne && kPlain && !(kVar & 8192u);
-    // The rows' stores (kVar bits 16 - 17): NON-TEMPORAL where the rows lie in mapped chunks (the launch below picks the
-    // instantiation), plain otherwise.  History: with the reads as launched `nt` was 18 % slower (round 5: the L2 was what put
-    // neighbouring rows' lines together); on top of the XCD ranges it was 3 % faster where one hipMalloc had put the rows well
-    // and 4 % slower where it had not (3.70 against 3.82, 4.26 against 4.11) - not a default; with the rows in chunks of 1 GB
-    // (initialize.hip), where the placement is the good one every time: **3.51 - 3.57 ms against 3.71 - 3.80** in eight processes on
-    // three boxes, C5 15.2 against 16.2 - the default there.
-    constexpr int kRowStoreMod = (int)((kVar >> 16) & 3u);
-    constexpr bool kSingleItem = kOne && kWaves > 1 && !(kVar & 1u);
-    constexpr bool kSingleItemArgs = kSingleItem && !(kVar & 4u);
-    constexpr bool kBufferEvents = kSens == 0 && !(kVar & 2u);
+    // kXcdRanges: every XCD writes one contiguous range of the rows (below).  kSingleItem: one item per wavefront, said so that the
+    // compiler sees no loop; kSingleItemArgs: the arguments fetched in one go (below).  kBufferEvents: the first pass loads its events
+    // through a buffer descriptor (phase 1).  Each measured against its opposite in round 6 and kept.
+    constexpr bool kXcdRanges = kOne && kPlain;
+    // K::kNtRows - the rows' stores are NON-TEMPORAL where the rows lie in mapped chunks (PileArgs::rows_chunked picks the
+    // instantiation), plain otherwise: with the rows in chunks of 1 GB (initialize.hip) **3.51 - 3.57 ms against 3.71 - 3.80** in
+    // eight processes on three boxes, C5 15.2 against 16.2; where one hipMalloc holds the rows it won or lost with the placement
+    // (3.70 against 3.82, 4.26 against 4.11) - not a default there (docs/history/r6_pile_kernel_notebook.md).
+    constexpr bool kSingleItem = kOne && kWaves > 1;
+    constexpr bool kSingleItemArgs = kSingleItem;
+    constexpr bool kBufferEvents = kSens == 0;
     constexpr bool kShort = kOne || kBases > 16384 || (kSens != 0 && kCap == 1024);     // reads of up to kBases bases only, 16-bit run starts
     constexpr uint32_t kMaxBases = kBases > 65535 ? 65535 : kBases;     // rs[R] = n in 16 bits
     typedef Layout<kCap, kShort, kBases> L;
@@ -708,10 +697,9 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
     // The product instantiation (round 6): every XCD writes ONE contiguous range of the rows - workgroup i runs on XCD i % 8 and takes
     // the reads (i % 8) * per + kWaves * (i / 8) + wavefront, per = the reads of an XCD (a multiple of kWaves), 8 * per / kWaves
     // workgroups.  A kernel that only fills the same rows goes from 5.2 to 6.2 TB/s that way (tools/fill_bench3.hip); this kernel, whose
-    // floor IS that fill rate (4.065 ms = 5.13 TB/s whatever is added to or taken from its instructions - tools/gpurun/r6_ab_inproc.sh),
+    // floor IS that fill rate (4.065 ms = 5.13 TB/s whatever is added to or taken from its instructions - r6_ab_inproc.sh under docs/history),
     // from 4.07 - 4.3 ms to 3.8 - 3.9 at C3, measured variant against variant inside one process.  Round 4 had
     // tried the mapping with one read per workgroup on a build that sat above that floor for other reasons and saw nothing.
-    // (kVar bit 13: the reads as launched - workgroup i takes 2 i and 2 i + 1 - for measurements.)
     if constexpr (kXcdRanges) {
         const uint32_t per = ((n_items + 8u * kWaves - 1u) / (8u * kWaves)) * kWaves, xcd = blockIdx.x & 7u, j = (blockIdx.x >> 3) * kWaves + wave_in_group;
         item_first = xcd * per + j;
@@ -806,7 +794,6 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
             // all loads first, unconditionally (clamped index), so that they are in flight together:
             // a load per predicated block would be waited for one by one
             uint32_t evr[kCap / 64];
-            const uint32_t e_last = n_ev ? n_ev - 1 : 0;
             if constexpr (kBufferEvents) {
                 // (round 6) the events through a buffer descriptor over exactly this read's slots: one lane offset and eight
                 // immediate ones instead of a clamped index and a 64-bit address per load, and nothing to mark behind the last
@@ -816,13 +803,6 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
                 const int lane4 = (int)(lane * 4u);
 #pragma unroll
                 for (uint32_t t = 0; t < kCap / 64; ++t) evr[t] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(slots, lane4 + (int)(t * 256u), 0, 0);
-            } else if constexpr (kSens == 0) {
-#pragma unroll
-                for (uint32_t t = 0; t < kCap / 64; ++t) evr[t] = rev[umin(t * 64 + lane, e_last)];
-#pragma unroll
-                for (uint32_t t = 0; t < kCap / 64; ++t) {
-                    if (t * 64 + lane >= n_ev) evr[t] = kNone;
-                }
             } else {
                 // the primary events, then the bounds of the sensitive overlaps
 #pragma unroll
@@ -1112,7 +1092,7 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
                 // one more bit for the padding behind the last base: run R, value 0
                 if (lane == 0 && n < kBases) atomicOr(&bm[n >> 5], 1u << (n & 31));
                 wave_sync();
-                expand_from_bitmap<L, kRowStoreMod>(sm, rv, A.pile, row_off, nv, lane, row_stores);
+                expand_from_bitmap<L, K::kNtRows>(sm, rv, A.pile, row_off, nv, lane, row_stores);
                 if (kShort) index_from_bitmap();
             } else
             for (uint32_t s0 = 0; s0 < nv * 8; s0 += kSeg) {       // sorted path: long reads, many events
@@ -1187,27 +1167,6 @@ __global__ __launch_bounds__(64 * kWaves, kOne ? 7 : kBases > 32768 ? 2 : kBases
             }
         }
         wave_sync();
-        if constexpr (((kVar >> 8) & 7u) != 0) {
-            constexpr uint32_t kKind = (kVar >> 8) & 7u;
-            uint32_t x0 = lane, x1 = lane + 1, x2 = lane + 2, x3 = lane + 3;
-            if constexpr (kKind == 1 || kKind == 5) {
-                asm volatile(".rept %4\n\tv_add_u32 %0, 1, %0\n\tv_add_u32 %1, 1, %1\n\tv_add_u32 %2, 1, %2\n\tv_add_u32 %3, 1, %3\n\t.endr"
-                             : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "n"(kKind == 1 ? 32 : 128));
-            } else if constexpr (kKind == 2) {
-                uint32_t s0 = n, s1 = R, s2 = n_ev, s3 = r;
-                asm volatile(".rept 32\n\ts_add_u32 %0, %0, 1\n\ts_add_u32 %1, %1, 1\n\ts_add_u32 %2, %2, 1\n\ts_add_u32 %3, %3, 1\n\t.endr"
-                             : "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3) : : "scc");
-                x0 += s0 + s1 + s2 + s3;
-            } else if constexpr (kKind == 3) {
-                asm volatile("s_sleep 16" : : : "memory");
-            } else if constexpr (kKind == 4) {
-                uint32_t acc = 0;
-                for (uint32_t t = 0; t < 32; ++t) acc += ((volatile uint32_t*)sm)[(lane + 64u * t) & 511u];
-                x0 += acc;
-            }
-            // (the results must be wanted: a store that never happens)
-            if (x0 + x1 + x2 + x3 == 0x12345u && n == 0xFFFFFFFFu) A.begin[r] = x0;
-        }
 
         RUN_STOP(31)
 
@@ -1870,142 +1829,174 @@ void launch_pile_dense_list(const PileArgs& args, uint32_t n_reads, uint32_t* li
                        n_reads, list, count);
 }
 
+// ---- the launch table: every instantiation of pile_runs_kernel the library contains, and the one function that picks from it ----
+//
 // (An EIGHTH wavefront per SIMD, round 4, timing only - the 384-event instantiation at 5 056 B and 64 registers over the
 // 99.7 % of the C3 reads it can take, the 512-event kernel over the same reads: 4.37 - 4.6 ms against 4.04 - 4.09,
 // docs/history/gpurun/r4_probe8.sh.  Seven is the kernel's optimum, not a limit worth lifting.)
 // Reads per workgroup in the first kernel (one wavefront each).  Rounds 2 - 3: one (two and four measured no gain: 4.80 /
 // 4.83 against 4.74 ms).  Round 4, once the rows start on cache-line boundaries and nothing else runs beside the kernel: two
 // 4.07 - 4.10 ms, one 4.16, four 4.23 (docs/history/gpurun/r4_waves2.sh) - two.
+// (Persistent wavefronts, each looping over a
+// share of the items - 6144 of them, what the chip holds at once, take 6.5 ms where a million short-lived ones take 4.8; 12288:
+// 5.4 ms: a wavefront that goes on to its next item waits for that item's first loads alone, a fresh workgroup's start overlaps
+// with the others' work.  The instantiations for one and four reads per workgroup and the switches that reached them:
+// docs/history/experiments/r20_pile_ab_variants.patch.)
 constexpr uint32_t kPileWavesPerGroup = 2;
 
-// the chain without rows (PileArgs::pile null): the same tiers with kRows = false
-static void launch_pile_runs_rowless(const PileArgs& args, uint32_t grid, int tier, uint32_t* overflow_list, uint32_t* overflow_count,
-                                     hipStream_t stream) {
-#define RALA_LAUNCH_ROWLESS(grid_, block_, ...)                                                                          \
-    hipLaunchKernelGGL((pile_runs_kernel<__VA_ARGS__, false>), dim3(grid_), dim3(block_), 0, stream, args, overflow_list, overflow_count)
-    if (tier == 0 && grid >= args.n_items && !args.n_items_dev) {
-        // (one workgroup per item; the product's shape - two reads per workgroup, XCD ranges - where the product takes it)
-        if (!args.order && !args.ev_cnt) RALA_LAUNCH_ROWLESS(8u * ((args.n_items + 15u) / 16u), 128, kRunEventCap, false, 0, true, 16384, 2, true, 0);
-        else RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, true, 16384, 1, false, 0);
-    } else if (tier == 3) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, false, 32768, 1, false, 0);
-    else if (tier == 0 || tier == 4) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCap, false, 0, false, 16384, 1, false, 0);
-    else if (tier == 1) RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCapMid, false, 0, false, 16384, 1, false, 0);
-    else RALA_LAUNCH_ROWLESS(grid, 64, kRunEventCapBig, false, 0, false, 16384, 1, false, 0);
-#undef RALA_LAUNCH_ROWLESS
-}
+// The shapes of the kernel that exist.
+enum class PileShape {
+    kLooped,        // a grid of any size loops over the items (which may be counted on the device); reads of any length
+    kLooped32k,     // the same over the short layout with the bitmap for reads of up to 32768 bases
+    kOnePerGroup,   // first kernel of a chain, one workgroup per item: one read per workgroup, no loop, short layout
+    kTwoByList,     // first kernel, kPileWavesPerGroup reads per workgroup as launched, the reads through args.order or fixed slots
+    kProduct,       // first kernel, kPileWavesPerGroup reads per workgroup in XCD ranges, the reads as they come, their events in the CSR
+    kProductNt,     // the same with non-temporal row stores
+};
+enum class PilePass { kPrimary = 0, kSensMedians = 1, kSensHills = 2 };     // (the kernel's kSens)
+enum class PileRows { kStored, kNone };
+enum class PileDiag { kOff, kOn };
 
-void launch_pile_runs(const PileArgs& args, uint32_t grid, int tier, uint32_t* overflow_list, uint32_t* overflow_count,
-                      hipStream_t stream) {
-    if (grid == 0) return;
+template <uint32_t kCap_, PileShape kShape_, PilePass kPass_, PileRows kRows_, PileDiag kDiag_>
+struct PileKernel {
+    static constexpr uint32_t kCap = kCap_;
+    static constexpr PileShape kShape = kShape_;
+    static constexpr PilePass kPass = kPass_;
+    static constexpr PileRows kRowsAre = kRows_;
+    static constexpr PileDiag kDiagIs = kDiag_;
+    // what the kernel reads
+    static constexpr int kSens = (int)kPass_;
+    static constexpr bool kDiag = kDiag_ == PileDiag::kOn;
+    static constexpr bool kRows = kRows_ == PileRows::kStored;
+    static constexpr bool kOne = kShape_ != PileShape::kLooped && kShape_ != PileShape::kLooped32k;
+    static constexpr uint32_t kBases = kShape_ == PileShape::kLooped32k ? 32768 : 16384;
+    static constexpr bool kPlain = kShape_ == PileShape::kProduct || kShape_ == PileShape::kProductNt;
+    static constexpr uint32_t kWaves = kPlain || kShape_ == PileShape::kTwoByList ? kPileWavesPerGroup : 1;
+    static constexpr bool kNtRows = kShape_ == PileShape::kProductNt;
+};
+
+template <class... Ks>
+struct PileKernelList {};
+
+// Asymmetries, kept as they are:
+//   * only the primary pass with rows has diagnostic kernels, and its diagnostic first kernel is the one-per-group shape;
+//   * without rows a first kernel that is given a read order or fixed slots takes one read per workgroup, with rows two;
+//   * the sensitive passes have no product shape (their first kernel takes one read per workgroup) and no diagnostics;
+//   * the repeat hills (kSensHills) neither read nor write a row: one set of kernels, whatever args.pile is.
+typedef PileKernelList<
+    //         events           shape                     pass                    rows              diagnostics
+    // the primary pass's first kernel
+    PileKernel<kRunEventCap,    PileShape::kProduct,      PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kProductNt,    PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kTwoByList,    PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kOnePerGroup,  PilePass::kPrimary,     PileRows::kStored, PileDiag::kOn>,
+    PileKernel<kRunEventCap,    PileShape::kProduct,      PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kOnePerGroup,  PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    // the primary pass's looped kernels (PileTier::kCap512First with a grid smaller than the items and kAnyLength: the same kernel)
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kPrimary,     PileRows::kStored, PileDiag::kOn>,
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOn>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOn>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kStored, PileDiag::kOn>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kPrimary,     PileRows::kNone,   PileDiag::kOff>,
+    // the sensitive pass's medians, with and without rows
+    PileKernel<kRunEventCap,    PileShape::kOnePerGroup,  PilePass::kSensMedians, PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kSensMedians, PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kSensMedians, PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kSensMedians, PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kSensMedians, PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kOnePerGroup,  PilePass::kSensMedians, PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kSensMedians, PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kSensMedians, PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kSensMedians, PileRows::kNone,   PileDiag::kOff>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kSensMedians, PileRows::kNone,   PileDiag::kOff>,
+    // the sensitive pass's repeat hills
+    PileKernel<kRunEventCap,    PileShape::kOnePerGroup,  PilePass::kSensHills,   PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped32k,    PilePass::kSensHills,   PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCap,    PileShape::kLooped,       PilePass::kSensHills,   PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapMid, PileShape::kLooped,       PilePass::kSensHills,   PileRows::kStored, PileDiag::kOff>,
+    PileKernel<kRunEventCapBig, PileShape::kLooped,       PilePass::kSensHills,   PileRows::kStored, PileDiag::kOff>>
+    PileKernels;
+
+// a row of the table, chosen at run time
+struct PileChoice {
+    uint32_t cap;
+    PileShape shape;
+    PilePass pass;
+    PileRows rows;
+    PileDiag diag;
+};
+
+// Which kernel a launch gets.  One workgroup per item (the first-kernel shapes) only where the grid covers the items and their
+// number is known on the host; otherwise the tier names a looped kernel.
+static PileChoice pick_pile_kernel(const PileArgs& args, uint32_t grid, PileTier tier, PilePass pass) {
+    const bool primary = pass == PilePass::kPrimary;
+    PileChoice c;
+    c.pass = pass;
+    c.rows = args.pile || pass == PilePass::kSensHills ? PileRows::kStored : PileRows::kNone;
     // (without rows there is no diagnostic run: rala_hip_initialize refuses debug_pile_stop_after != 99 with pile_rows = 0)
-    if (!args.pile) { launch_pile_runs_rowless(args, grid, tier, overflow_list, overflow_count, stream); return; }
-    // diagnostics: extra dynamic LDS lowers the occupancy (sensitivity experiments)
-    static const uint32_t extra_lds = getenv("RALA_PILE_EXTRA_LDS") ? (uint32_t)atoi(getenv("RALA_PILE_EXTRA_LDS")) : 0u;
-    const bool diag = args.stop_after != 99;
-#define RALA_LAUNCH_RUNS(cap, lds)                                                                                      \
-    do {                                                                                                                \
-        if (diag) hipLaunchKernelGGL((pile_runs_kernel<cap, true, 0>), dim3(grid), dim3(64), lds, stream, args,         \
-                                     overflow_list, overflow_count);                                                    \
-        else hipLaunchKernelGGL((pile_runs_kernel<cap, false, 0>), dim3(grid), dim3(64), lds, stream, args,             \
-                                overflow_list, overflow_count);                                                         \
-    } while (0)
-    if (tier == 0 && grid >= args.n_items && !args.n_items_dev) {
-        // the first kernel of the chain: one workgroup per item.  (Measured and not kept, RALA_PILE_PERSIST=<grid>:
-        // persistent wavefronts, each looping over a share of the items - 6144 of them, what the chip holds at
-        // once, take 6.5 ms where a million short-lived ones take 4.8; 12288: 5.4 ms.  A wavefront that goes on
-        // to its next item waits for that item's first loads alone; a fresh workgroup's start overlaps with the
-        // others' work.  The SQ counters' 74 % slot occupancy is not the dispatcher's doing.)
-        static const uint32_t persist = getenv("RALA_PILE_PERSIST") ? (uint32_t)atoi(getenv("RALA_PILE_PERSIST")) : 0u;
-        const uint32_t g = persist && persist < grid ? persist / 8u * 8u : grid;
-        // reads per workgroup (one wavefront each): RALA_PILE_WAVES = 1, 2 or 4
-        static const uint32_t waves = getenv("RALA_PILE_WAVES") ? (uint32_t)atoi(getenv("RALA_PILE_WAVES")) : kPileWavesPerGroup;
-        if (diag) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, true, 0, true>), dim3(g), dim3(64), extra_lds, stream,
-                                     args, overflow_list, overflow_count);
-        else if (waves == 4 && !persist) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 0, true, 16384, 4>), dim3((grid + 3) / 4), dim3(256),
-                                                            extra_lds, stream, args, overflow_list, overflow_count);
-        else if (waves == 2 && !persist && !args.order && !args.ev_cnt && !getenv("RALA_PILE_NOT_PLAIN")) {
-#define RALA_LAUNCH_PRODUCT(var)                                                                                                  \
-            hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 0, true, 16384, 2, true, var>),                            \
-                               dim3(((var) & 8192u) ? (grid + 1) / 2 : 8u * ((args.n_items + 15u) / 16u)), dim3(128),            \
-                               extra_lds, stream, args, overflow_list, overflow_count)
-            // the product's choice: non-temporal row stores (65536) where the rows lie in mapped chunks, plain ones (0) where one
-            // hipMalloc holds them; debug_pile_variant = 262144 asks for the plain stores whatever holds the rows
-            constexpr uint32_t kNt = 65536u, kForcePlain = 262144u;
-            uint32_t variant = args.variant == 0 && args.rows_chunked ? kNt : args.variant == kForcePlain ? 0u : args.variant;
-#ifdef RALA_PILE_AB
-#ifndef RALA_PILE_AB_CASES          // (-DRALA_PILE_AB_CASES="X(8) X(11)": the variants a measurement build carries beside 0 and 65536)
-#define RALA_PILE_AB_CASES X(1) X(2) X(3) X(4)
-#endif
-            switch (variant) {
-#define X(v) case v: RALA_LAUNCH_PRODUCT(v); break;
-                RALA_PILE_AB_CASES
-#undef X
-                case kNt: RALA_LAUNCH_PRODUCT(65536); break;
-                default: RALA_LAUNCH_PRODUCT(0); break;
-            }
-#else
-            if (variant == kNt) RALA_LAUNCH_PRODUCT(65536);
-            else RALA_LAUNCH_PRODUCT(0);
-#endif
-#undef RALA_LAUNCH_PRODUCT
+    c.diag = primary && args.pile && args.stop_after != 99 ? PileDiag::kOn : PileDiag::kOff;
+    c.cap = kRunEventCap;
+    if (tier == PileTier::kCap512First && grid >= args.n_items && !args.n_items_dev) {
+        c.shape = PileShape::kOnePerGroup;
+        if (primary && c.diag == PileDiag::kOff) {
+            // non-temporal row stores where the rows lie in mapped chunks, plain ones where one hipMalloc holds them
+            if (!args.order && !args.ev_cnt) c.shape = args.pile && args.rows_chunked ? PileShape::kProductNt : PileShape::kProduct;
+            else if (args.pile) c.shape = PileShape::kTwoByList;
         }
-        else if (waves == 2 && !persist) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 0, true, 16384, 2>), dim3((grid + 1) / 2), dim3(128),
-                                                            extra_lds, stream, args, overflow_list, overflow_count);
-        else hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 0, true>), dim3(g), dim3(64), extra_lds, stream,
-                                args, overflow_list, overflow_count);
-    } else if (tier == 3) {
-        // reads of 16385 .. 32768 bases: the short layout with a bitmap twice the size
-        if (diag) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, true, 0, false, 32768>), dim3(grid), dim3(64), 0, stream,
-                                     args, overflow_list, overflow_count);
-        else hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 0, false, 32768>), dim3(grid), dim3(64), 0, stream,
-                                args, overflow_list, overflow_count);
-    } else if (tier == 0 || tier == 4) RALA_LAUNCH_RUNS(kRunEventCap, extra_lds);
-    else if (tier == 1) RALA_LAUNCH_RUNS(kRunEventCapMid, 0);
-    else RALA_LAUNCH_RUNS(kRunEventCapBig, 0);
-#undef RALA_LAUNCH_RUNS
+        return c;
+    }
+    switch (tier) {
+        case PileTier::kUpTo32k: c.shape = PileShape::kLooped32k; break;
+        case PileTier::kCap512First: c.shape = PileShape::kLooped; break;
+        // (the sensitive pass is never asked for this tier; what it always answered to anything but the tiers it knows is cap 1024)
+        case PileTier::kAnyLength: c.shape = PileShape::kLooped; c.cap = primary ? kRunEventCap : kRunEventCapMid; break;
+        case PileTier::kCap1024: c.shape = PileShape::kLooped; c.cap = kRunEventCapMid; break;
+        case PileTier::kCap2048: c.shape = PileShape::kLooped; c.cap = kRunEventCapBig; break;
+    }
+    return c;
 }
 
-void launch_pile_sens(const PileArgs& args, uint32_t grid, int tier, int mode, uint32_t* overflow_list,
-                      uint32_t* overflow_count, hipStream_t stream) {
+template <class K>
+static bool launch_if_chosen(const PileChoice& c, const PileArgs& args, uint32_t grid, uint32_t* overflow_list, uint32_t* overflow_count,
+                             hipStream_t stream) {
+    if (c.cap != K::kCap || c.shape != K::kShape || c.pass != K::kPass || c.rows != K::kRowsAre || c.diag != K::kDiagIs) return false;
+    // XCD ranges: 8 * per / kWaves workgroups, per = the reads of an XCD rounded up to kWaves; as launched: kWaves items per workgroup
+    const uint32_t groups = K::kPlain ? 8u * ((args.n_items + 8u * K::kWaves - 1u) / (8u * K::kWaves)) : (grid + K::kWaves - 1u) / K::kWaves;
+    hipLaunchKernelGGL(pile_runs_kernel<K>, dim3(groups), dim3(64 * K::kWaves), 0, stream, args, overflow_list, overflow_count);
+    return true;
+}
+
+template <class... Ks>
+static bool launch_from(PileKernelList<Ks...>, const PileChoice& c, const PileArgs& args, uint32_t grid, uint32_t* overflow_list,
+                        uint32_t* overflow_count, hipStream_t stream) {
+    return (launch_if_chosen<Ks>(c, args, grid, overflow_list, overflow_count, stream) || ...);
+}
+
+static void launch_pile_kernel(const PileArgs& args, uint32_t grid, PileTier tier, PilePass pass, uint32_t* overflow_list,
+                               uint32_t* overflow_count, hipStream_t stream) {
     if (grid == 0) return;
-    if (mode == 1 && !args.pile) {
-        // without rows (option pile_rows = 0): medians as ever, the expansion to HBM left out (mode 2 never touches a row)
-#define RALA_LAUNCH_SENS_ROWLESS(...)                                                                                   \
-    hipLaunchKernelGGL((pile_runs_kernel<__VA_ARGS__, false>), dim3(grid), dim3(64), 0, stream, args, overflow_list, overflow_count)
-        if (tier == 0 && grid >= args.n_items && !args.n_items_dev) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, true, 16384, 1, false, 0);
-        else if (tier == 3) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, false, 32768, 1, false, 0);
-        else if (tier == 0) RALA_LAUNCH_SENS_ROWLESS(kRunEventCap, false, 1, false, 16384, 1, false, 0);
-        else if (tier == 2) RALA_LAUNCH_SENS_ROWLESS(kRunEventCapBig, false, 1, false, 16384, 1, false, 0);
-        else RALA_LAUNCH_SENS_ROWLESS(kRunEventCapMid, false, 1, false, 16384, 1, false, 0);
-#undef RALA_LAUNCH_SENS_ROWLESS
-        return;
+    if (!launch_from(PileKernels(), pick_pile_kernel(args, grid, tier, pass), args, grid, overflow_list, overflow_count, stream)) {
+        fprintf(stderr, "rala_hip: no pile kernel for this launch (a choice outside the launch table)\n");
+        abort();
     }
-#define RALA_LAUNCH_SENS(cap, m)                                                                                        \
-    hipLaunchKernelGGL((pile_runs_kernel<cap, false, m>), dim3(grid), dim3(64), 0, stream, args, overflow_list,         \
-                       overflow_count)
-    if (tier == 0 && grid >= args.n_items && !args.n_items_dev) {
-        // one workgroup per read: no loop, short layout (the sensitive pass takes reads of up to 16384 bases anyway)
-        if (mode == 1) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 1, true>), dim3(grid), dim3(64), 0, stream, args,
-                                          overflow_list, overflow_count);
-        else hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 2, true>), dim3(grid), dim3(64), 0, stream, args,
-                                overflow_list, overflow_count);
-    } else if (tier == 3) {
-        // reads of up to 32768 bases: the short layout with the bigger bitmap, as in the first pass
-        if (mode == 1) hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 1, false, 32768>), dim3(grid), dim3(64), 0, stream,
-                                          args, overflow_list, overflow_count);
-        else hipLaunchKernelGGL((pile_runs_kernel<kRunEventCap, false, 2, false, 32768>), dim3(grid), dim3(64), 0, stream, args,
-                                overflow_list, overflow_count);
-    } else if (tier == 0) {
-        if (mode == 1) RALA_LAUNCH_SENS(kRunEventCap, 1);
-        else RALA_LAUNCH_SENS(kRunEventCap, 2);
-    } else if (tier == 2) {
-        if (mode == 1) RALA_LAUNCH_SENS(kRunEventCapBig, 1);
-        else RALA_LAUNCH_SENS(kRunEventCapBig, 2);
-    } else {
-        if (mode == 1) RALA_LAUNCH_SENS(kRunEventCapMid, 1);
-        else RALA_LAUNCH_SENS(kRunEventCapMid, 2);
-    }
-#undef RALA_LAUNCH_SENS
+}
+
+void launch_pile_runs(const PileArgs& args, uint32_t grid, PileTier tier, uint32_t* overflow_list, uint32_t* overflow_count,
+                      hipStream_t stream) {
+    launch_pile_kernel(args, grid, tier, PilePass::kPrimary, overflow_list, overflow_count, stream);
+}
+
+void launch_pile_sens(const PileArgs& args, uint32_t grid, PileTier tier, int mode, uint32_t* overflow_list,
+                      uint32_t* overflow_count, hipStream_t stream) {
+    launch_pile_kernel(args, grid, tier, mode == 1 ? PilePass::kSensMedians : PilePass::kSensHills, overflow_list, overflow_count, stream);
 }
 
 }  // namespace rala_hip
+

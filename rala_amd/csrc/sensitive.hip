@@ -152,16 +152,16 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
     }
     pa.n_items_dev = nullptr;
     pa.order = sp.out[kClassCap512]; pa.n_items = cls[kClassCap512];
-    launch_pile_sens(pa, cls[kClassCap512], 0, mode, handed_512, from_512, s);
+    launch_pile_sens(pa, cls[kClassCap512], PileTier::kCap512First, mode, handed_512, from_512, s);
     pa.order = sp.out[kClassCap512Long]; pa.n_items = cls[kClassCap512Long];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap512Long], 16384), 3, mode, handed_512, from_512, s);
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap512Long], 16384), PileTier::kUpTo32k, mode, handed_512, from_512, s);
     pa.order = sp.out[kClassCap1024]; pa.n_items = cls[kClassCap1024];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap1024], 8192), 1, mode, handed_1024, from_1024, aux);
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap1024], 8192), PileTier::kCap1024, mode, handed_1024, from_1024, aux);
     if (aux != s) HIPCHECK(hipEventRecord(ctx->ev[kEvSensAuxDone], aux));
     // (the event-dense reads: run space at 2048 events, one wavefront per SIMD - 6 842 of C5's 281 k targets took as long in
     // position space as all the others in theirs; what this kernel hands on goes down the chain with the cap-1024 kernel's)
     pa.order = sp.out[kClassCap2048]; pa.n_items = cls[kClassCap2048];
-    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap2048], 4096), 2, mode, handed_1024, from_1024, pos);
+    launch_pile_sens(pa, std::min<uint32_t>(cls[kClassCap2048], 4096), PileTier::kCap2048, mode, handed_1024, from_1024, pos);
     if (const uint32_t n_rest = cls[kClassPosition]) {
         std::vector<uint32_t> rest(ctx->p_sens_rest.p, ctx->p_sens_rest.p + std::min<uint32_t>(n_rest, kRestAhead));
         if (n_rest > kRestAhead) {
@@ -182,7 +182,7 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
         }
     }
     pa.order = handed_512; pa.n_items = count; pa.n_items_dev = from_512;
-    launch_pile_sens(pa, std::min<uint32_t>(count, 2048), 1, mode, handed_1024, from_1024, s);
+    launch_pile_sens(pa, std::min<uint32_t>(count, 2048), PileTier::kCap1024, mode, handed_1024, from_1024, s);
     // look 2: what was handed on, and the call's counters
     uint32_t handed[kChainLookWords] = {};
     HIPCHECK(d2h_small(ctx, handed, from_512, sizeof(handed), s));
@@ -190,7 +190,7 @@ int run_sens_pass(rala_hip_ctx* ctx, PileArgs pa, const RepeatArgs& ra, int mode
     HIPCHECK(stream_sync(ctx, s));
     HIPCHECK(hipGetLastError());
     trc(mode == 1 ? "sens pass 1: run space" : "sens pass 2: run space", count);
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] sens pass %d: classes %u / %u / %u / %u / %u, handed on %u + %u\n", mode, cls[kClassCap512], cls[kClassCap512Long], cls[kClassCap1024],
                 cls[kClassCap2048], cls[kClassPosition], handed[kChainFrom512], handed[kChainFrom1024]);
     }

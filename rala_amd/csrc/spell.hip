@@ -7,7 +7,6 @@
 #include "spell.h"
 
 using namespace rala_hip;
-using rala_hip::ingest::now_ms;
 
 void rala_hip::bases_released(rala_hip_ctx* ctx) {
     ctx->d_bases.release();
@@ -133,7 +132,7 @@ int rala_hip_spell(rala_hip_ctx* ctx, const rala_hip_span* spans, uint64_t n_spa
     info.upload_ms = (float)(t1 - t0);
     info.kernel_ms = (float)kernel_ms;
     info.copy_ms = (float)copy_ms;
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         fprintf(stderr, "[trace] device spell: %lu spans, %lu bytes in %lu windows, upload %.2f ms, kernel %.2f ms, bytes to the host %.2f ms\n",
                 (unsigned long)n_spans, (unsigned long)total, (unsigned long)info.windows, info.upload_ms, info.kernel_ms, info.copy_ms);
     }

@@ -250,7 +250,7 @@ int rala_hip::gpu_tail_part_b(rala_hip_ctx* ctx) {
     HIPCHECK(d2h_small(ctx, &look, ctx->d_counts.p + kTailTotals, sizeof(look), s));
     HIPCHECK(stream_sync(ctx, s));
     HIPCHECK(hipGetLastError());
-    if (getenv("RALA_HIP_TRACE")) {
+    if (trace_on()) {
         struct { uint32_t ov, in, ov_conditional, in_conditional; } killers = {};
         static_assert(sizeof(killers) == kTailKillerWords * 4, "one word per count");
         HIPCHECK(hipMemcpy(&killers, ctx->d_counts.p + kTailKillers, sizeof(killers), hipMemcpyDeviceToHost));

@@ -148,7 +148,7 @@ def lib(build=True):
         path = LIB_PATH
         if build:
             path = _build.build_hip()
-        if os.environ.get("RALA_HIP_LIB_AB"):        # (measurements: another build of the library, tools/gpurun/r6_build_ab.sh)
+        if os.environ.get("RALA_HIP_LIB_AB"):        # (measurements: another build of the library, profiles/r19_pipeline_split.txt)
             path = os.environ["RALA_HIP_LIB_AB"]
         if not os.path.exists(path):
             raise RuntimeError("librala_hip.so is missing: run __graft_entry__.build()")

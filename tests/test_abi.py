@@ -130,3 +130,24 @@ def test_create_sequence_keeps_the_reference_fatal_checks():
         res = subprocess.run([sys.executable, "-c", code, name, data], capture_output=True, text=True)
         assert res.returncode == 1
         assert "[rala::createSequence] error: empty %s!" % what in res.stderr
+
+
+def test_library_reads_only_the_kept_environment_variables():
+    """rala_amd/csrc asks the environment for the trace, the two switches tests set and nothing else; the measurement builds'
+    macros are gone from it (what they switched: docs/history/experiments/)"""
+    kept = {"RALA_HIP_TRACE", "RALA_HIP_TRACE_BUFFERS", "RALA_INGEST_WINDOW", "RALA_HIP_DEBUG_FAIL_RANK"}
+    d = os.path.join(ROOT, "rala_amd", "csrc")
+    files = sorted(f for f in os.listdir(d) if f.endswith((".hip", ".h")))
+    assert len(files) >= 50
+    asked = set()
+    for f in files:
+        text = open(os.path.join(d, f)).read()
+        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", text)
+        for arg in calls:
+            m = re.fullmatch(r'\s*"([A-Za-z_0-9]+)"\s*', arg)
+            assert m, "%s: getenv(%s) does not name its variable" % (f, arg)
+            assert m.group(1) in kept, "%s reads %s" % (f, m.group(1))
+            asked.add(m.group(1))
+        for macro in ("RALA_PILE_AB", "RALA_ROW_STORE_MOD", "RALA_EXPAND_EXTEND"):
+            assert macro not in text, "%s mentions %s" % (f, macro)
+    assert asked == kept

@@ -177,6 +177,24 @@ def test_refusals_in_every_state(hip_ctx_factory):
     parity.check_tr(ctx, st)
 
 
+def test_removed_measurement_option_is_unknown(hip_ctx_factory):
+    """debug_pile_variant (the pile kernel's measurement variants, docs/history/experiments/r20_pile_ab_variants.patch) is refused
+    like any unknown key, and the context goes on: it initializes a set of 8 reads and 16 overlaps"""
+    ctx = hip_ctx_factory()
+    _refused(ctx, lambda: ctx.set_option("debug_pile_variant", 0), "unknown option")
+    # 8 reads of 10 000 bases; read r is the query of two overlaps, with r + 1 and r + 2, over [200, 9800) on both sides: every
+    # read lies under four, each bound 15 bases further in (the oracle says the same)
+    a = np.repeat(np.arange(8), 2)
+    lo, hi = np.full(16, 200), np.full(16, 9800)
+    ctx.set_reads(np.full(8, 10_000, dtype=np.uint32))
+    ctx.set_overlaps(Overlaps(a_id=a, b_id=(a + np.tile([1, 2], 8)) % 8, a_begin=lo, a_end=hi, b_begin=lo, b_end=hi, length=hi - lo,
+                              strand=np.zeros(16, dtype=np.uint8)))
+    ctx.initialize()
+    p = ctx.piles()
+    for k, want in (("alive", 1), ("begin", 215), ("end", 9785), ("median", 4), ("p10", 4)):
+        parity.assert_same("piles." + k, p[k], np.full(8, want, dtype=p[k].dtype))
+
+
 # ---- one context, several data sets --------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("pile_rows", [1, 0])
