@@ -119,6 +119,7 @@ const char* rala_hip_last_error(const rala_hip_ctx* ctx);
  * "debug_dedupe_list_cap" (tests: the list of the runs duplicate removal's counting pass marks holds this many marks, 0 = the
  * default 2^20; a list that does not hold them all is given up and the pass over all overlaps does the work),
  * "gzip_on_device" (default 0; 1: rala_hip_set_overlaps_from_paf / _mhap inflate a single-member gzip file on the device, see there),
+ * "gzip_in_pieces" (default 0; with "gzip_on_device" 1: the ranks of a sharded run take such a file together, see rala_hip_mg_set_overlaps_from_mhap),
  * "gzip_members" (default 0; with "gzip_on_device" 1: a gzip file of SEVERAL members that is not BGZF - cat a.gz b.gz, pigz -i,
  * a .gz file that was appended to - is walked member by member on the device instead of refused, see rala_hip_gzip_chain_members),
  * "gzip_chunk_bytes" (default 65536: the compressed bytes one wave of that inflater starts in; at least 1024),
@@ -595,6 +596,54 @@ int rala_hip_mg_set_overlaps_from_paf(rala_hip_mg* mg, const char* path, int che
  * *irregular = 8 on every rank, nothing set. */
 int rala_hip_mg_set_overlaps_from_mhap(rala_hip_mg* mg, const char* path, int check_lengths, uint32_t threads, int64_t* length_error_read,
                                        int* irregular);
+/* ---- a single-member gzip file that is not BGZF, over the ranks (option "gzip_in_pieces" beside "gzip_on_device") --------------
+ * What gzip, pigz and `minimap2 | gzip` write.  With both options set on rala_hip_mg_context(mg) of EVERY rank (default 0: such a
+ * file is *irregular = 8 on every rank before anything is shipped), rala_hip_mg_set_overlaps_from_paf / _mhap take it together.
+ * The options are part of the collective call's contract - every rank makes the same calls in the same order with the same
+ * options; ranks that differ wait for each other in exchanges the others do not make.
+ * Every rank ships the whole compressed file and looks for block starts in its own chunks of "gzip_chunk_bytes" (rank k of P:
+ * chunks [n k / P, n (k + 1) / P), chunk 0 always rank 0's); the ranks exchange the chunks' starts, count their own chunks -
+ * each landing on a start some rank found - exchange the spans and build the same chain (rala_hip_gzip_chain).  A rank owns
+ * the chain's jobs that begin in its chunks (rala_hip_gzip_pieces) and decodes them, and what the tokeniser's halo needs behind
+ * them, into 16-bit symbols behind 32 768 markers "byte i of the 32 768 in front of this piece" - without a byte of the text in
+ * front of it.  A kernel follows the markers of the last 32 768 symbols of its own text to bytes or to markers into the
+ * window in front of the piece (the rank's OUT-window); the ranks exchange those 64 KB each and every rank composes the window
+ * in front of its own piece from the ones of the ranks before it (rala_hip_gzip_compose_windows).  With that as the carry the
+ * text is resolved as a window of a single context's walk is, the lines whose first byte lies in the rank's own text are
+ * tokenised, and the CRC registers of the ranks' own texts, chained in rank order, must give the trailer's CRC32 (ISIZE and
+ * the final block's end: the chain's).  Anything else - on any rank - is *irregular = 8 on every rank with nothing set; a
+ * failure of one rank alone (device memory for its piece: symbols and text, 3 bytes per byte of text, are held at once) is
+ * learned by every rank in the next exchange: every rank's call fails, and the group stays usable.
+ * Not taken so, as before: BGZF (option "bgzf_in_pieces"), files of several members, -s files (rala_hip_tokenise_sensitive).
+ *
+ * The split of a chain over the parts (no context, no device): job j begins at bit job_start_bit[j] (ascending) of a file whose
+ * deflate bytes begin at deflate_off and are cut into n_chunks chunks of chunk_bytes; part k's jobs are
+ * [first_job[k], first_job[k + 1]) - first_job has parts + 1 entries, an empty run is legal.  RALA_HIP_EINVAL: parts or
+ * chunk_bytes 0, jobs without chunks, a first bit in front of deflate_off, starts that do not ascend. */
+int rala_hip_gzip_pieces(const uint64_t* job_start_bit, uint64_t n_jobs, uint64_t deflate_off, uint64_t chunk_bytes, uint64_t n_chunks,
+                         uint32_t parts, uint64_t* first_job);
+/* The window in front of part `part` (< parts) from the parts' out-windows (no context, no device).  out_windows[r * 32768 + i]:
+ * the symbol 32 768 - i in front of the end of part r's own text - a byte (< 0x100), or 0x8000 | k: entry k of the window in
+ * front of part r (0x8000 | 0 is such a marker).  W_0 is nothing at all; W_{r+1}[i] = out_r[i] where that is a byte, else
+ * W_r[out_r[i] & 0x7FFF].  in_window[i] = W_part[i]: a byte, or RALA_HIP_GZIP_NOTHING where the file's text has not begun
+ * (the carry the device gets says 0x8000 there, the convention of its kernels).  *valid = 0: an entry that is neither byte nor
+ * marker, or nothing BEHIND a byte - a window is the tail of the text, so nothing stands in front of all its bytes or a match
+ * copied it from in front of the file's first byte, which zlib refuses. */
+#define RALA_HIP_GZIP_NOTHING 0x4000
+int rala_hip_gzip_compose_windows(const uint16_t* out_windows, uint32_t parts, uint32_t part, uint16_t* in_window, int* valid);
+/* the rank's piece in the last rala_hip_mg_set_overlaps_from_paf / _mhap on the slice context: every such call begins with zeros,
+ * and zeros stay where the file was not taken together (options off, another kind of file) or was refused before the resolve */
+typedef struct rala_hip_gzip_pieces_info {
+    uint64_t own_chunks;            /* chunks the rank looked for a start in and counted */
+    uint64_t own_jobs;              /* jobs of the chain that begin in them */
+    uint64_t halo_jobs;             /* jobs behind them decoded for the tokeniser's halo */
+    uint64_t own_text_bytes;
+    uint64_t window_markers;        /* own symbols that resolved through the composed window in front of the piece */
+    uint32_t longest_chase;         /* the compose kernel's longest way from a symbol to a byte or to that window, in hops */
+    float compose_ms;               /* the compose kernel and its copies */
+    float exchange_ms;              /* the four host exchanges, waiting for the slowest rank included */
+} rala_hip_gzip_pieces_info;
+int rala_hip_get_gzip_pieces_info(rala_hip_ctx* ctx, rala_hip_gzip_pieces_info* out);
 /* the rank's slice as it was set: file position of its record 0, records (the columns: rala_hip_get_overlap_columns on
  * rala_hip_mg_context(mg)) */
 int rala_hip_mg_get_slice(rala_hip_mg* mg, uint64_t* first, uint64_t* n);

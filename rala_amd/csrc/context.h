@@ -248,6 +248,7 @@ struct rala_hip_ctx {
     // chunks' jobs and text offsets, the 16-bit symbols, the segments' CRCs, the resident text
     bool gzip_on_device = false;
     bool gzip_members = false;                  // option: a file of several members is walked member by member (with gzip_on_device)
+    bool gzip_in_pieces = false;                // option: the ranks of a sharded run take a single-member gzip overlap file together (with gzip_on_device)
     bool bgzf_in_pieces = false;                // option: a rank of a sharded run takes its piece of a BGZF overlap file (rala_hip_mg_set_overlaps_from_*)
     int64_t gzip_chunk_bytes = 64 << 10;        // option: compressed bytes per chunk
     uint32_t debug_gzip_false_sync = 0;         // tests: every n-th chunk is given a bogus start at its first bit
@@ -261,6 +262,8 @@ struct rala_hip_ctx {
     rala_hip::DevBuf<uint8_t> d_gzip_cands, d_gzip_mspans, d_gzip_pieces;
     std::vector<rala_hip::GzipMember> gzip_members_last;
     rala_hip_gzip_timings gzip_tm = {};
+    rala_hip_gzip_pieces_info gzip_pieces = {}; // the rank's piece of the last such ingest (rala_hip_get_gzip_pieces_info)
+    rala_hip::DevBuf<uint32_t> d_gzip_compose_stats;    // four words of gzip_window_compose_kernel's own
     // the sequence index (ingest_sequences.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
     int64_t debug_sequence_window = 0;          // tests: the window over the read file's text (0: as the overlap ingest's, 2 GiB at most)
     rala_hip::DevBuf<uint64_t> d_seq_event[2], d_seq_name_pos, d_seq_data_off, d_seq_data_stripped, d_seq_name_off, d_seq_span;

@@ -193,6 +193,7 @@ int rala_hip_set_option(rala_hip_ctx* ctx, const char* key, int64_t value) {
     if (!strcmp(key, "debug_sequence_window")) { ctx->debug_sequence_window = std::max<int64_t>(0, value); return RALA_HIP_OK; }
     if (!strcmp(key, "gzip_on_device")) { ctx->gzip_on_device = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "gzip_members")) { ctx->gzip_members = value != 0; return RALA_HIP_OK; }
+    if (!strcmp(key, "gzip_in_pieces")) { ctx->gzip_in_pieces = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "bgzf_in_pieces")) { ctx->bgzf_in_pieces = value != 0; return RALA_HIP_OK; }
     if (!strcmp(key, "gzip_chunk_bytes")) { ctx->gzip_chunk_bytes = value > 0 ? value : 64 << 10; return RALA_HIP_OK; }
     if (!strcmp(key, "debug_gzip_false_sync")) { ctx->debug_gzip_false_sync = (uint32_t)std::max<int64_t>(0, value); return RALA_HIP_OK; }

@@ -974,6 +974,47 @@ __global__ __launch_bounds__(256) void gzip_carry_kernel(const uint16_t* __restr
     out[i] = p < kRing ? sym[p] : (uint16_t)text[p - kRing];
 }
 
+// ---- a PIECE of a stream (a rank of a sharded run: option gzip_in_pieces) -------------------------------------------------------
+// The piece's symbols lie behind a ring of kRing identity markers (0x8000 | i: "byte i of the 32 768 in front of this piece"),
+// as the writing pass left them: a marker of chunk j stands for symbol text_off[j] - kRing + k, which may itself be a marker of
+// an earlier chunk - the windows pass has not run, and must not have (it needs the bytes in front of the piece, which are what
+// this kernel helps to find).  One lane per symbol follows its marker from chunk to chunk until it meets a byte or the ring:
+// every hop lands in a strictly earlier chunk or in the ring, so n_own + 1 hops are the most there can be; a lane that needs
+// more (text offsets that do not ascend) sets the flag.  Nothing is written to sym.
+//   lanes [0, kRing): out[i] = symbol own_n + i of (ring ++ the piece's own own_n symbols) - the piece's OUT-window, each
+//     entry a byte or a marker into the ring, that is into the piece's in-window;
+//   lanes [kRing, kRing + own_n): the own symbols, counted where they end in the ring (stats[0], 64 bits) - what the piece
+//     takes from the pieces in front of it; stats[2] = the longest chase in hops.
+constexpr uint32_t kComposeThreads = 256;
+__global__ __launch_bounds__(kComposeThreads) void gzip_window_compose_kernel(const uint16_t* __restrict__ sym, const uint64_t* __restrict__ text_off,
+                                                                             uint32_t n_own, uint64_t own_n, uint16_t* __restrict__ out,
+                                                                             uint32_t* __restrict__ stats, uint32_t* flags) {
+    const uint64_t lane = (uint64_t)blockIdx.x * kComposeThreads + threadIdx.x;
+    const bool window = lane < kRing;
+    const bool live = lane < kRing + own_n;
+    uint64_t p = window ? own_n + lane : lane;                      // (positions count from the ring's first symbol)
+    uint32_t s = live ? sym[p] : 0u, hops = 0;
+    bool lost = false;
+    while ((s & 0x8000u) && p >= kRing) {
+        if (hops > n_own) { lost = true; break; }
+        const uint32_t j = owner_of(text_off, n_own, p);
+        p = text_off[j] + (s & 0x7FFFu) - kRing;                    // text_off[j] >= kRing: the ring lies in front of the first chunk
+        if (p >= kRing + own_n) { lost = true; break; }             // (never forward: text offsets that are not the chain's)
+        s = sym[p];
+        ++hops;
+    }
+    if (lost) atomicOr(flags, 8u);
+    if (window) out[lane] = (uint16_t)(lost ? 0x8000u : s);
+    // per wave: the own symbols that ended in the ring, the longest chase
+    const unsigned long long through = __ballot(live && !window && !lost && (s & 0x8000u));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) hops = max(hops, (uint32_t)__shfl_xor((int)hops, off, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        if (through) atomicAdd((unsigned long long*)stats, (unsigned long long)__popcll(through));
+        if (hops) atomicMax(stats + 2, hops);
+    }
+}
+
 // ---- the members of a gzip file (cat a.gz b.gz, pigz -i) -----------------------------------------------------------------------
 constexpr uint32_t kHeadTile = 4096;        // bytes of the file per workgroup of the member find
 constexpr uint32_t kHeadThreads = 256;      // 16 bytes per thread
@@ -1170,6 +1211,33 @@ uint32_t gzip_ring_symbols() { return kRing; }
 void launch_gzip_carry(uint16_t* sym, const uint8_t* text, uint64_t text_n, uint16_t* tmp, hipStream_t s) {
     hipLaunchKernelGGL(gzip_carry_kernel, dim3(kRing / 256), dim3(256), 0, s, sym, text, text_n, tmp);
     (void)hipMemcpyAsync(sym, tmp, kRing * sizeof(uint16_t), hipMemcpyDeviceToDevice, s);
+}
+
+// The find and the count over the chunks [c0, c1) alone, with the kernels as they are: both give the chunk of block 0 a special
+// role (the stream's first chunk), so for c0 > 0 the launch begins one chunk earlier and that block's output is no result -
+// launch_gzip_find_range writes a value of no meaning to starts[c0 - 1], and launch_gzip_count_range expects the caller to have
+// put kGzipNoStart there (the block then decodes nothing); spans[c].next counts from chunk c0 - 1 then (c0 = 0: from chunk 0).
+void launch_gzip_find_range(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t c0, uint32_t c1,
+                            uint32_t false_sync, uint64_t* starts, hipStream_t s) {
+    if (c1 <= c0) return;
+    const uint32_t lead = c0 ? 1 : 0;
+    hipLaunchKernelGGL(gzip_find_kernel, dim3(c1 - c0 + lead), dim3(kWave), 0, s, comp, end, n_words, deflate_off + (uint64_t)(c0 - lead) * chunk_bytes,
+                       chunk_bytes, false_sync, starts + (c0 - lead));
+}
+
+void launch_gzip_count_range(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, uint32_t c0, uint32_t c1, GzipSpan* spans,
+                             hipStream_t s) {
+    if (c1 <= c0) return;
+    const uint32_t lead = c0 ? 1 : 0, base = c0 - lead;
+    // (block b is chunk base + b; it lands on the starts behind it, to the file's last chunk)
+    hipLaunchKernelGGL(gzip_count_kernel, dim3(c1 - base), dim3(kWave), 0, s, comp, end, starts + base, n_chunks - base, spans + base, nullptr, 0ull,
+                       1ull, nullptr);
+}
+
+void launch_gzip_window_compose(const uint16_t* sym, const uint64_t* text_off, uint32_t n_own, uint64_t own_n, uint16_t* out, uint32_t* stats,
+                                uint32_t* flags, hipStream_t s) {
+    const uint64_t blocks = (kRing + own_n + kComposeThreads - 1) / kComposeThreads;
+    hipLaunchKernelGGL(gzip_window_compose_kernel, dim3((uint32_t)blocks), dim3(kComposeThreads), 0, s, sym, text_off, n_own, own_n, out, stats, flags);
 }
 
 uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n) {

@@ -92,12 +92,6 @@ PafTarget paf_target(DevBuf<uint32_t>* col, DevBuf<uint8_t>* strand, bool mhap) 
     return T;
 }
 
-int ingest_ready(rala_hip_ctx* ctx, bool mhap) {
-    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
-    if (ctx->n_name_buckets == 0 && !mhap) return fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
-    return RALA_HIP_OK;
-}
-
 // An overlap file's text, wherever it comes from: a plain file's bytes, a BGZF file's members (text_n: their text), a gzip
 // member's text resident in ctx->d_gzip_text.
 struct OverlapText {
@@ -268,6 +262,27 @@ int rala_hip::overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_
                 (unsigned long)F, (unsigned long)X.bg.jobs.size(), X.bg.shipped / 1e9, X.bg.ship_ms, X.bg.text_n / 1e9, X.bg.inflate_ms);
     }
     return RALA_HIP_OK;
+}
+
+// A rank's piece of a single-member gzip file (ingest_gzip.hip: gzip_piece_*), behind the exchange of the out-windows: resolved,
+// then the lines whose FIRST byte lies in the piece's own text tokenised - the rule of a plain file's byte ranges; the byte in
+// front of the own text is the last of the window in front of it, the line at text offset 0 is part 0's.
+int rala_hip::gzip_piece_tokenise(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, bool check_lengths, uint32_t threads,
+                                  size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t own[2]) {
+    *out = PafRange();
+    uint32_t flag = 0;
+    int rc = gzip_piece_resolve(ctx, g, all, stride, &flag, own);
+    if (rc != RALA_HIP_OK) return rc;
+    if (flag) { out->flags = 8; return RALA_HIP_OK; }
+    OverlapText X;
+    X.kind = kTextGzip;
+    uint64_t own_n = 0, n_w = 0;
+    float ship_ms = 0;
+    gzip_piece_text(g, &own_n, &n_w, &X.file_n, &ship_ms, &X.gz.n_readers);
+    X.text_n = 16 + n_w;                        // (16 bytes in front of the text: the byte in front of it is the last of them)
+    rc = tokenise_range(ctx, X, 16, 16 + own_n, check_lengths, threads, extra_rows, T, out);
+    if (rc == RALA_HIP_OK) ctx->ingest_tm.ship_ms += ship_ms;
+    return rc;
 }
 
 extern "C" {

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,13 @@ inline int open_regular(rala_hip_ctx* ctx, const char* path, Fd& file, uint64_t*
     struct stat st;
     if (fstat(file.fd, &st) != 0 || !S_ISREG(st.st_mode)) return fail(ctx, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
     *size = (uint64_t)st.st_size;
+    return RALA_HIP_OK;
+}
+
+// what every way into the tokeniser needs of the context first
+inline int ingest_ready(rala_hip_ctx* ctx, bool mhap) {
+    if (ctx->n_reads == 0) return fail(ctx, RALA_HIP_EINVAL, "no reads set");
+    if (ctx->n_name_buckets == 0 && !mhap) return fail(ctx, RALA_HIP_EINVAL, "no name table set (rala_hip_set_name_table)");
     return RALA_HIP_OK;
 }
 

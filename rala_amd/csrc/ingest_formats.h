@@ -280,6 +280,65 @@ inline bool gzip_chain_from_spans(const uint64_t* starts, const GzipSpan* spans,
     return end_bit / 8 + (end_bit % 8 != 0) == end && (uint32_t)text_n == isize;
 }
 
+// ---- a single-member gzip stream over the ranks of a sharded run (option gzip_in_pieces) ------------------------------------
+// Part k of `parts` owns the chunks [gzip_part_chunk(k), gzip_part_chunk(k + 1)): n_chunks k / parts, except that chunk 0 -
+// whose start is the stream's, not one to be found - is always part 0's.
+inline uint64_t gzip_part_chunk(uint64_t n_chunks, uint32_t parts, uint32_t k) {
+    if (k == 0) return 0;
+    if (k >= parts) return n_chunks;
+    return std::min(n_chunks, std::max<uint64_t>(1, (uint64_t)((unsigned __int128)n_chunks * k / parts)));
+}
+
+// A job of the chain belongs to the part whose chunk range holds the chunk its first bit lies in; the chain ascends, so part
+// k's jobs are one run [first_job[k], first_job[k + 1]) - an empty one where no block start was found in its chunks (a stream of
+// fixed or stored blocks: all of it part 0's).  false: no parts, no chunks, a first bit in front of the deflate bytes, starts
+// that do not ascend.
+inline bool gzip_pieces_split(const uint64_t* job_start_bit, uint64_t n_jobs, uint64_t deflate_off, uint64_t chunk_bytes, uint64_t n_chunks,
+                              uint32_t parts, uint64_t* first_job) {
+    if (!parts || !chunk_bytes || (n_jobs && !n_chunks)) return false;
+    uint32_t k = 0;
+    first_job[0] = 0;
+    for (uint64_t j = 0; j < n_jobs; ++j) {
+        const uint64_t byte = job_start_bit[j] / 8;
+        if (byte < deflate_off || (j && job_start_bit[j] <= job_start_bit[j - 1])) return false;
+        const uint64_t c = std::min((byte - deflate_off) / chunk_bytes, n_chunks - 1);
+        while (k + 1 < parts && c >= gzip_part_chunk(n_chunks, parts, k + 1)) first_job[++k] = j;
+    }
+    while (k < parts) first_job[++k] = n_jobs;
+    return true;
+}
+
+// The window in front of a part - the 32 768 bytes of text that precede its first own byte - from the parts' OUT-windows:
+// out_windows[r * 32768 + i] is the symbol 32 768 - i in front of the end of part r's own text, a byte or 0x8000 | k = "entry k
+// of the window in front of part r" (what gzip_window_compose_kernel writes).  W_0 is nothing at all; W_{r+1}[i] = out_r[i] where
+// that is a byte, else W_r[out_r[i] & 0x7FFF].  in_window = W_part: bytes, and kGzipNothing where the file's text has not begun.
+// 0x8000 | 0 is a marker like any other, so "nothing" has a code that is neither a byte nor a marker.  *valid = false: an entry
+// that is neither, or nothing BEHIND a byte - a window is the text's tail, nothing can only stand in front of all its bytes;
+// behind one it is what a match copied from in front of the text's first byte, which zlib refuses.
+constexpr uint32_t kGzipWindow = 32768;
+constexpr uint16_t kGzipNothing = 0x4000;
+inline void gzip_compose_windows(const uint16_t* out_windows, uint32_t part, uint16_t* in_window, bool* valid) {
+    std::vector<uint16_t> w(kGzipWindow, kGzipNothing), next(kGzipWindow);
+    bool ok = true;
+    for (uint32_t r = 0; r < part; ++r) {
+        const uint16_t* o = out_windows + (size_t)r * kGzipWindow;
+        for (uint32_t i = 0; i < kGzipWindow; ++i) {
+            const uint16_t s = o[i];
+            if (s < 0x100) next[i] = s;
+            else if (s & 0x8000) next[i] = w[s & 0x7FFF];
+            else { next[i] = kGzipNothing; ok = false; }
+        }
+        w.swap(next);
+    }
+    bool byte_seen = false;
+    for (uint32_t i = 0; i < kGzipWindow; ++i) {
+        if (w[i] != kGzipNothing) byte_seen = true;
+        else if (byte_seen) ok = false;
+        in_window[i] = w[i];
+    }
+    *valid = ok;
+}
+
 // ---- a gzip file of several members (cat a.gz b.gz, pigz -i, appended files) ------------------------------------------------
 // The same walk through a file whose members follow each other as gzread walks them (reference src/graph.cpp:190-224): besides
 // the chunks, the member headers the device found (cands[k], ascending header_off: launch_gzip_member_find) and what it counted

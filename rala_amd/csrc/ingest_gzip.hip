@@ -4,6 +4,8 @@
 // its start, the chain from chunk 0 built and proven on the host - and two back ends: the whole text at once (overlap files)
 // or window by window (read files).  Either proves every member: its ISIZE in the chain, its CRC32 from the registers of the
 // 16 KB segments that lie inside it and of the pieces of those a member boundary cuts.
+// A third way for one member and the ranks of a sharded run (option gzip_in_pieces): every rank its own chunks of the stream, in
+// steps with the ranks' exchanges between them (gzip_piece_*, below).
 #include "ingest_common.h"
 
 using namespace rala_hip;
@@ -357,6 +359,309 @@ bool rala_hip::ingest::gzip_walk_proven(const GzipWalk& g) {
     return g.next_job == g.chain.size() && g.proven == g.members.size() && g.crc_ok;
 }
 
+// ---- in PIECES over the ranks of a sharded run (option gzip_in_pieces; the collectives between the steps: sharded.hip) --------
+// The writing pass gives symbols that name the 32 768 bytes in front of a chunk without knowing them, so a rank decodes its own
+// chunks of the stream without a byte of the text in front of them; what travels is every chunk's start and span (so that every
+// rank builds the same chain) and one window of 32 768 symbols per rank (so that every rank learns the bytes in front of its
+// piece).  Every rank ships the whole compressed file; windows inside a piece are not made: own text and halo fit at once or
+// the step fails with ENOMEM.
+struct rala_hip::GzipPieceRun {
+    Fd file;
+    std::string path;
+    uint64_t file_n = 0, deflate_off = 0, end = 0, chunk = 0, n_chunks = 0;
+    uint32_t crc = 0, isize = 0;
+    uint32_t part = 0, parts = 1;
+    uint64_t c0 = 0, c1 = 0, most = 0;          // own chunks; the most chunks any part owns
+    std::vector<uint64_t> starts;               // of all chunks, behind the first exchange
+    std::vector<GzipJob> chain;                 // the same on every rank
+    size_t j0 = 0, j1 = 0, j2 = 0;              // own jobs [j0, j1), written jobs [j0, j2)
+    uint64_t a = 0, b = 0, n_w = 0;             // own text [a, b), written text [a, a + n_w)
+    uint32_t n_readers = 0;
+    float ship_ms = 0;
+    rala_hip_gzip_timings tm = {};
+    rala_hip_gzip_pieces_info info = {};
+};
+
+uint64_t rala_hip::gzip_piece_most_chunks(uint64_t n_chunks, uint32_t parts) {
+    uint64_t most = 0;
+    for (uint32_t k = 0; k < parts; ++k) most = std::max(most, gzip_part_chunk(n_chunks, parts, k + 1) - gzip_part_chunk(n_chunks, parts, k));
+    return most;
+}
+
+int rala_hip::gzip_piece_open(rala_hip_ctx* ctx, const char* path, bool mhap, uint64_t head[6], GzipPieceRun** run) {
+    for (int k = 0; k < 6; ++k) head[k] = 0;
+    *run = nullptr;
+    std::unique_ptr<GzipPieceRun> g(new GzipPieceRun());
+    g->path = path;
+    ctx->gzip_pieces = rala_hip_gzip_pieces_info();
+    int rc = ingest_ready(ctx, mhap);
+    if (rc != RALA_HIP_OK) return rc;
+    rc = open_regular(ctx, path, g->file, &g->file_n);
+    if (rc != RALA_HIP_OK) return rc;
+    const uint64_t file_n = g->file_n;
+    std::vector<uint8_t> first((size_t)std::min(file_n, kGzipHeadReach));
+    uint8_t trailer[8];
+    if (file_n >= 18 && pread(g->file.fd, first.data(), first.size(), 0) == (ssize_t)first.size() && pread(g->file.fd, trailer, 8, (off_t)(file_n - 8)) == 8 &&
+        sniff(first.data(), first.size()) == kTextGzip && gzip_head(first.data(), first.size(), &g->deflate_off) && g->deflate_off + 8 < file_n) {
+        g->end = file_n - 8;
+        g->crc = le32(trailer);
+        g->isize = le32(trailer + 4);
+        g->chunk = (uint64_t)std::max<int64_t>(1024, ctx->gzip_chunk_bytes);
+        g->n_chunks = (g->end - g->deflate_off + g->chunk - 1) / g->chunk;
+        if (g->n_chunks >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "file too large for 32-bit chunk ids");
+        head[0] = 1; head[1] = file_n; head[2] = g->deflate_off; head[3] = g->n_chunks;
+        head[4] = g->crc; head[5] = g->isize;
+    }
+    *run = g.release();
+    return RALA_HIP_OK;
+}
+
+void rala_hip::gzip_piece_close(rala_hip_ctx* ctx, GzipPieceRun* run) {
+    if (!run) return;
+    ctx->d_bgzf_comp.release();
+    ctx->d_gzip_sym.release();
+    ctx->d_gzip_text.release();
+    ctx->d_gzip_starts.release();
+    ctx->d_gzip_spans.release();
+    ctx->d_gzip_carry.release();
+    ctx->d_gzip_compose_stats.release();
+    delete run;
+}
+
+// a. the file shipped, block starts found in the own chunks -> starts_out: `most` words, the own chunks' first
+int rala_hip::gzip_piece_find(rala_hip_ctx* ctx, GzipPieceRun* g, uint32_t part, uint32_t parts, uint32_t threads, std::vector<uint64_t>& starts_out) {
+    g->part = part;
+    g->parts = parts;
+    g->c0 = gzip_part_chunk(g->n_chunks, parts, part);
+    g->c1 = gzip_part_chunk(g->n_chunks, parts, part + 1);
+    g->most = gzip_piece_most_chunks(g->n_chunks, parts);
+    starts_out.assign(g->most, kGzipNoStart);
+    hipStream_t s = ctx->stream;
+    const uint64_t file_n = g->file_n;
+    const double t0 = now_ms();
+    if (ctx->d_bgzf_comp.ensure(file_n + 64) != hipSuccess || ctx->d_bgzf_flag.ensure(1) != hipSuccess || ctx->d_gzip_starts.ensure(g->n_chunks) != hipSuccess ||
+        ctx->d_gzip_spans.ensure(g->n_chunks * sizeof(GzipSpan)) != hipSuccess) {
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for the compressed file");
+    }
+    HIPCHECK(hipMemsetAsync(ctx->d_bgzf_comp.p + file_n, 0, 64, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_bgzf_flag.p, 0, 4, s));
+    if (ship_file(g->file.fd, 0, file_n, ctx->d_bgzf_comp.p, ctx->device, threads, nullptr, []() { return true; }, &g->n_readers)) {
+        return fail(ctx, RALA_HIP_EDEVICE, "reading / copying " + g->path + " failed");
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    g->ship_ms = (float)(t1 - t0);
+    g->tm.compressed_bytes = file_n;
+    g->tm.chunks = g->n_chunks;
+    launch_gzip_find_range(ctx->d_bgzf_comp.p, g->end, (file_n + 56) / 8, g->deflate_off, g->chunk, (uint32_t)g->c0, (uint32_t)g->c1, ctx->debug_gzip_false_sync,
+                           ctx->d_gzip_starts.p, s);
+    HIPCHECK(hipGetLastError());
+    if (g->c1 > g->c0) HIPCHECK(hipMemcpyAsync(starts_out.data(), ctx->d_gzip_starts.p + g->c0, (g->c1 - g->c0) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    g->tm.find_ms = (float)(now_ms() - t1);
+    g->info.own_chunks = g->c1 - g->c0;
+    return RALA_HIP_OK;
+}
+
+// b. all: every part's `most` start words at all[p * stride + 1 ..]; the own chunks counted, each landing on the starts behind it
+// wherever they were found -> spans_out: 4 words per chunk {end_bit, text, next | status << 32, refuted}
+int rala_hip::gzip_piece_count(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, std::vector<uint64_t>& spans_out) {
+    hipStream_t s = ctx->stream;
+    spans_out.assign(4 * g->most, 0);
+    g->starts.assign(g->n_chunks, kGzipNoStart);
+    for (uint32_t p = 0; p < g->parts; ++p) {
+        const uint64_t lo = gzip_part_chunk(g->n_chunks, g->parts, p), hi = gzip_part_chunk(g->n_chunks, g->parts, p + 1);
+        for (uint64_t c = lo; c < hi; ++c) g->starts[c] = all[(size_t)p * stride + 1 + (c - lo)];
+    }
+    const double t0 = now_ms();
+    std::vector<uint64_t> dev(g->starts);
+    if (g->c0) dev[g->c0 - 1] = kGzipNoStart;                  // (launch_gzip_count_range: the block in front of the own chunks decodes nothing)
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_starts.p, dev.data(), g->n_chunks * 8, hipMemcpyHostToDevice, s));
+    launch_gzip_count_range(ctx->d_bgzf_comp.p, g->end, ctx->d_gzip_starts.p, (uint32_t)g->n_chunks, (uint32_t)g->c0, (uint32_t)g->c1,
+                            (GzipSpan*)ctx->d_gzip_spans.p, s);
+    HIPCHECK(hipGetLastError());
+    std::vector<GzipSpan> spans(g->c1 - g->c0);
+    if (!spans.empty()) HIPCHECK(hipMemcpyAsync(spans.data(), (const GzipSpan*)ctx->d_gzip_spans.p + g->c0, spans.size() * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    const uint64_t base = g->c0 ? g->c0 - 1 : 0;
+    for (size_t c = 0; c < spans.size(); ++c) {
+        const GzipSpan& sp = spans[c];
+        spans_out[4 * c] = sp.end_bit;
+        spans_out[4 * c + 1] = sp.text;
+        spans_out[4 * c + 2] = (uint64_t)(uint32_t)(sp.next + base) | (uint64_t)sp.status << 32;
+        spans_out[4 * c + 3] = sp.refuted;
+    }
+    g->tm.decode_ms = (float)(now_ms() - t0);
+    ctx->d_gzip_starts.release();
+    ctx->d_gzip_spans.release();
+    return RALA_HIP_OK;
+}
+
+// c - e. all: every part's span words; the chain (the same on every rank; *valid = false: refused, nothing else was done), the
+// own jobs and those the halo needs written behind a ring of identity markers, the out-window composed -> window_out: 8192 words
+int rala_hip::gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, bool* valid, std::vector<uint64_t>& window_out) {
+    hipStream_t s = ctx->stream;
+    const uint64_t ring = gzip_ring_symbols();
+    *valid = false;
+    window_out.assign(ring / 4, 0);
+    std::vector<GzipSpan> spans(g->n_chunks);
+    for (uint32_t p = 0; p < g->parts; ++p) {
+        const uint64_t lo = gzip_part_chunk(g->n_chunks, g->parts, p), hi = gzip_part_chunk(g->n_chunks, g->parts, p + 1);
+        for (uint64_t c = lo; c < hi; ++c) {
+            const uint64_t* w = all + (size_t)p * stride + 1 + 4 * (c - lo);
+            spans[c] = GzipSpan{w[0], w[1], (uint32_t)w[2], (uint32_t)(w[2] >> 32), (uint32_t)w[3], 0};
+        }
+    }
+    if (!gzip_chain_from_spans(g->starts.data(), spans.data(), g->n_chunks, g->end, g->isize, g->chain, &g->tm)) return RALA_HIP_OK;
+    const size_t n_jobs = g->chain.size();
+    std::vector<uint64_t> start_bit(n_jobs), first_job(g->parts + 1);
+    for (size_t j = 0; j < n_jobs; ++j) start_bit[j] = g->chain[j].start_bit;
+    if (!gzip_pieces_split(start_bit.data(), n_jobs, g->deflate_off, g->chunk, g->n_chunks, g->parts, first_job.data())) return RALA_HIP_OK;
+    *valid = true;
+    const uint64_t text_n = g->tm.text_bytes;
+    auto off_of = [&](size_t j) { return j < n_jobs ? g->chain[j].text_off : text_n; };
+    g->j0 = first_job[g->part];
+    g->j1 = first_job[g->part + 1];
+    g->a = off_of(g->j0);
+    g->b = off_of(g->j1);
+    g->j2 = g->j1;
+    while (g->j2 < n_jobs && off_of(g->j2) - g->b < (uint64_t)paf_halo_bytes() + 1) ++g->j2;
+    g->n_w = off_of(g->j2) - g->a;
+    const uint64_t own_n = g->b - g->a;
+    g->info.own_jobs = g->j1 - g->j0;
+    g->info.halo_jobs = g->j2 - g->j1;
+    g->info.own_text_bytes = own_n;
+    if (own_n >= 1ull << 38) return fail(ctx, RALA_HIP_ETOOLARGE, "a piece's text too large for one launch");
+    std::vector<GzipJob> jobs(g->chain.begin() + g->j0, g->chain.begin() + g->j2);
+    std::vector<uint64_t> text_off(jobs.size() + 1, ring), floors(jobs.size() + 1, 0);
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - g->a);
+        floors[j] = ring >= g->a ? ring - g->a : 0;             // (where the file's text begins, in the launch's positions)
+    }
+    const uint64_t n_seg = (g->n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
+    if (n_seg >= 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
+    if (ctx->d_gzip_sym.ensure(ring + g->n_w + 64) != hipSuccess || ctx->d_gzip_text.ensure(16 + g->n_w + paf_chunk_bytes() + 8192) != hipSuccess ||
+        ctx->d_gzip_jobs.ensure((jobs.size() + 1) * sizeof(GzipJob)) != hipSuccess || ctx->d_gzip_off.ensure(text_off.size()) != hipSuccess ||
+        ctx->d_gzip_floor.ensure(floors.size()) != hipSuccess || ctx->d_gzip_crc.ensure(n_seg + 1) != hipSuccess || ctx->d_gzip_carry.ensure(ring) != hipSuccess ||
+        ctx->d_gzip_compose_stats.ensure(4) != hipSuccess) {
+        return fail(ctx, RALA_HIP_ENOMEM, "device memory for a piece of the inflated text");
+    }
+    std::vector<uint16_t> identity(ring);
+    for (uint32_t i = 0; i < ring; ++i) identity[i] = (uint16_t)(0x8000u | i);
+    const double t0 = now_ms();
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_sym.p, identity.data(), ring * 2, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_gzip_sym.p + ring + g->n_w, 0, 128, s));
+    if (!jobs.empty()) HIPCHECK(hipMemcpyAsync(ctx->d_gzip_jobs.p, jobs.data(), jobs.size() * sizeof(GzipJob), hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_off.p, text_off.data(), text_off.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_floor.p, floors.data(), floors.size() * 8, hipMemcpyHostToDevice, s));
+    launch_gzip_write(ctx->d_bgzf_comp.p, g->end, (const GzipJob*)ctx->d_gzip_jobs.p, (uint32_t)jobs.size(), ctx->d_gzip_sym.p, ctx->d_bgzf_flag.p, s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    const double t1 = now_ms();
+    g->tm.decode_ms += (float)(t1 - t0);
+    ctx->d_bgzf_comp.release();
+    // the out-window, taken at b
+    uint32_t stats[4] = {0, 0, 0, 0};
+    HIPCHECK(hipMemsetAsync(ctx->d_gzip_compose_stats.p, 0, 16, s));
+    launch_gzip_window_compose(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)(g->j1 - g->j0), own_n, ctx->d_gzip_carry.p, ctx->d_gzip_compose_stats.p,
+                               ctx->d_bgzf_flag.p, s);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(window_out.data(), ctx->d_gzip_carry.p, ring * 2, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(stats, ctx->d_gzip_compose_stats.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    g->info.window_markers = (uint64_t)stats[0] | (uint64_t)stats[1] << 32;
+    g->info.longest_chase = stats[2];
+    g->info.compose_ms = (float)(now_ms() - t1);
+    return RALA_HIP_OK;
+}
+
+// f - g. all: every part's out-window; the window in front of the piece composed and uploaded as the carry, windows and resolve
+// as for a window of a walk: the text [a, a + n_w) to ctx->d_gzip_text + 16 with the byte in front of it ('\n' in front of the
+// file's first) and newlines behind it; *flag: the inflater's.  own[0 .. 1] = CRC register and length of the own text [a, b).
+int rala_hip::gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, uint32_t* flag, uint64_t own[2]) {
+    hipStream_t s = ctx->stream;
+    const uint64_t ring = gzip_ring_symbols(), seg = gzip_segment_bytes();
+    *flag = 0;
+    own[0] = own[1] = 0;
+    std::vector<uint16_t> windows((size_t)g->parts * ring), carry(ring);
+    for (uint32_t p = 0; p < g->parts; ++p) memcpy(windows.data() + (size_t)p * ring, all + (size_t)p * stride + 1, ring * 2);
+    bool valid = false;
+    gzip_compose_windows(windows.data(), g->part, carry.data(), &valid);
+    // (a window that is not the text's tail: refused here - and by the rank whose match it was, whose resolve meets no byte)
+    if (!valid) *flag = 8;
+    uint8_t before = '\n';
+    if (g->a && carry[ring - 1] < 0x100) before = (uint8_t)carry[ring - 1];
+    for (uint32_t i = 0; i < ring; ++i) if (carry[i] >= 0x100) carry[i] = 0x8000;
+    const uint64_t own_n = g->b - g->a, n_w = g->n_w, n_seg = (n_w + seg - 1) / seg;
+    const uint32_t n_jobs = (uint32_t)(g->j2 - g->j0);
+    uint8_t* text = ctx->d_gzip_text.p + 16;
+    const double t0 = now_ms();
+    HIPCHECK(hipMemcpyAsync(ctx->d_gzip_sym.p, carry.data(), ring * 2, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(ctx->d_gzip_text.p, '\n', 16, s));
+    HIPCHECK(hipMemcpyAsync(text - 1, &before, 1, hipMemcpyHostToDevice, s));
+    launch_gzip_resolve(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, n_jobs, n_w, text, ctx->d_gzip_crc.p, ctx->d_bgzf_flag.p, s, ring);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemsetAsync(text + n_w, '\n', paf_chunk_bytes() + 8192 - 16, s));
+    std::vector<uint32_t> seg_crc(n_seg);
+    uint32_t kernel_flag = 0;
+    if (n_seg) HIPCHECK(hipMemcpyAsync(seg_crc.data(), ctx->d_gzip_crc.p, n_seg * 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(&kernel_flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    *flag |= kernel_flag;
+    // the own text's register: the whole segments' and, where b cuts one, that segment's front by gzip_piece_crc_kernel
+    std::vector<uint32_t> reg;
+    std::vector<uint64_t> len;
+    const uint64_t whole = own_n == n_w ? n_seg : own_n / seg;
+    for (uint64_t k = 0; k < whole; ++k) { reg.push_back(seg_crc[k]); len.push_back(std::min(seg, own_n - k * seg)); }
+    if (!*flag && whole * seg < own_n) {
+        const GzipPiece cut{whole * seg, (uint32_t)(own_n - whole * seg), 0};
+        uint32_t r = 0;
+        if (ctx->d_gzip_pieces.ensure(sizeof(GzipPiece)) != hipSuccess || ctx->d_gzip_piece_crc.ensure(1) != hipSuccess) {
+            return fail(ctx, RALA_HIP_ENOMEM, "device memory for the piece's last segment");
+        }
+        HIPCHECK(hipMemcpyAsync(ctx->d_gzip_pieces.p, &cut, sizeof(cut), hipMemcpyHostToDevice, s));
+        launch_gzip_piece_crc(text, (const GzipPiece*)ctx->d_gzip_pieces.p, 1, ctx->d_gzip_piece_crc.p, s);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(&r, ctx->d_gzip_piece_crc.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+        reg.push_back(r);
+        len.push_back(cut.n);
+    }
+    own[0] = gzip_crc_register_chain(reg.data(), len.data(), reg.size());
+    own[1] = own_n;
+    g->tm.resolve_ms = (float)(now_ms() - t0);
+    ctx->d_gzip_sym.release();
+    ctx->d_gzip_carry.release();
+    ctx->gzip_tm = g->tm;
+    ctx->gzip_pieces = g->info;
+    if (trace_on()) {
+        fprintf(stderr, "[trace] device inflate: part %u of %u of one gzip member: chunks [%lu, %lu) of %lu, jobs [%lu, %lu) and %lu for the halo, text [%lu, "
+                "%lu) of %lu; %lu own symbols through the window in front (longest chase %u hops), compose %.2f ms; find %.2f ms, decode %.2f ms, "
+                "resolve %.2f ms, the file shipped in %.1f ms\n", g->part, g->parts, (unsigned long)g->c0, (unsigned long)g->c1, (unsigned long)g->n_chunks,
+                (unsigned long)g->j0, (unsigned long)g->j1, (unsigned long)(g->j2 - g->j1), (unsigned long)g->a, (unsigned long)g->b,
+                (unsigned long)g->tm.text_bytes, (unsigned long)g->info.window_markers, g->info.longest_chase, g->info.compose_ms, g->tm.find_ms,
+                g->tm.decode_ms, g->tm.resolve_ms, g->ship_ms);
+    }
+    return RALA_HIP_OK;
+}
+
+void rala_hip::gzip_piece_text(const GzipPieceRun* g, uint64_t* own_n, uint64_t* n_w, uint64_t* file_n, float* ship_ms, uint32_t* n_readers) {
+    *own_n = g->b - g->a;
+    *n_w = g->n_w;
+    *file_n = g->file_n;
+    *ship_ms = g->ship_ms;
+    *n_readers = g->n_readers;
+}
+
+// every part's {register, length} of its own text, in part order: is the text the trailer's?
+bool rala_hip::gzip_piece_proven(const GzipPieceRun* g, const uint32_t* reg, const uint64_t* len, uint32_t parts) {
+    uint64_t total = 0;
+    for (uint32_t p = 0; p < parts; ++p) total += len[p];
+    return total == g->tm.text_bytes && gzip_crc_chain(reg, len, parts) == g->crc;
+}
+
+void rala_hip::gzip_piece_exchange_ms(rala_hip_ctx* ctx, float ms) { ctx->gzip_pieces.exchange_ms = ms; }
+
 void rala_hip::ingest::trace_gzip(const GzipStream& g, uint64_t windows, uint64_t window) {
     const rala_hip_gzip_timings& t = g.tm;
     char in[96] = "", members[160] = "one gzip member";
@@ -473,6 +778,27 @@ int rala_hip_gzip_find_members(rala_hip_ctx* ctx, const uint8_t* bytes, uint64_t
         if (header_off) header_off[k] = cands[k].header_off;
         if (deflate_off) deflate_off[k] = cands[k].deflate_bit / 8;
     }
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_pieces(const uint64_t* job_start_bit, uint64_t n_jobs, uint64_t deflate_off, uint64_t chunk_bytes, uint64_t n_chunks,
+                         uint32_t parts, uint64_t* first_job) {
+    if (!first_job || (!job_start_bit && n_jobs)) return RALA_HIP_EINVAL;
+    return gzip_pieces_split(job_start_bit, n_jobs, deflate_off, chunk_bytes, n_chunks, parts, first_job) ? RALA_HIP_OK : RALA_HIP_EINVAL;
+}
+
+int rala_hip_gzip_compose_windows(const uint16_t* out_windows, uint32_t parts, uint32_t part, uint16_t* in_window, int* valid) {
+    static_assert(kGzipNothing == RALA_HIP_GZIP_NOTHING, "the header names the code");
+    if (!out_windows || !in_window || !valid || part >= parts) return RALA_HIP_EINVAL;
+    bool ok = false;
+    gzip_compose_windows(out_windows, part, in_window, &ok);
+    *valid = ok ? 1 : 0;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_gzip_pieces_info(rala_hip_ctx* ctx, rala_hip_gzip_pieces_info* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->gzip_pieces;
     return RALA_HIP_OK;
 }
 

@@ -666,6 +666,20 @@ uint32_t gzip_crc_of_segments(const uint32_t* seg_crc, uint64_t text_n);        
 // the carry of the next window: the last gzip_ring_symbols() of (the carry in front of sym, then the window's text_n bytes at
 // text) as symbols, through tmp (that many symbols) to the front of sym
 void launch_gzip_carry(uint16_t* sym, const uint8_t* text, uint64_t text_n, uint16_t* tmp, hipStream_t s);
+// A PIECE of the stream (a rank of a sharded run, ingest_gzip.hip).  The find and the count over the chunks [c0, c1) alone, by the
+// kernels as they are: for c0 > 0 the launch begins one chunk earlier, whose block is no result - the find writes a value of
+// no meaning to starts[c0 - 1], the count expects kGzipNoStart there and gives spans[c].next counted from chunk c0 - 1.
+// starts, spans: the arrays of ALL n_chunks chunks (the count lands on the starts of the chunks behind c1 too).
+void launch_gzip_find_range(const uint8_t* comp, uint64_t end, uint64_t n_words, uint64_t deflate_off, uint64_t chunk_bytes, uint32_t c0, uint32_t c1,
+                            uint32_t false_sync, uint64_t* starts, hipStream_t s);
+void launch_gzip_count_range(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, uint32_t c0, uint32_t c1, GzipSpan* spans,
+                             hipStream_t s);
+// The piece's OUT-window: out[i], i < gzip_ring_symbols() = symbol own_n + i of (the ring of identity markers at sym, then the
+// own_n symbols of the piece's n_own own chunks, text_off[j] counted from the ring's first symbol, as launch_gzip_write left
+// them), every marker followed from chunk to chunk to a byte or to 0x8000 | its position in the ring; sym is not changed.
+// stats (4 words, zeroed by the caller): [0..1] the own symbols that end in the ring (64 bits), [2] the longest chase in hops.
+void launch_gzip_window_compose(const uint16_t* sym, const uint64_t* text_off, uint32_t n_own, uint64_t own_n, uint16_t* out, uint32_t* stats,
+                                uint32_t* flags, hipStream_t s);
 // (host) the CRC register (from zero, no final inversion) of text_n bytes from launch_gzip_resolve's segment registers
 uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n);
 // (host) the CRC32 of pieces laid end to end from each piece's register (from zero, no final inversion) and length

@@ -547,6 +547,10 @@ int rala_hip_mg_slice_cuts(const uint32_t* a_id, const uint32_t* b_id, uint64_t 
 // GPU) and the lines whose first byte follows a byte of their text; begin, end and emptiness of every rank's piece travel with
 // the same exchange, and every rank checks that the pieces are one chain from byte 0 to the file's end.  A file where they
 // are not, a member the inflater refuses on any rank, any other gzip file: *irregular = 8 on every rank.
+//
+// With the options "gzip_on_device" and "gzip_in_pieces" set on every rank's slice context a gzip file of ONE member that is not
+// BGZF is taken by the ranks together (stages.h: gzip_piece_*; include/rala_hip.h): four more exchanges in front of the one that
+// settles the cuts, every one made by every rank whatever happened to it locally.
 namespace {
 int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular);
 int set_overlaps_from_text(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read,
@@ -596,10 +600,63 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
         else file_n = (uint64_t)st.st_size;
     }
     inputs_dropped(cs);
-    if (rc == RALA_HIP_OK) {
+    cs->gzip_pieces = rala_hip_gzip_pieces_info();      // (of THIS call: zeros unless the file is taken together below)
+    // A single-member gzip file that is not BGZF, taken by the ranks together (options gzip_on_device and gzip_in_pieces, the same
+    // on every rank): four exchanges in front of the one below - who has what file, the chunks' starts, their spans, the
+    // out-windows.  A rank that fails in between makes the next exchange with its code, where every rank learns of it and
+    // returns; a refusal is computed from the exchanged words, the same on every rank.
+    uint64_t own_crc[2] = {0, 0};
+    bool gzip_pieces = false;
+    const bool together = cs->gzip_on_device && cs->gzip_in_pieces;
+    GzipPieceRun* run = nullptr;
+    struct Close {
+        rala_hip_ctx* ctx;
+        GzipPieceRun*& run;
+        ~Close() { gzip_piece_close(ctx, run); }
+    } close_run{cs, run};
+    if (together) {
+        const double tx0 = now_ms();
+        double in_steps = 0;
+        auto step = [&](int code, const char* what, double t) { in_steps += now_ms() - t; return from_ctx(mg, cs, code, what); };
+        uint64_t head[6] = {0, 0, 0, 0, 0, 0};
+        std::vector<uint64_t> all, words;
+        double t = now_ms();
+        if (rc == RALA_HIP_OK) rc = step(gzip_piece_open(cs, path, mhap, head, &run), "gzip in pieces", t);
+        rc = agree_with(mg, rc, "gzip in pieces: the file", 0, head, 6, all);
+        if (rc != RALA_HIP_OK) return rc;
+        gzip_pieces = true;
+        for (uint32_t p = 0; p < P; ++p) {
+            gzip_pieces = gzip_pieces && all[(size_t)p * 7 + 1] == 1;
+            for (int f = 1; f < 6; ++f) gzip_pieces = gzip_pieces && all[(size_t)p * 7 + 1 + f] == all[1 + f];
+        }
+        if (gzip_pieces) {
+            const uint32_t most = (uint32_t)gzip_piece_most_chunks(head[3], P);
+            t = now_ms();
+            rc = step(gzip_piece_find(cs, run, me, P, threads, words), "gzip in pieces: find", t);
+            rc = agree_with(mg, rc, "gzip in pieces: the chunks' starts", 0, words.data(), most, all);
+            if (rc != RALA_HIP_OK) return rc;
+            t = now_ms();
+            rc = step(gzip_piece_count(cs, run, all.data(), (size_t)most + 1, words), "gzip in pieces: count", t);
+            rc = agree_with(mg, rc, "gzip in pieces: the chunks' spans", 0, words.data(), 4 * most, all);
+            if (rc != RALA_HIP_OK) return rc;
+            bool chain = false;
+            t = now_ms();
+            rc = step(gzip_piece_write(cs, run, all.data(), (size_t)4 * most + 1, &chain, words), "gzip in pieces: write", t);
+            // (the chain is the same on every rank: so is this way out)
+            if (rc == RALA_HIP_OK && !chain) { *irregular = 8; return RALA_HIP_OK; }
+            rc = agree_with(mg, rc, "gzip in pieces: the out-windows", 0, words.data(), 8192, all);
+            if (rc != RALA_HIP_OK) return rc;
+            t = now_ms();
+            rc = step(gzip_piece_tokenise(cs, run, all.data(), 8193, check_lengths != 0, threads, 1u << 16, T, &R, own_crc), "gzip in pieces: tokenise", t);
+            piece[0] = piece[1] = 0; piece[2] = 0;
+            gzip_piece_exchange_ms(cs, (float)(now_ms() - tx0 - in_steps));
+        }
+    }
+    if (rc == RALA_HIP_OK && !gzip_pieces) {
         // (a plain file: bytes [n me / P, n (me + 1) / P); a compressed one is text like any other unless the option says otherwise)
         PartKinds take;
-        take.bgzf_pieces = take.refuse_other = cs->bgzf_in_pieces;
+        take.bgzf_pieces = cs->bgzf_in_pieces;
+        take.refuse_other = cs->bgzf_in_pieces || together;
         rc = from_ctx(mg, cs, overlap_tokenise_part(cs, path, me, P, take, check_lengths != 0, threads, 1u << 16, T, &R, piece, &in_pieces), "tokenise");
     }
     // what the cuts need of this rank's rows
@@ -624,14 +681,23 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
     }
     // one host exchange: {rows, first resolved row, end of the first run, query of the first / last resolved row, tokeniser's
     // flags, first length error; begin, end, emptiness of its piece of a BGZF file (bit 1 of the last: the file was taken so)}
-    const uint64_t mine[10] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad,
-                               piece[0], piece[1], piece[2] | (in_pieces ? 2u : 0u)};
+    // and, of a gzip file taken together, CRC register and length of the rank's own text
+    const uint64_t mine[12] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad,
+                               piece[0], piece[1], piece[2] | (in_pieces ? 2u : 0u), own_crc[0], own_crc[1]};
     std::vector<uint64_t> all;
-    rc = agree_with(mg, rc, "device ingest", 0, mine, 10, all);
+    rc = agree_with(mg, rc, "device ingest", 0, mine, 12, all);
     if (rc != RALA_HIP_OK) return rc;
-    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 11 + 1 + f]; };
+    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 13 + 1 + f]; };
     uint32_t flags = 0;
     for (uint32_t p = 0; p < P; ++p) flags |= (uint32_t)of(p, 5);
+    if (gzip_pieces) {
+        // every rank chains the same pairs: the text is the trailer's, or the file is refused on every rank - whatever the
+        // tokeniser made of a text that is not the file's (one context proves the text before it tokenises it)
+        std::vector<uint32_t> reg(P);
+        std::vector<uint64_t> len(P);
+        for (uint32_t p = 0; p < P; ++p) { reg[p] = (uint32_t)of(p, 10); len[p] = of(p, 11); }
+        if ((flags & 8) || !gzip_piece_proven(run, reg.data(), len.data(), P)) flags = 8;
+    }
     // the pieces of a BGZF file must be one chain from byte 0 to the file's end: the same verdict from the same words on every rank
     bool any_pieces = false;
     for (uint32_t p = 0; p < P; ++p) any_pieces = any_pieces || (of(p, 9) & 2) != 0;

@@ -32,7 +32,8 @@ SYMBOLS = (
     "rala_hip_find_repetitive_hills",
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
-    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members",
+    "rala_hip_gzip_pieces", "rala_hip_gzip_compose_windows", "rala_hip_get_gzip_pieces_info", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_bgzf_index_range", "rala_hip_bgzf_pieces_chain", "rala_hip_tokenise_sensitive", "rala_hip_mg_set_overlaps_from_mhap",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
@@ -95,6 +96,19 @@ class GzipTimings(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GzipPiecesInfo(ctypes.Structure):
+    """rala_hip_gzip_pieces_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("own_chunks", "own_jobs", "halo_jobs", "own_text_bytes", "window_markers")] + [
+        ("longest_chase", ctypes.c_uint32), ("compose_ms", ctypes.c_float), ("exchange_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+GZIP_WINDOW = 32768
+GZIP_NOTHING = 0x4000       # RALA_HIP_GZIP_NOTHING
 
 
 class LayoutInfo(ctypes.Structure):
@@ -240,6 +254,9 @@ def lib(build=True):
                                                   [u64, ctypes.POINTER(u64)] + [vp] * 3 + [ctypes.POINTER(GzipTimings), ctypes.POINTER(i32)])
         L.rala_hip_gzip_find_members.argtypes = [vp, vp, u64, u64, ctypes.POINTER(u64), vp, vp]
         L.rala_hip_get_gzip_members.argtypes = [vp, ctypes.POINTER(u64), u64, vp, vp, vp]
+        L.rala_hip_gzip_pieces.argtypes = [vp, u64, u64, u64, u64, u32, vp]
+        L.rala_hip_gzip_compose_windows.argtypes = [vp, u32, u32, vp, ctypes.POINTER(i32)]
+        L.rala_hip_get_gzip_pieces_info.argtypes = [vp, ctypes.POINTER(GzipPiecesInfo)]
         _lib = L
     return _lib
 
@@ -502,6 +519,11 @@ class Context:
     def gzip_timings(self):
         t = GzipTimings()
         self._check(self.L.rala_hip_get_gzip_timings(self.h, ctypes.byref(t)))
+        return t.as_dict()
+
+    def gzip_pieces_info(self):
+        t = GzipPiecesInfo()
+        self._check(self.L.rala_hip_get_gzip_pieces_info(self.h, ctypes.byref(t)))
         return t.as_dict()
 
     def gzip_members(self):
@@ -933,6 +955,25 @@ def gzip_chain(starts, end_bit, text, nxt, status, refuted, end, isize):
                                    ctypes.byref(tm), ctypes.byref(valid))
     assert rc == 0
     return (tuple(a[:n_jobs.value] for a in out) if valid.value else None), tm.as_dict()
+
+
+def gzip_pieces(job_start_bit, deflate_off, chunk_bytes, n_chunks, parts):
+    """rala_hip_gzip_pieces (no device): first_job[parts + 1] of the chain's split over the parts, or None where it is refused"""
+    bits = np.ascontiguousarray(job_start_bit, dtype=np.uint64)
+    first = np.zeros(parts + 1, dtype=np.uint64)
+    rc = lib().rala_hip_gzip_pieces(bits.ctypes.data, len(bits), deflate_off, chunk_bytes, n_chunks, parts, first.ctypes.data)
+    return [int(x) for x in first] if rc == 0 else None
+
+
+def gzip_compose_windows(out_windows, part):
+    """rala_hip_gzip_compose_windows (no device): (the window in front of `part`, valid) from the parts' out-windows, an array of
+    parts x 32768 symbols"""
+    w = np.ascontiguousarray(out_windows, dtype=np.uint16).reshape(-1, GZIP_WINDOW)
+    got, valid = np.zeros(GZIP_WINDOW, dtype=np.uint16), ctypes.c_int32(-1)
+    rc = lib().rala_hip_gzip_compose_windows(w.ctypes.data, len(w), part, got.ctypes.data, ctypes.byref(valid))
+    if rc != 0:
+        raise RalaHipError(rc, "rala_hip_gzip_compose_windows")
+    return got, valid.value
 
 
 def gzip_chain_members(chunks, cands, file_n, last_crc, last_isize):

@@ -149,13 +149,25 @@ extern "C" int rala_e2e_from_paf_ranks(const char* paf_path, const uint32_t* rea
             return r;
         });
     }
+    const std::string path(paf_path);
+    const bool mhap = rala::io::has_suffix(path, ".mhap") || rala::io::has_suffix(path, ".mhap.gz");
+    // (one look at the file for all ranks: what it finds must be the same on every one of them)
+    const bool ranks_gzip = rala::io::device_compressed_wanted() && rala::io::has_suffix(path, ".gz") && rala::io::device_gzip_wanted() &&
+                            !rala::io::device_gzip_members_wanted() && rala::io::sniff_compression(path) == 2;
     const auto t0 = clock::now();
     if (bad_rc == RALA_HIP_OK) {
         on_every_rank([&](uint32_t k) {
+            // (one gzip member that is not BGZF is taken by the ranks together: these two options decide which collectives the
+            // call below makes, so they are set first, from a value every rank shares, whatever becomes of the steps behind)
+            int r_opt = RALA_HIP_OK;
+            if (ranks_gzip) {
+                r_opt = rala_hip_set_option(rala_hip_mg_context(ranks[k]), "gzip_on_device", 1);
+                const int r_pieces = rala_hip_set_option(rala_hip_mg_context(ranks[k]), "gzip_in_pieces", 1);
+                if (r_opt == RALA_HIP_OK) r_opt = r_pieces;
+            }
             int r = rala_hip_set_name_table(rala_hip_mg_context(ranks[k]), table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
+            if (r == RALA_HIP_OK) r = r_opt;
             // (io::device_compressed_wanted(): a BGZF file in pieces, a .mhap file as MHAP - as Graph::initialize does)
-            const std::string path(paf_path);
-            const bool mhap = rala::io::has_suffix(path, ".mhap") || rala::io::has_suffix(path, ".mhap.gz");
             if (r == RALA_HIP_OK && rala::io::device_compressed_wanted() && rala::io::has_suffix(path, ".gz")) {
                 r = rala_hip_set_option(rala_hip_mg_context(ranks[k]), "bgzf_in_pieces", 1);
             }

@@ -377,8 +377,12 @@ void Graph::initialize() {
     // ... unless io::device_compressed_wanted() (RALA_DEVICE_COMPRESSED=1): then the ranks take a plain .mhap as they take a
     // .paf, and a .gz file that is BGZF in pieces - every rank the members whose header begins in its byte range (option
     // bgzf_in_pieces; a file whose pieces do not join, or any other gzip file, is irregular there and the host reader decides)
-    const bool ranks_compressed = !ranks_.empty() && io::device_compressed_wanted() &&
-                                  (gz ? io::sniff_compression(overlaps_path_) == 1 : mhap_text);
+    // ... and, where io::device_gzip_wanted() says so as well (RALA_DEVICE_GZIP=1), a .gz file of one gzip member that is not
+    // BGZF together (options gzip_on_device and gzip_in_pieces on every rank: the chunks' starts and spans and one window of
+    // 32 768 symbols per rank travel between them).  A file of several members (RALA_DEVICE_GZIP=2) stays the host reader's.
+    const int gz_kind = gz && !ranks_.empty() && io::device_compressed_wanted() ? io::sniff_compression(overlaps_path_) : 0;
+    const bool ranks_gzip = gz_kind == 2 && io::device_gzip_wanted() && !io::device_gzip_members_wanted();
+    const bool ranks_compressed = !ranks_.empty() && io::device_compressed_wanted() && (gz ? gz_kind == 1 || ranks_gzip : mhap_text);
     const bool device_ingest = (io::has_suffix(overlaps_path_, ".paf") || ((mhap_text || gz) && ranks_.empty()) || ranks_compressed) &&
                                !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
     // A single-member gzip file (gzip, pigz, `minimap2 | gzip`) is inflated on the device too where io::device_gzip_wanted()
@@ -431,7 +435,17 @@ void Graph::initialize() {
         for (uint32_t k = 0; k < P; ++k) {
             th.emplace_back([&, k]() {
                 rala_hip_mg* mg = ranks_[k];
+                // The options that decide WHICH collectives the call below makes come first and hang on nothing this rank
+                // alone can see (ranks_gzip is one value for the process; setting a known option cannot fail on a live
+                // context): a rank that fails in a step below must still make the same exchanges as the others.
+                int r_opt = RALA_HIP_OK;
+                if (ranks_gzip) {
+                    r_opt = rala_hip_set_option(rala_hip_mg_context(mg), "gzip_on_device", 1);
+                    const int r_pieces = rala_hip_set_option(rala_hip_mg_context(mg), "gzip_in_pieces", 1);
+                    if (r_opt == RALA_HIP_OK) r_opt = r_pieces;
+                }
                 int r = rala_hip_mg_set_reads(mg, read_len_.data(), read_len_.size());
+                if (r == RALA_HIP_OK) r = r_opt;
                 if (r == RALA_HIP_OK && device_names_) {
                     r = rala_hip_copy_name_table(rala_hip_mg_context(mg), ctx_);       // (the main context built it; device to device)
                 } else if (r == RALA_HIP_OK) {

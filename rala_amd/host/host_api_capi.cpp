@@ -135,6 +135,7 @@ struct PafOnDevice {
     rala_hip_ingest_timings tm = {};
     rala_hip_gzip_timings gz = {};
     std::vector<uint64_t> member_off, member_n;     // rala_hip_get_gzip_members of the call
+    std::vector<rala_hip_gzip_pieces_info> pieces;   // rala_hip_get_gzip_pieces_info of every rank (hp_text_device_ranks)
     std::vector<uint32_t> member_crc;
     int before_irregular = 0;       // what the file ingested first on the same context gave (hp_text_device_after)
     int64_t before_bad = -1;
@@ -328,6 +329,7 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
     for (auto& c : col) c.resize(world);
     std::vector<std::vector<uint8_t>> strand(world);
     std::vector<uint64_t> share(3 * (size_t)world, 0);
+    out->pieces.assign(world, rala_hip_gzip_pieces_info());
     if (out->rc == RALA_HIP_OK) {
         std::vector<std::thread> th;
         for (uint32_t k = 0; k < world; ++k) {
@@ -378,6 +380,7 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
                     }
                 }
                 slices[2 * k] = first; slices[2 * k + 1] = n;
+                (void)rala_hip_get_gzip_pieces_info(cs, &out->pieces[k]);
                 for (int c = 0; c < 7; ++c) col[c][k] = std::move(got[c]);
                 strand[k] = std::move(got_strand);
                 rc[k] = r;
@@ -433,6 +436,17 @@ uint64_t hp_paf_device_gzip_members(void* h, uint64_t cap, uint64_t* text_off, u
     const uint64_t n = o->member_off.size();
     for (uint64_t k = 0; k < n && cap >= n; ++k) { text_off[k] = o->member_off[k]; text_n[k] = o->member_n[k]; crc32[k] = o->member_crc[k]; }
     return n;
+}
+// rank k's piece of a gzip file the ranks took together (hp_text_device_ranks; rala_hip_get_gzip_pieces_info): info[0 .. 7] = own
+// chunks, own jobs, halo jobs, own text bytes, window markers, longest chase, compose us, exchange us; 0: no such rank
+int hp_paf_device_pieces_info(void* h, uint32_t k, int64_t* info) {
+    const auto* o = (const PafOnDevice*)h;
+    if (k >= o->pieces.size()) return 0;
+    const rala_hip_gzip_pieces_info& p = o->pieces[k];
+    info[0] = (int64_t)p.own_chunks; info[1] = (int64_t)p.own_jobs; info[2] = (int64_t)p.halo_jobs; info[3] = (int64_t)p.own_text_bytes;
+    info[4] = (int64_t)p.window_markers; info[5] = (int64_t)p.longest_chase;
+    info[6] = (int64_t)(p.compose_ms * 1000.0f); info[7] = (int64_t)(p.exchange_ms * 1000.0f);
+    return 1;
 }
 void hp_paf_device_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uint32_t* a_end, uint32_t* b_begin, uint32_t* b_end,
                         uint32_t* length, uint8_t* strand) {
