@@ -700,6 +700,56 @@ typedef struct rala_hip_layout_info {
 } rala_hip_layout_info;
 int rala_hip_get_layout_info(rala_hip_ctx* ctx, rala_hip_layout_info* out);
 
+/* ---- the layout of a round's components shared by the ranks of a sharded run --------------------------------------------------
+ * A step is a Jacobi step: every point's new position depends on the previous positions only, so any split of the POINTS over the
+ * ranks gives the bits of rala_hip_layout_batch.  What travels per step is 16 bytes per point against n_c pair terms per point.
+ *
+ * The split (no context, no device).  Units, in point order, component after component: a component of at most fused_max points
+ * is ONE unit of cost n_c^2 (one workgroup runs all its steps: it stays whole); a larger one is its tiles of 256 points, each of
+ * cost (points in the tile) * n_c; an empty component is no unit.  Part k ends behind the first unit at which the cost of the
+ * units up to and including it reaches ceil(total * (k + 1) / parts); the last part ends at N = comp_off[n_components].  Part k is
+ * the points [first_point[k], first_point[k + 1]) - first_point has parts + 1 entries, an empty part is legal - and cost[k]
+ * (parts entries, may be NULL) the cost of its units: at most ceil(total / parts) + the largest unit's cost.
+ * RALA_HIP_EINVAL: parts == 0, first_point or (with components) comp_off NULL, a comp_off that does not start at 0 or decreases,
+ * fused_max > 1024. */
+int rala_hip_layout_split(uint32_t n_components, const uint32_t* comp_off, uint32_t fused_max, uint32_t parts,
+                          uint32_t* first_point, uint64_t* cost);
+/* rala_hip_layout_batch by all ranks of a group together (collective: every rank calls it with the SAME inputs, as for
+ * rala_hip_mg_run; x and y are inputs here, the result goes to x_out / y_out, which may be x / y).  "layout_fused_max" is read
+ * from rala_hip_mg_context(mg) and must be equal on all ranks (compared in the call's one host exchange: ranks that differ all
+ * get RALA_HIP_EINVAL, the group stays usable).  The host checks are those of rala_hip_layout_batch, made before anything is
+ * enqueued or exchanged (RALA_HIP_EINVAL; the same inputs give the same verdict on every rank, so nobody waits for a rank that
+ * refused); no components, no points and iterations == 0 are valid, touch nothing and make no exchange.
+ * Every rank uploads the whole batch (positions as {x, y} pairs, offsets, partner lists, k, the tile table), takes part `rank`
+ * of rala_hip_layout_split over `world` parts, runs its fused components in one launch per size class and, per step, its range
+ * of the tile table (layout_shard_step_kernel) followed by ONE all-gather of the ranks' point ranges of the buffer just written
+ * (in place; the last one carries the fused results too; without any tile one gather behind the fused launches takes its
+ * place).  A rank whose x_out and y_out are both NULL takes part without a download.
+ * A device error or RALA_HIP_ENOMEM on one rank alone behaves as in rala_hip_mg_run: the rank aborts the group, every rank's
+ * call fails and the rank objects are to be destroyed.  RCCL: never run with a peer; tested with the in-process transport. */
+int rala_hip_mg_layout_batch(rala_hip_mg* mg, uint32_t n_components, const uint32_t* comp_off, const double* x, const double* y,
+                             double* x_out, double* y_out, const uint32_t* adj_off, const uint32_t* adj, const double* k,
+                             uint32_t iterations, double t, double dt);
+/* the same for n ranks of this process, one host thread per rank, joined before it returns: rank 0 downloads into the caller's
+ * x / y (in / out), the others pass NULL */
+int rala_hip_mg_layout_batch_threads(rala_hip_mg** ranks, uint32_t n, uint32_t n_components, const uint32_t* comp_off, double* x,
+                                     double* y, const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
+                                     double t, double dt);
+/* The rank's share of its last rala_hip_mg_layout_batch (zeros before the first; a refused call leaves the previous one's). */
+typedef struct rala_hip_mg_layout_info {
+    uint32_t first_point, end_point;                        /* the rank's points: [first_point, end_point) of the batch */
+    uint32_t components_fused_256, components_fused_1024;   /* its fused components per size class */
+    uint32_t step_tiles;        /* its tiles: workgroups of one of its step launches */
+    uint32_t launches;          /* kernel launches it enqueued */
+    uint32_t gathers;           /* all-gathers it took part in */
+    uint64_t cost;              /* its part's cost (rala_hip_layout_split) */
+    uint64_t total_cost;        /* all parts' */
+    uint64_t bytes_received;    /* positions of other ranks' points, all gathers */
+    float device_ms;            /* between two HIP events around its kernels, summed over the steps (without copies and gathers) */
+    float exchange_ms;          /* wall clock inside the gathers: waiting for the slowest rank included */
+} rala_hip_mg_layout_info;
+int rala_hip_mg_get_layout_info(rala_hip_mg* mg, rala_hip_mg_layout_info* out);
+
 /* ---- results (host buffers owned by the caller) --------------------------------------- */
 /* is_valid_overlap_ (src/graph.hpp:168), one byte per overlap */
 int rala_hip_get_valid(rala_hip_ctx* ctx, uint8_t* valid);

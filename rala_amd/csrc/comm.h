@@ -42,7 +42,8 @@ public:
                              size_t elem_bytes, hipStream_t s, bool own_part = true) = 0;
     // every rank contributes `bytes` bytes; recv = world * bytes
     virtual int all_gather(const void* send, void* recv, size_t bytes, hipStream_t s) = 0;
-    // rank k contributes counts[k] elements; recv holds them back to back in rank order
+    // rank k contributes counts[k] elements; recv holds them back to back in rank order.  In place: send may be the rank's
+    // own part of recv (recv + the counts in front of it), which then stays where it is
     virtual int all_gather_v(const void* send, void* recv, const uint64_t* counts, size_t elem_bytes, hipStream_t s) = 0;
     // in place over n uint32 values
     virtual int all_reduce_u32(uint32_t* buf, size_t n, ReduceOp op, hipStream_t s) = 0;

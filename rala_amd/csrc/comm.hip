@@ -372,7 +372,9 @@ public:
         size_t ro = 0;
         for (uint32_t p = 0; p < world_; ++p) {
             const size_t bytes = (size_t)counts[p] * elem_bytes;
-            if (bytes && !bad_ && !copy((char*)recv + ro, g_->ptr[p], bytes, p, s)) bad_ = true;
+            // (in place - send is the rank's own part of recv: that part is where it belongs)
+            const bool in_place = p == rank_ && (const char*)send == (char*)recv + ro;
+            if (bytes && !bad_ && !in_place && !copy((char*)recv + ro, g_->ptr[p], bytes, p, s)) bad_ = true;
             ro += bytes;
         }
         return finish(s);

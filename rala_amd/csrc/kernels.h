@@ -734,5 +734,13 @@ void launch_layout_fused(uint32_t block, uint32_t n_list, const uint32_t* list, 
 void launch_layout_batch_step(uint32_t n_tiles, const uint2* tiles, const uint32_t* comp_off, const double* x, const double* y,
                               double* x_out, double* y_out, const uint32_t* adj_off, const uint32_t* adj, const double* k,
                               double t, hipStream_t s);
+// The same arithmetic on positions that lie as double2 (layout_shard_kernels.hip; rala_hip_mg_layout_batch): one step of the
+// n_tiles tiles at `tiles` - a rank's range of the tile table - from buffer `cur` into `out` (the other buffer);
+// launch_layout_shard_fused: every component of list[] in one workgroup, all steps in the launch, `out` may be `in`.
+void launch_layout_shard_step(uint32_t n_tiles, const uint2* tiles, const uint32_t* comp_off, const double2* cur, double2* out,
+                              const uint32_t* adj_off, const uint32_t* adj, const double* k, double t, hipStream_t s);
+void launch_layout_shard_fused(uint32_t block, uint32_t n_list, const uint32_t* list, const uint32_t* comp_off,
+                               const double2* in, double2* out, const uint32_t* adj_off, const uint32_t* adj, const double* k,
+                               uint32_t iterations, double t, double dt, hipStream_t s);
 
 }  // namespace rala_hip

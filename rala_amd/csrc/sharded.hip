@@ -57,6 +57,7 @@ struct rala_hip_mg {
     DevBuf<uint8_t> d_bytes[2];
     rala_hip_mg_timings tm = {};
     hipEvent_t ev[8] = {};              // stage boundaries on cs->stream (timings without a wait)
+    LayoutShardState layout;            // rala_hip_mg_layout_batch: its buffers on cs's device, the rank's share of the last call
 };
 
 namespace {
@@ -472,6 +473,7 @@ void rala_hip_mg_destroy(rala_hip_mg* mg) {
     if (mg->cs) (void)hipStreamSynchronize(mg->cs->stream);
     if (mg->cl) (void)hipStreamSynchronize(mg->cl->stream);
     for (auto& e : mg->ev) if (e) (void)hipEventDestroy(e);
+    layout_shard_release(mg->layout);
     delete mg->comm;
     mg->d_send.release(); mg->d_recv.release(); mg->d_state_mine.release(); mg->d_state_all.release();
     if (mg->cl) rala_hip_destroy(mg->cl);
@@ -827,6 +829,82 @@ int rala_hip_mg_run_threads(rala_hip_mg** ranks, uint32_t n, const rala_hip_over
         if (pairs[k] != pairs[0]) { ranks[0]->err = "ranks disagree on the transitive reduction"; return RALA_HIP_EDEVICE; }
     }
     *n_pairs = pairs[0];
+    return RALA_HIP_OK;
+}
+
+// ---- the layout of a round's components, the points shared out over the ranks (layout_shard.hip has the steps) ----------------
+namespace {
+
+int layout_batch_all(rala_hip_mg* mg, const LayoutShardBatch& b, double* x_out, double* y_out) {
+    rala_hip_ctx* cs = mg->cs;
+    // what no rank could go on from is refused before anything is enqueued or exchanged: the same inputs, the same verdict
+    const char* why = "";
+    if (layout_shard_check(b, &why) != RALA_HIP_OK) {
+        mg->verdict_shared = true;
+        return mg_fail(mg, RALA_HIP_EINVAL, std::string("rala_hip_mg_layout_batch: ") + why);
+    }
+    const size_t N = b.n_components ? b.comp_off[b.n_components] : 0;
+    const rala_hip_mg_layout_info before = mg->layout.info;
+    int rc = from_ctx(mg, cs, layout_shard_prepare(cs, mg->layout, mg->rank, mg->world, b), "layout");
+    if (N == 0 || b.iterations == 0) {              // nothing to do, on every rank: no collective
+        mg->verdict_shared = true;
+        if (rc != RALA_HIP_OK) mg->layout.info = before;
+        return rc;
+    }
+    // one host exchange: a rank without memory for the batch is learned of here, and so are ranks whose split would differ
+    const uint64_t fused_max = (uint64_t)cs->layout_fused_max;
+    std::vector<uint64_t> all;
+    rc = agree_with(mg, rc, "layout", 0, &fused_max, 1, all);
+    for (uint32_t p = 0; p < mg->world && rc == RALA_HIP_OK; ++p) {
+        if (all[(size_t)p * 2 + 1] != all[1]) {
+            mg->verdict_shared = true;
+            rc = mg_fail(mg, RALA_HIP_EINVAL, "rala_hip_mg_layout_batch: rank " + std::to_string(p) + " disagrees on layout_fused_max");
+        }
+    }
+    if (rc == RALA_HIP_OK) rc = from_ctx(mg, cs, layout_shard_steps(cs, mg->comm, mg->layout, b, x_out, y_out), "layout");
+    if (rc != RALA_HIP_OK) {
+        mg->layout.info = before;
+        (void)hipStreamSynchronize(cs->stream);     // (the upload may still read the pinned block the next call fills)
+    }
+    return rc;
+}
+
+}  // namespace
+
+int rala_hip_mg_layout_batch(rala_hip_mg* mg, uint32_t n_components, const uint32_t* comp_off, const double* x, const double* y,
+                             double* x_out, double* y_out, const uint32_t* adj_off, const uint32_t* adj, const double* k,
+                             uint32_t iterations, double t, double dt) {
+    if (!mg) return RALA_HIP_EINVAL;
+    if (!mg->comm) return mg_fail(mg, RALA_HIP_EINVAL, "the rank has not joined its group (rala_hip_mg_join)");
+    mg->verdict_shared = false;
+    const LayoutShardBatch b = {n_components, comp_off, x, y, adj_off, adj, k, iterations, t, dt};
+    const int rc = layout_batch_all(mg, b, x_out, y_out);
+    // (a failure the others do not know of: they must not wait for this rank in the next gather)
+    if (rc != RALA_HIP_OK && !mg->verdict_shared) mg->comm->abort();
+    return rc;
+}
+
+int rala_hip_mg_layout_batch_threads(rala_hip_mg** ranks, uint32_t n, uint32_t n_components, const uint32_t* comp_off, double* x,
+                                     double* y, const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
+                                     double t, double dt) {
+    if (!ranks || n == 0) return RALA_HIP_EINVAL;
+    std::vector<int> rc(n, RALA_HIP_OK);
+    std::vector<std::thread> th;
+    // (every rank has read x and y before the first exchange; rank 0 writes them behind the last one)
+    for (uint32_t r = 0; r < n; ++r) {
+        th.emplace_back([&, r]() {
+            rc[r] = rala_hip_mg_layout_batch(ranks[r], n_components, comp_off, x, y, r == 0 ? x : nullptr, r == 0 ? y : nullptr, adj_off,
+                                             adj, k, iterations, t, dt);
+        });
+    }
+    for (auto& one : th) one.join();
+    for (uint32_t r = 0; r < n; ++r) if (rc[r] != RALA_HIP_OK) return rc[r];
+    return RALA_HIP_OK;
+}
+
+int rala_hip_mg_get_layout_info(rala_hip_mg* mg, rala_hip_mg_layout_info* out) {
+    if (!mg || !out) return RALA_HIP_EINVAL;
+    *out = mg->layout.info;
     return RALA_HIP_OK;
 }
 

@@ -94,6 +94,37 @@ bool gzip_piece_proven(const GzipPieceRun* g, const uint32_t* reg, const uint64_
 void gzip_piece_exchange_ms(rala_hip_ctx* ctx, float ms);
 void gzip_piece_close(rala_hip_ctx* ctx, GzipPieceRun* g);
 
+// rala_hip_mg_layout_batch (layout_shard.hip), as steps with the caller's one host exchange between the first two (sharded.hip
+// makes it: the status word and layout_fused_max):
+//   check     the host checks of rala_hip_layout_batch (no device); *why names what was refused
+//   prepare   the split for `world` parts, the rank's fused lists and tile range, the batch packed and its upload enqueued
+//             (nothing collective: a failure here travels with the exchange)
+//   steps     the fused launches, then per step the rank's tiles and one all-gather of the buffer just written; the download
+//             (x_out and y_out both null: none).  A failure in here is the rank's alone.
+struct LayoutShardBatch {
+    uint32_t n_components;
+    const uint32_t* comp_off;
+    const double *x, *y;
+    const uint32_t *adj_off, *adj;
+    const double* k;
+    uint32_t iterations;
+    double t, dt;
+};
+struct LayoutShardState {
+    DevBuf<unsigned char> d_block;
+    PinnedBuf<unsigned char> p_block;
+    hipEvent_t ev[2] = {};
+    rala_hip_mg_layout_info info = {};
+    // of the call under way (prepare -> steps)
+    std::vector<uint32_t> first_point;
+    uint32_t n_list256 = 0, n_list1024 = 0, tile_first = 0, n_tiles_all = 0;
+    size_t o_k = 0, o_comp = 0, o_adj_off = 0, o_adj = 0, o_l256 = 0, o_l1024 = 0, o_tiles = 0, o_pos1 = 0;
+};
+int layout_shard_check(const LayoutShardBatch& b, const char** why);
+int layout_shard_prepare(rala_hip_ctx* ctx, LayoutShardState& st, uint32_t rank, uint32_t world, const LayoutShardBatch& b);
+int layout_shard_steps(rala_hip_ctx* ctx, Comm* comm, LayoutShardState& st, const LayoutShardBatch& b, double* x_out, double* y_out);
+void layout_shard_release(LayoutShardState& st);
+
 // checksums of the rows cl holds (verify_kernels.hip) under the regions / liveness given per row (host arrays, cl->n_reads entries)
 int pile_row_digests(rala_hip_ctx* cl, const uint32_t* begin, const uint32_t* end, const uint8_t* alive, uint64_t* fnv, uint64_t* inside,
                      uint64_t* outside);

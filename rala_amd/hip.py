@@ -45,6 +45,7 @@ SYMBOLS = (
     "rala_hip_mg_set_overlaps", "rala_hip_mg_run", "rala_hip_mg_run_threads", "rala_hip_mg_context",
     "rala_hip_mg_owner_context",
     "rala_hip_mg_get_pile_data", "rala_hip_mg_get_pile_row_digests", "rala_hip_mg_get_timings",
+    "rala_hip_layout_split", "rala_hip_mg_layout_batch", "rala_hip_mg_layout_batch_threads", "rala_hip_mg_get_layout_info",
 )
 COMM_RCCL, COMM_LOCAL = 0, 1
 
@@ -117,6 +118,17 @@ class LayoutInfo(ctypes.Structure):
                 ("points_fused_256", ctypes.c_uint64), ("points_fused_1024", ctypes.c_uint64),
                 ("points_stepped", ctypes.c_uint64), ("step_tiles", ctypes.c_uint32), ("launches", ctypes.c_uint32),
                 ("device_ms", ctypes.c_float)]
+
+
+class MgLayoutInfo(ctypes.Structure):
+    """rala_hip_mg_layout_info"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("first_point", "end_point", "components_fused_256", "components_fused_1024",
+                                               "step_tiles", "launches", "gathers")] + [
+        (n, ctypes.c_uint64) for n in ("cost", "total_cost", "bytes_received")] + [
+        ("device_ms", ctypes.c_float), ("exchange_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class NameTableInfo(ctypes.Structure):
@@ -257,6 +269,10 @@ def lib(build=True):
         L.rala_hip_gzip_pieces.argtypes = [vp, u64, u64, u64, u64, u32, vp]
         L.rala_hip_gzip_compose_windows.argtypes = [vp, u32, u32, vp, ctypes.POINTER(i32)]
         L.rala_hip_get_gzip_pieces_info.argtypes = [vp, ctypes.POINTER(GzipPiecesInfo)]
+        L.rala_hip_layout_split.argtypes = [u32, vp, u32, u32, vp, vp]
+        L.rala_hip_mg_layout_batch.argtypes = [vp, u32] + [vp] * 8 + [u32, ctypes.c_double, ctypes.c_double]
+        L.rala_hip_mg_layout_batch_threads.argtypes = [vp, u32, u32] + [vp] * 6 + [u32, ctypes.c_double, ctypes.c_double]
+        L.rala_hip_mg_get_layout_info.argtypes = [vp, ctypes.POINTER(MgLayoutInfo)]
         _lib = L
     return _lib
 
@@ -877,6 +893,24 @@ class ShardedRank:
         self._check(self.L.rala_hip_mg_get_timings(self.h, ctypes.byref(t)))
         return t.as_dict()
 
+    def set_option(self, key, value):
+        """rala_hip_set_option on the rank's slice context (rala_hip_mg_context)"""
+        Context(_borrowed=self.L.rala_hip_mg_context(self.h)).set_option(key, value)
+
+    def layout_batch(self, comp_off, x, y, adj_off, adj, k, iterations, t, dt, out=None):
+        """this rank's call of the collective rala_hip_mg_layout_batch (every rank of the group makes it, each on a thread of
+        its own); out = (x_out, y_out) float64 arrays or None: no download.  Returns the call's code."""
+        arrays = _layout_arrays(comp_off, x, y, adj_off, adj, k)
+        ox, oy = (None, None) if out is None else (out[0].ctypes.data, out[1].ctypes.data)
+        return self.L.rala_hip_mg_layout_batch(self.h, arrays[0], arrays[1], arrays[2], arrays[3], ox, oy, arrays[4], arrays[5],
+                                               arrays[6], iterations, t, dt)
+
+    def layout_info(self):
+        """the rank's share of its last layout_batch / layout_ranks: point range, fused components, tiles, launches, gathers ..."""
+        info = MgLayoutInfo()
+        self._check(self.L.rala_hip_mg_get_layout_info(self.h, ctypes.byref(info)))
+        return info.as_dict()
+
 
 class LocalGroup:
     """rendezvous object of ranks that are threads of this process (RALA_HIP_COMM_LOCAL)"""
@@ -930,6 +964,47 @@ def run_ranks(ranks, sens_slices=None):
         msgs = [L.rala_hip_mg_last_error(r.h).decode() for r in ranks]
         raise RalaHipError(rc, " | ".join(m for m in msgs if m))
     return int(pairs.value)
+
+
+def _layout_arrays(comp_off, x, y, adj_off, adj, k):
+    """(n_components, comp_off, x, y, adj_off, adj, k, keep) as the layout calls take them; `keep` holds the converted arrays,
+    which must outlive the call"""
+    assert x.dtype == np.float64 and y.dtype == np.float64 and x.flags.c_contiguous and y.flags.c_contiguous
+    comp_off = np.ascontiguousarray(comp_off, dtype=np.uint32)
+    adj_off = np.ascontiguousarray(adj_off, dtype=np.uint32)
+    adj = np.ascontiguousarray(adj, dtype=np.uint32)
+    k = np.ascontiguousarray(k, dtype=np.float64)
+    n_components = max(len(comp_off) - 1, 0)
+    assert len(k) == n_components
+    return (n_components, comp_off.ctypes.data if len(comp_off) else None, x.ctypes.data, y.ctypes.data,
+            adj_off.ctypes.data if len(adj_off) else None, adj.ctypes.data if len(adj) else None, k.ctypes.data,
+            (comp_off, adj_off, adj, k))
+
+
+def layout_ranks(ranks, comp_off, x, y, adj_off, adj, k, iterations, t, dt):
+    """rala_hip_mg_layout_batch_threads: the layout steps of all components by all ranks of this process together, one host
+    thread per rank; x / y (float64) updated in place from rank 0's download"""
+    L = lib()
+    n = len(ranks)
+    arr = (ctypes.c_void_p * n)(*[r.h for r in ranks])
+    a = _layout_arrays(comp_off, x, y, adj_off, adj, k)
+    rc = L.rala_hip_mg_layout_batch_threads(arr, n, a[0], a[1], a[2], a[3], a[4], a[5], a[6], iterations, t, dt)
+    if rc != 0:
+        msgs = [L.rala_hip_mg_last_error(r.h).decode() for r in ranks]
+        raise RalaHipError(rc, " | ".join(m for m in msgs if m))
+
+
+def layout_split(comp_off, fused_max, parts, with_cost=True):
+    """rala_hip_layout_split (no device): (first_point[parts + 1], cost[parts]) of the split of a batch's points over the parts,
+    or None where it is refused"""
+    comp_off = np.ascontiguousarray(comp_off, dtype=np.uint32)
+    first = np.zeros(parts + 1, dtype=np.uint32)
+    cost = np.zeros(max(parts, 1), dtype=np.uint64)
+    rc = lib().rala_hip_layout_split(max(len(comp_off) - 1, 0), comp_off.ctypes.data if len(comp_off) else None, fused_max, parts,
+                                     first.ctypes.data, cost.ctypes.data if with_cost else None)
+    if rc != 0:
+        return None
+    return [int(v) for v in first], [int(v) for v in cost[:parts]]
 
 
 def crc32_chain(reg, length):

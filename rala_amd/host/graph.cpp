@@ -888,7 +888,31 @@ void Graph::postprocess() {
     StageTimer timer;
     // all components of the round in one call where io::layout_batch_wanted() (RALA_LAYOUT_BATCH=1), component after
     // component without it; the same weights either way
-    const int rc = io::layout_batch_wanted()
+    // ... and by all ranks of a run on several GPUs together where io::layout_ranks_wanted() (RALA_LAYOUT_RANKS=1)
+    const int rc = io::layout_ranks_wanted() && ranks_.size() > 1
+        ? graph_.postprocess_batched([&](uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
+                                         const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
+                                         double t, double dt) {
+              const int r = rala_hip_mg_layout_batch_threads(ranks_.data(), (uint32_t)ranks_.size(), n_components, comp_off, x, y,
+                                                             adj_off, adj, k, iterations, t, dt);
+              if (r != RALA_HIP_OK) {
+                  for (rala_hip_mg* mg : ranks_) {
+                      if (rala_hip_mg_last_error(mg)[0]) fprintf(stderr, "[rala::Graph::postprocess] error: %s!\n", rala_hip_mg_last_error(mg));
+                  }
+                  return r;
+              }
+              uint64_t largest = 0, total = 0;
+              for (rala_hip_mg* mg : ranks_) {
+                  rala_hip_mg_layout_info info;
+                  if (rala_hip_mg_get_layout_info(mg, &info) != RALA_HIP_OK) continue;
+                  largest = std::max<uint64_t>(largest, info.cost);
+                  total = info.total_cost;
+              }
+              fprintf(stderr, "[rala::Graph::postprocess] layout by %zu ranks: %u points, the largest share %.1f %% of the cost\n",
+                      ranks_.size(), n_components ? comp_off[n_components] : 0u, total ? 100.0 * (double)largest / (double)total : 0.0);
+              return r;
+          }, layout_seed_++)
+        : io::layout_batch_wanted()
         ? graph_.postprocess_batched([&](uint32_t n_components, const uint32_t* comp_off, double* x, double* y,
                                          const uint32_t* adj_off, const uint32_t* adj, const double* k, uint32_t iterations,
                                          double t, double dt) {

@@ -82,6 +82,11 @@ bool layout_batch_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool layout_ranks_wanted() {
+    const char* e = getenv("RALA_LAYOUT_RANKS");
+    return e ? atoi(e) != 0 : false;
+}
+
 bool device_compressed_wanted() {
     const char* e = getenv("RALA_DEVICE_COMPRESSED");
     return e ? atoi(e) != 0 : false;

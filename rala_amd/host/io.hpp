@@ -50,6 +50,10 @@ bool device_compressed_wanted();
  * rala_hip_layout per component?  RALA_LAYOUT_BATCH=1 says so; without it: no - the same weights either way; many components
  * gain a lot, one giant component loses 1 %, see README.md, "Layout of all components in one call" */
 bool layout_batch_wanted();
+/*! @brief in a run on several GPUs, do all ranks lay out the components of a round together, the points shared out by cost
+ * (rala_hip_mg_layout_batch_threads), instead of the graph's context alone?  RALA_LAYOUT_RANKS=1 says so; without it, or on one
+ * GPU: no - the same weights either way; scaling over real devices is unmeasured, see README.md, "Layout shared by the ranks" */
+bool layout_ranks_wanted();
 /*! @brief what a file is by its first 18 bytes: 0 text (or unreadable), 1 BGZF (what the host reader's BgzfSource recognises),
  * 2 any other gzip file */
 int sniff_compression(const std::string& path);
