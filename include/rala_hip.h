@@ -614,7 +614,8 @@ int rala_hip_mg_set_overlaps_from_mhap(rala_hip_mg* mg, const char* path, int ch
  * the final block's end: the chain's).  Anything else - on any rank - is *irregular = 8 on every rank with nothing set; a
  * failure of one rank alone (device memory for its piece: symbols and text, 3 bytes per byte of text, are held at once) is
  * learned by every rank in the next exchange: every rank's call fails, and the group stays usable.
- * Not taken so, as before: BGZF (option "bgzf_in_pieces"), files of several members, -s files (rala_hip_tokenise_sensitive).
+ * Not taken so, as before: BGZF (option "bgzf_in_pieces"), files of several members (unless "gzip_members" is set too, below); -s files
+ * have an entry of their own (rala_hip_mg_tokenise_sensitive, below).
  *
  * The split of a chain over the parts (no context, no device): job j begins at bit job_start_bit[j] (ascending) of a file whose
  * deflate bytes begin at deflate_off and are cut into n_chunks chunks of chunk_bytes; part k's jobs are
@@ -644,6 +645,62 @@ typedef struct rala_hip_gzip_pieces_info {
     float exchange_ms;              /* the four host exchanges, waiting for the slowest rank included */
 } rala_hip_gzip_pieces_info;
 int rala_hip_get_gzip_pieces_info(rala_hip_ctx* ctx, rala_hip_gzip_pieces_info* out);
+/* ---- a gzip file of SEVERAL members that is not BGZF, over the ranks ("gzip_members" beside the two options above) --------------
+ * cat part*.paf.gz, pigz -i.  With "gzip_on_device", "gzip_in_pieces" and "gzip_members" set on rala_hip_mg_context(mg) of EVERY
+ * rank, rala_hip_mg_set_overlaps_from_paf / _mhap take such a file together (one member included); "gzip_members" is compared in
+ * the first exchange, ranks that disagree on it all return RALA_HIP_EINVAL and the group stays usable.  Every rank finds the member
+ * headers of the whole file (the list is exact, the same everywhere), counts those whose deflate bytes begin in its own chunks
+ * from their first block as from a stream's first chunk, and the spans travel with the chunks'; every rank walks the same words
+ * (rala_hip_gzip_chain_members): the same jobs, members and verdict everywhere, and where a member begins is never guessed from
+ * a byte range.  Jobs are owned as before; a member's first job emits no markers and every later one carries its member's floor.
+ * The out-window's chase ends at the floor of the member its first symbol belongs to (a hop below it: nothing, flag 8); the
+ * window in front of a piece is composed as before and masked in front of the member the piece begins in
+ * (rala_hip_gzip_compose_windows_masked).  Every member is proven alone: ISIZE in the chain, CRC32 against ITS trailer - inside
+ * one rank's text by that rank, across ranks from at most two partial registers per rank that ride on the last exchange
+ * (rala_hip_gzip_members_proof).  Anything else is *irregular = 8 on every rank with nothing set.
+ * rala_hip_get_gzip_members on every rank's slice context gives the file's members, the same on every rank.
+ *
+ * The masked composition (no context, no device): reach[r], r < parts = the text bytes between the first byte of the member in
+ * which part r's text begins and part r's first byte, clamped to 32 768.  in_window = the window in front of `part` as
+ * rala_hip_gzip_compose_windows gives it with every entry more than reach[part] in front of the part RALA_HIP_GZIP_NOTHING;
+ * *before = the byte in front of the part from the UNMASKED window (lines straddle members), -1: the text begins with the part;
+ * *valid = 0: what rala_hip_gzip_compose_windows refuses, or an entry within reach[r] of a part r <= part that is no byte. */
+int rala_hip_gzip_compose_windows_masked(const uint16_t* out_windows, uint32_t parts, const uint64_t* reach, uint32_t part, uint16_t* in_window,
+                                         int* before, int* valid);
+/* The members' proof over parts (no context, no device).  Part p holds the text [part_begin[p], part_end[p]), the parts in order
+ * and back to back from 0 to the text's end.  A part owes: local_bad[p] = the first member that lies inside its text alone and is
+ * not its trailer's (~0: none); {head_reg, head_len}[p] = CRC register (from zero, no final inversion: rala_hip_crc32_chain's
+ * convention) and length of its first bytes where they belong to a member begun in front of it; {tail_reg, tail_len}[p] = the
+ * same of its last bytes where they belong to a member begun in it that goes on behind it; zeros where there is no such member.
+ * A member that spans parts is the chain of those registers in part order against member_crc32; an empty member's CRC32 is 0.
+ * *valid = 0 with *bad_member = the first member that fails (n_members: the parts are not the members' text). */
+int rala_hip_gzip_members_proof(const uint64_t* member_text_off, const uint64_t* member_text_n, const uint32_t* member_crc32, uint64_t n_members,
+                                const uint64_t* part_begin, const uint64_t* part_end, const uint32_t* head_reg, const uint64_t* head_len,
+                                const uint32_t* tail_reg, const uint64_t* tail_len, const uint64_t* local_bad, uint32_t parts, uint64_t* bad_member,
+                                int* valid);
+/* what the rank's piece saw of the members in the last such call on the slice context (zeros otherwise) */
+typedef struct rala_hip_gzip_member_pieces_info {
+    uint64_t own_candidates;        /* member headers whose deflate bytes begin in the rank's chunks: counted by it */
+    uint64_t members_begun;         /* members (not empty) whose first byte lies in its own text */
+    uint64_t member_ends;           /* members (not empty) whose last byte lies in its own text: where its range is cut for the proof */
+    uint32_t registers_sent;        /* partial CRC registers it gave for members that span ranks: 0 - 2 */
+    uint32_t floor_stops;           /* chases gzip_window_compose_members_kernel ended at a member's floor (each one refuses the file) */
+    float compose_ms;               /* that kernel and its copies */
+    float pad;
+} rala_hip_gzip_member_pieces_info;
+int rala_hip_get_gzip_member_pieces_info(rala_hip_ctx* ctx, rala_hip_gzip_member_pieces_info* out);
+/* The -s file of a sharded run through ONE collective (every rank calls it, with the same options on its slice context): rank k's
+ * share of the sensitive overlaps tokenised on its GPU into the buffers rala_hip_tokenise_sensitive uses - never into the primary
+ * overlaps' columns -, no length check.  format 0: PAF, 1: MHAP.  Plain text and BGZF: the rank's part as
+ * rala_hip_tokenise_sensitive(ctx, path, format, rank, world, ..) takes it, the BGZF pieces' begin, end and emptiness exchanged and
+ * joined on every rank - the caller has nothing to join.  A gzip file that is not BGZF, of one member ("gzip_on_device" +
+ * "gzip_in_pieces") or of several (+ "gzip_members"): taken together as rala_hip_mg_set_overlaps_from_paf takes it, without cuts -
+ * a rank's share is the lines whose first byte lies in its own text (any contiguous shares will do for rala_hip_mg_run).
+ * out: device pointers that stay the slice context's, for rala_hip_mg_run with "sensitive_in_device_memory"; compressed bytes,
+ * symbols and text are released before it returns.  *irregular (flag 8: a file that cannot be proven), a failure of any rank
+ * (RALA_HIP_ENOMEM there, RALA_HIP_EDEVICE elsewhere) and RALA_HIP_ETOOLARGE are every rank's verdict, and the group stays usable. */
+int rala_hip_mg_tokenise_sensitive(rala_hip_mg* mg, const char* path, int format, uint32_t threads, rala_hip_overlaps* out, uint64_t* n,
+                                   int* irregular);
 /* the rank's slice as it was set: file position of its record 0, records (the columns: rala_hip_get_overlap_columns on
  * rala_hip_mg_context(mg)) */
 int rala_hip_mg_get_slice(rala_hip_mg* mg, uint64_t* first, uint64_t* n);

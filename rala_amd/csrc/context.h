@@ -263,6 +263,7 @@ struct rala_hip_ctx {
     std::vector<rala_hip::GzipMember> gzip_members_last;
     rala_hip_gzip_timings gzip_tm = {};
     rala_hip_gzip_pieces_info gzip_pieces = {}; // the rank's piece of the last such ingest (rala_hip_get_gzip_pieces_info)
+    rala_hip_gzip_member_pieces_info gzip_member_pieces = {};   // ... of a file of several members (rala_hip_get_gzip_member_pieces_info)
     rala_hip::DevBuf<uint32_t> d_gzip_compose_stats;    // four words of gzip_window_compose_kernel's own
     // the sequence index (ingest_sequences.hip: rala_hip_index_sequences; sequence_kernels.hip): events, records, the names' arena
     int64_t debug_sequence_window = 0;          // tests: the window over the read file's text (0: as the overlap ingest's, 2 GiB at most)

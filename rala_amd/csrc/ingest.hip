@@ -268,7 +268,7 @@ int rala_hip::overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_
 // then the lines whose FIRST byte lies in the piece's own text tokenised - the rule of a plain file's byte ranges; the byte in
 // front of the own text is the last of the window in front of it, the line at text offset 0 is part 0's.
 int rala_hip::gzip_piece_tokenise(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, bool check_lengths, uint32_t threads,
-                                  size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t own[2]) {
+                                  size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t own[7]) {
     *out = PafRange();
     uint32_t flag = 0;
     int rc = gzip_piece_resolve(ctx, g, all, stride, &flag, own);

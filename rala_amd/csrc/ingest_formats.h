@@ -415,5 +415,104 @@ inline bool gzip_chain_members(const uint64_t* starts, const GzipSpan* spans, ui
     return true;
 }
 
+// ---- a gzip file of several members over the ranks of a sharded run (options gzip_in_pieces + gzip_members) -------------------
+// The window in front of a part whose text begins `reach[part]` bytes behind the first byte of the member it begins in (clamped
+// to 32 768): composed from the out-windows as gzip_compose_windows does - they are the TEXT's tail, whatever members it is made
+// of - and then masked: entries more than reach[part] in front of the part are nothing, a marker of that member has no
+// business there.  *before = the byte in front of the part's text from the UNMASKED window (whether the part's first byte
+// starts a line is a question about the text: lines straddle members), -1 where the file's text begins with the part.
+// *valid = false: what gzip_compose_windows refuses, or - for this part or one in front of it - an entry within reach that is
+// no byte (a member cannot have begun that far back where the text has not).
+// (The window of every part in front is composed again to check its reach: `part` + 1 compositions of 32 768 entries, O(P^2) over
+// the ranks of a run - a few ms at the rank counts a node has; a run of hundreds of ranks would keep the windows it has walked.)
+inline void gzip_compose_windows_masked(const uint16_t* out_windows, const uint64_t* reach, uint32_t part, uint16_t* in_window, int* before,
+                                        bool* valid) {
+    std::vector<uint16_t> w(kGzipWindow);
+    bool ok = true;
+    for (uint32_t r = 0; r <= part; ++r) {
+        bool v = false;
+        if (r < part && reach[r] == 0) continue;                                // (nothing to check in front of that part)
+        gzip_compose_windows(out_windows, r, w.data(), &v);
+        if (r == part) ok = ok && v;
+        const uint32_t keep = (uint32_t)std::min<uint64_t>(reach[r], kGzipWindow);
+        for (uint32_t i = kGzipWindow - keep; i < kGzipWindow; ++i) ok = ok && w[i] < 0x100;
+    }
+    *before = w[kGzipWindow - 1] < 0x100 ? (int)w[kGzipWindow - 1] : -1;
+    const uint32_t keep = (uint32_t)std::min<uint64_t>(reach[part], kGzipWindow);
+    for (uint32_t i = 0; i < kGzipWindow; ++i) in_window[i] = i < kGzipWindow - keep ? kGzipNothing : w[i];
+    *valid = ok;
+}
+
+// What part [a, b) of the text owes the proof of the members that are not its own alone: head_n bytes at a that belong to a
+// member begun in front of a (member *head_m), tail_n bytes up to b that belong to a member begun in [a, b) that goes on
+// behind b (member *tail_m).  A part that lies inside one member gives its whole text as the head.
+inline void gzip_part_owes(const GzipMember* members, uint64_t n_members, uint64_t a, uint64_t b, uint64_t* head_n, uint64_t* head_m, uint64_t* tail_n,
+                           uint64_t* tail_m) {
+    *head_n = *tail_n = 0;
+    *head_m = *tail_m = n_members;
+    for (uint64_t m = 0; m < n_members && a < b; ++m) {
+        const uint64_t lo = members[m].text_off, hi = lo + members[m].text_n;
+        if (lo < a && a < hi) { *head_n = std::min(b, hi) - a; *head_m = m; }
+        if (lo >= a && lo < b && b < hi) { *tail_n = b - lo; *tail_m = m; }
+    }
+}
+
+// Every member proven over the parts.  Part p holds the text [part_a[p], part_b[p]) - the parts in order, back to back from 0
+// to the text's end - and gives: local_bad[p], the first member that lies inside its text alone and whose CRC32 is not its
+// trailer's (~0: none); {head_reg, head_len} and {tail_reg, tail_len}, the CRC registers (from zero, no final inversion:
+// rala_hip_crc32_chain's convention) of what gzip_part_owes names, zeros where it names nothing.  A member that spans parts is
+// the chain of the tail of the part it begins in, the heads of the parts behind it, in part order, against ITS trailer; an
+// empty member's CRC32 is 0.  crc_chain: kernels.h's gzip_crc_chain.  false with *bad = the first member that fails (n_members: the parts are not the text's).
+inline bool gzip_members_proof(const GzipMember* members, uint64_t n_members, const uint64_t* part_a, const uint64_t* part_b, const uint32_t* head_reg,
+                               const uint64_t* head_len, const uint32_t* tail_reg, const uint64_t* tail_len, const uint64_t* local_bad, uint32_t parts,
+                               uint32_t (*crc_chain)(const uint32_t*, const uint64_t*, uint64_t), uint64_t* bad) {
+    *bad = n_members;
+    uint64_t total = 0;
+    for (uint64_t m = 0; m < n_members; ++m) {
+        if (members[m].text_off != total) return false;
+        total += members[m].text_n;
+    }
+    if (!parts || !n_members || part_a[0] != 0 || part_b[parts - 1] != total) return false;
+    for (uint32_t p = 0; p < parts; ++p) {
+        if (part_b[p] < part_a[p] || (p && part_a[p] != part_b[p - 1])) return false;
+    }
+    uint64_t first = n_members;
+    auto fails = [&](uint64_t m) { first = std::min(first, m); };
+    std::vector<uint64_t> want_head(parts), want_tail(parts), head_m(parts), tail_m(parts);
+    for (uint32_t p = 0; p < parts; ++p) {
+        gzip_part_owes(members, n_members, part_a[p], part_b[p], &want_head[p], &head_m[p], &want_tail[p], &tail_m[p]);
+        if (local_bad[p] != ~0ull) fails(std::min<uint64_t>(local_bad[p], n_members - 1));
+        // a register nobody owes, or one of another length: the member that holds the byte it claims to begin with
+        if (head_len[p] != want_head[p] || tail_len[p] != want_tail[p]) {
+            uint64_t m = head_len[p] != want_head[p] ? head_m[p] : tail_m[p];
+            const uint64_t at = head_len[p] != want_head[p] ? part_a[p] : (part_b[p] ? part_b[p] - 1 : 0);
+            for (uint64_t k = 0; m == n_members && k < n_members; ++k) {
+                if (members[k].text_n && members[k].text_off <= at && at < members[k].text_off + members[k].text_n) m = k;
+            }
+            fails(std::min<uint64_t>(m, n_members - 1));
+        }
+    }
+    for (uint64_t m = 0; m < n_members; ++m) {
+        const uint64_t lo = members[m].text_off, hi = lo + members[m].text_n;
+        if (lo == hi) {
+            if (members[m].crc != 0) fails(m);
+            continue;
+        }
+        std::vector<uint32_t> reg;
+        std::vector<uint64_t> len;
+        bool spans = false;
+        for (uint32_t p = 0; p < parts; ++p) {
+            if (tail_m[p] == m) { reg.push_back(tail_reg[p]); len.push_back(tail_len[p]); spans = true; }
+            if (head_m[p] == m) { reg.push_back(head_reg[p]); len.push_back(head_len[p]); spans = true; }
+        }
+        if (!spans) continue;                                       // (inside one part: local_bad's)
+        uint64_t sum = 0;
+        for (uint64_t l : len) sum += l;
+        if (sum != hi - lo || crc_chain(reg.data(), len.data(), reg.size()) != members[m].crc) fails(m);
+    }
+    *bad = first;
+    return first == n_members;
+}
+
 }  // namespace ingest
 }  // namespace rala_hip

@@ -380,7 +380,92 @@ struct rala_hip::GzipPieceRun {
     float ship_ms = 0;
     rala_hip_gzip_timings tm = {};
     rala_hip_gzip_pieces_info info = {};
+    // a file of several members (option gzip_members): the header candidates of the whole file and the part each one's deflate
+    // bytes begin in (the same on every rank), the most any part owns; behind the chain the members, every job's member floor
+    // and every part's first job
+    bool members_mode = false, cands_agree = true, cands_split = false;
+    std::vector<GzipMemberCand> cands;
+    std::vector<uint32_t> cand_part;
+    uint64_t most_cands = 0;
+    std::vector<GzipMember> members;
+    std::vector<uint64_t> job_floor, first_job;
+    float member_find_ms = 0;
+    rala_hip_gzip_member_pieces_info minfo = {};
 };
+
+namespace {
+// the part whose chunks hold the byte a candidate's deflate bytes begin at (the chunk gzip_count_members_kernel starts from)
+uint32_t part_of_bit(const GzipPieceRun* g, uint64_t bit) {
+    const uint64_t byte = bit / 8, c = std::min((byte - std::min(byte, g->deflate_off)) / g->chunk, g->n_chunks - 1);
+    uint32_t p = 0;
+    while (p + 1 < g->parts && c >= gzip_part_chunk(g->n_chunks, g->parts, p + 1)) ++p;
+    return p;
+}
+}  // namespace
+
+namespace {
+// Behind the resolve of a piece of a file of several members: the text [a, a + n_w) at `text`, its segments' registers in seg_crc.
+// Every member's share of the own text [a, b) gets its register - whole segments', and gzip_piece_crc_kernel's for the pieces a
+// member end or b cuts off a segment; a member that lies inside [a, b) is compared with its trailer here (own[6]: the first one
+// that differs), the head and the tail the piece owes members that span ranks go to own[2 .. 5].
+int piece_prove_members(rala_hip_ctx* ctx, GzipPieceRun* g, const uint8_t* text, const std::vector<uint32_t>& seg_crc, uint64_t own[7]) {
+    hipStream_t s = ctx->stream;
+    const uint64_t seg = gzip_segment_bytes(), a = g->a, b = g->b, n_w = g->n_w;
+    struct Item { uint64_t idx, len; bool piece; };
+    struct Share { size_t m, first, n; int kind; };                  // kind 0: inside, 1: head, 2: tail
+    std::vector<Item> items;
+    std::vector<Share> shares;
+    std::vector<GzipPiece> pieces;
+    for (size_t m = 0; m < g->members.size(); ++m) {
+        const GzipMember& mem = g->members[m];
+        const uint64_t m_end = mem.text_off + mem.text_n, lo = std::max(mem.text_off, a), hi = std::min(m_end, b);
+        if (lo >= hi) continue;
+        Share sh{m, items.size(), 0, mem.text_off < a ? 1 : (m_end > b ? 2 : 0)};
+        for (uint64_t p = lo; p < hi;) {
+            const uint64_t k = (p - a) / seg, seg_lo = a + k * seg, seg_hi = std::min(seg_lo + seg, a + n_w), q = std::min(hi, seg_hi);
+            if (p == seg_lo && q == seg_hi) {
+                items.push_back(Item{k, q - p, false});
+            } else {
+                items.push_back(Item{pieces.size(), q - p, true});
+                pieces.push_back(GzipPiece{p - a, (uint32_t)(q - p), 0});
+            }
+            p = q;
+        }
+        sh.n = items.size() - sh.first;
+        shares.push_back(sh);
+    }
+    std::vector<uint32_t> piece_crc(pieces.size());
+    if (!pieces.empty()) {
+        if (pieces.size() >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "too many member boundaries in one piece");
+        if (ctx->d_gzip_pieces.ensure(pieces.size() * sizeof(GzipPiece)) != hipSuccess || ctx->d_gzip_piece_crc.ensure(pieces.size()) != hipSuccess) {
+            return fail(ctx, RALA_HIP_ENOMEM, "device memory for the members' pieces");
+        }
+        HIPCHECK(hipMemcpyAsync(ctx->d_gzip_pieces.p, pieces.data(), pieces.size() * sizeof(GzipPiece), hipMemcpyHostToDevice, s));
+        launch_gzip_piece_crc(text, (const GzipPiece*)ctx->d_gzip_pieces.p, (uint32_t)pieces.size(), ctx->d_gzip_piece_crc.p, s);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(piece_crc.data(), ctx->d_gzip_piece_crc.p, pieces.size() * 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+    }
+    for (const Share& sh : shares) {
+        std::vector<uint32_t> reg(sh.n);
+        std::vector<uint64_t> len(sh.n);
+        uint64_t total = 0;
+        for (size_t i = 0; i < sh.n; ++i) {
+            const Item& it = items[sh.first + i];
+            reg[i] = it.piece ? piece_crc[it.idx] : seg_crc[it.idx];
+            total += len[i] = it.len;
+        }
+        if (sh.kind == 0) {
+            if (gzip_crc_chain(reg.data(), len.data(), sh.n) != g->members[sh.m].crc && own[6] == ~0ull) own[6] = sh.m;
+        } else {
+            own[sh.kind == 1 ? 2 : 4] = gzip_crc_register_chain(reg.data(), len.data(), sh.n);
+            own[sh.kind == 1 ? 3 : 5] = total;
+            ++g->minfo.registers_sent;
+        }
+    }
+    return RALA_HIP_OK;
+}
+}  // namespace
 
 uint64_t rala_hip::gzip_piece_most_chunks(uint64_t n_chunks, uint32_t parts) {
     uint64_t most = 0;
@@ -388,12 +473,16 @@ uint64_t rala_hip::gzip_piece_most_chunks(uint64_t n_chunks, uint32_t parts) {
     return most;
 }
 
-int rala_hip::gzip_piece_open(rala_hip_ctx* ctx, const char* path, bool mhap, uint64_t head[6], GzipPieceRun** run) {
-    for (int k = 0; k < 6; ++k) head[k] = 0;
+int rala_hip::gzip_piece_open(rala_hip_ctx* ctx, const char* path, bool mhap, uint64_t head[7], GzipPieceRun** run) {
+    for (int k = 0; k < 7; ++k) head[k] = 0;
+    head[6] = ctx->gzip_members ? 1 : 0;
     *run = nullptr;
     std::unique_ptr<GzipPieceRun> g(new GzipPieceRun());
     g->path = path;
+    g->members_mode = ctx->gzip_members;
     ctx->gzip_pieces = rala_hip_gzip_pieces_info();
+    ctx->gzip_member_pieces = rala_hip_gzip_member_pieces_info();
+    if (g->members_mode) ctx->gzip_members_last.clear();
     int rc = ingest_ready(ctx, mhap);
     if (rc != RALA_HIP_OK) return rc;
     rc = open_regular(ctx, path, g->file, &g->file_n);
@@ -425,17 +514,22 @@ void rala_hip::gzip_piece_close(rala_hip_ctx* ctx, GzipPieceRun* run) {
     ctx->d_gzip_spans.release();
     ctx->d_gzip_carry.release();
     ctx->d_gzip_compose_stats.release();
+    ctx->d_gzip_cands.release();
+    ctx->d_gzip_mspans.release();
+    ctx->d_gzip_tile.release();
     delete run;
 }
 
-// a. the file shipped, block starts found in the own chunks -> starts_out: `most` words, the own chunks' first
+// a. the file shipped, block starts found in the own chunks -> starts_out: `most` + 1 words, the own chunks' first, the last one
+// the member headers found in the whole file (option gzip_members; otherwise 0)
 int rala_hip::gzip_piece_find(rala_hip_ctx* ctx, GzipPieceRun* g, uint32_t part, uint32_t parts, uint32_t threads, std::vector<uint64_t>& starts_out) {
     g->part = part;
     g->parts = parts;
     g->c0 = gzip_part_chunk(g->n_chunks, parts, part);
     g->c1 = gzip_part_chunk(g->n_chunks, parts, part + 1);
     g->most = gzip_piece_most_chunks(g->n_chunks, parts);
-    starts_out.assign(g->most, kGzipNoStart);
+    starts_out.assign(g->most + 1, kGzipNoStart);
+    starts_out[g->most] = 0;
     hipStream_t s = ctx->stream;
     const uint64_t file_n = g->file_n;
     const double t0 = now_ms();
@@ -458,22 +552,57 @@ int rala_hip::gzip_piece_find(rala_hip_ctx* ctx, GzipPieceRun* g, uint32_t part,
     HIPCHECK(hipGetLastError());
     if (g->c1 > g->c0) HIPCHECK(hipMemcpyAsync(starts_out.data(), ctx->d_gzip_starts.p + g->c0, (g->c1 - g->c0) * 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
+    if (g->members_mode) {
+        // every rank over the whole file: the list is exact and ascending, the same everywhere without an exchange
+        const double tm0 = now_ms();
+        uint64_t n_cands = 0;
+        const int rc = gzip_member_find(ctx, ctx->d_bgzf_comp.p, file_n, &n_cands);
+        if (rc != RALA_HIP_OK) return rc;
+        if (g->n_chunks + n_cands >= 0x7FFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "too many member candidates for 32-bit span ids");
+        g->cands.resize(n_cands);
+        if (n_cands) HIPCHECK(hipMemcpy(g->cands.data(), ctx->d_gzip_cands.p, n_cands * sizeof(GzipMemberCand), hipMemcpyDeviceToHost));
+        ctx->d_gzip_tile.release();
+        starts_out[g->most] = n_cands;
+        g->member_find_ms = (float)(now_ms() - tm0);
+    }
     g->tm.find_ms = (float)(now_ms() - t1);
     g->info.own_chunks = g->c1 - g->c0;
     return RALA_HIP_OK;
 }
 
 // b. all: every part's `most` start words at all[p * stride + 1 ..]; the own chunks counted, each landing on the starts behind it
-// wherever they were found -> spans_out: 4 words per chunk {end_bit, text, next | status << 32, refuted}
+// wherever they were found -> spans_out: 4 words per chunk {end_bit, text, next | status << 32, refuted}; behind the `most` chunks
+// (option gzip_members) 4 words per member candidate whose deflate bytes begin in the own chunks, decoded from its first block as
+// from a stream's first chunk, padded to the most candidates any part owns (gzip_piece_span_words)
 int rala_hip::gzip_piece_count(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, std::vector<uint64_t>& spans_out) {
     hipStream_t s = ctx->stream;
-    spans_out.assign(4 * g->most, 0);
+    spans_out.assign(gzip_piece_span_words(g, all, stride), 0);
     g->starts.assign(g->n_chunks, kGzipNoStart);
     for (uint32_t p = 0; p < g->parts; ++p) {
         const uint64_t lo = gzip_part_chunk(g->n_chunks, g->parts, p), hi = gzip_part_chunk(g->n_chunks, g->parts, p + 1);
         for (uint64_t c = lo; c < hi; ++c) g->starts[c] = all[(size_t)p * stride + 1 + (c - lo)];
     }
     const double t0 = now_ms();
+    std::vector<GzipSpan> mspans;
+    if (g->members_mode && g->cands_agree) {
+        // the own candidates, against the starts as they are (the launch below blinds one of them)
+        std::vector<GzipMemberCand> own;
+        for (size_t k = 0; k < g->cands.size(); ++k) if (g->cand_part[k] == g->part) own.push_back(g->cands[k]);
+        g->minfo.own_candidates = own.size();
+        if (!own.empty()) {
+            if (ctx->d_gzip_cands.ensure((own.size() + 1) * sizeof(GzipMemberCand)) != hipSuccess || ctx->d_gzip_mspans.ensure((own.size() + 1) * sizeof(GzipSpan)) != hipSuccess) {
+                return fail(ctx, RALA_HIP_ENOMEM, "device memory for the member candidates");
+            }
+            mspans.resize(own.size());
+            HIPCHECK(hipMemcpyAsync(ctx->d_gzip_starts.p, g->starts.data(), g->n_chunks * 8, hipMemcpyHostToDevice, s));
+            HIPCHECK(hipMemcpyAsync(ctx->d_gzip_cands.p, own.data(), own.size() * sizeof(GzipMemberCand), hipMemcpyHostToDevice, s));
+            launch_gzip_count_members(ctx->d_bgzf_comp.p, g->end, ctx->d_gzip_starts.p, (uint32_t)g->n_chunks, (const GzipMemberCand*)ctx->d_gzip_cands.p,
+                                      (uint32_t)own.size(), g->deflate_off, g->chunk, (GzipSpan*)ctx->d_gzip_mspans.p, s);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpyAsync(mspans.data(), ctx->d_gzip_mspans.p, own.size() * sizeof(GzipSpan), hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+        }
+    }
     std::vector<uint64_t> dev(g->starts);
     if (g->c0) dev[g->c0 - 1] = kGzipNoStart;                  // (launch_gzip_count_range: the block in front of the own chunks decodes nothing)
     HIPCHECK(hipMemcpyAsync(ctx->d_gzip_starts.p, dev.data(), g->n_chunks * 8, hipMemcpyHostToDevice, s));
@@ -491,10 +620,35 @@ int rala_hip::gzip_piece_count(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_
         spans_out[4 * c + 2] = (uint64_t)(uint32_t)(sp.next + base) | (uint64_t)sp.status << 32;
         spans_out[4 * c + 3] = sp.refuted;
     }
+    for (size_t k = 0; k < mspans.size(); ++k) {
+        const GzipSpan& sp = mspans[k];
+        uint64_t* w = &spans_out[4 * (g->most + k)];
+        w[0] = sp.end_bit; w[1] = sp.text; w[2] = (uint64_t)sp.next | (uint64_t)sp.status << 32; w[3] = 0;
+    }
     g->tm.decode_ms = (float)(now_ms() - t0);
     ctx->d_gzip_starts.release();
     ctx->d_gzip_spans.release();
+    ctx->d_gzip_cands.release();
+    ctx->d_gzip_mspans.release();
     return RALA_HIP_OK;
+}
+
+// all: what the exchange of the starts gathered.  The words a part gives to the exchange of the spans: 4 per chunk of the most
+// any part owns and (option gzip_members) 4 per member candidate of the most any part owns - computed by every rank from the
+// list every rank found; ranks that did not find the same number of candidates (not the same file) count none: the chain
+// then refuses, on every rank.
+size_t rala_hip::gzip_piece_span_words(GzipPieceRun* g, const uint64_t* all, size_t stride) {
+    if (g->members_mode && !g->cands_split) {
+        g->cands_split = true;
+        for (uint32_t p = 0; p < g->parts; ++p) g->cands_agree = g->cands_agree && all[(size_t)p * stride + 1 + g->most] == g->cands.size();
+        std::vector<uint64_t> owned(g->parts, 0);
+        g->cand_part.resize(g->cands.size());
+        for (size_t k = 0; k < g->cands.size(); ++k) ++owned[g->cand_part[k] = part_of_bit(g, g->cands[k].deflate_bit)];
+        g->most_cands = 0;
+        for (uint64_t n : owned) g->most_cands = std::max(g->most_cands, n);
+        if (!g->cands_agree) g->most_cands = 0;
+    }
+    return 4 * (size_t)(g->most + g->most_cands);
 }
 
 // c - e. all: every part's span words; the chain (the same on every rank; *valid = false: refused, nothing else was done), the
@@ -512,12 +666,36 @@ int rala_hip::gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_
             spans[c] = GzipSpan{w[0], w[1], (uint32_t)w[2], (uint32_t)(w[2] >> 32), (uint32_t)w[3], 0};
         }
     }
-    if (!gzip_chain_from_spans(g->starts.data(), spans.data(), g->n_chunks, g->end, g->isize, g->chain, &g->tm)) return RALA_HIP_OK;
+    if (g->members_mode) {
+        // every rank walks the same words: the same jobs, `first` flags, members and verdict everywhere - where a member begins
+        // is the chain's to say (the trailer in front of its header), never a rank's byte range
+        if (!g->cands_agree) return RALA_HIP_OK;
+        std::vector<GzipSpan> mspans(g->cands.size());
+        std::vector<uint64_t> seen(g->parts, 0);
+        for (size_t k = 0; k < g->cands.size(); ++k) {
+            const uint32_t p = g->cand_part[k];
+            const uint64_t* w = all + (size_t)p * stride + 1 + 4 * (g->most + seen[p]++);
+            mspans[k] = GzipSpan{w[0], w[1], (uint32_t)w[2], (uint32_t)(w[2] >> 32), 0, 0};
+        }
+        if (!gzip_chain_members(g->starts.data(), spans.data(), g->n_chunks, g->cands.data(), mspans.data(), g->cands.size(), g->file_n, g->crc, g->isize,
+                                g->chain, g->members, &g->tm)) {
+            return RALA_HIP_OK;
+        }
+    } else {
+        if (!gzip_chain_from_spans(g->starts.data(), spans.data(), g->n_chunks, g->end, g->isize, g->chain, &g->tm)) return RALA_HIP_OK;
+        g->members.assign(1, GzipMember{0, g->tm.text_bytes, g->end, g->crc, 0});
+    }
     const size_t n_jobs = g->chain.size();
-    std::vector<uint64_t> start_bit(n_jobs), first_job(g->parts + 1);
+    std::vector<uint64_t> start_bit(n_jobs);
+    std::vector<uint64_t>& first_job = g->first_job;
+    first_job.assign(g->parts + 1, 0);
     for (size_t j = 0; j < n_jobs; ++j) start_bit[j] = g->chain[j].start_bit;
     if (!gzip_pieces_split(start_bit.data(), n_jobs, g->deflate_off, g->chunk, g->n_chunks, g->parts, first_job.data())) return RALA_HIP_OK;
     *valid = true;
+    // where the text of every job's member begins
+    g->job_floor.resize(n_jobs);
+    for (size_t j = 0; j < n_jobs; ++j) g->job_floor[j] = j == 0 || g->chain[j].first ? g->chain[j].text_off : g->job_floor[j - 1];
+    if (g->members_mode) ctx->gzip_members_last = g->members;
     const uint64_t text_n = g->tm.text_bytes;
     auto off_of = [&](size_t j) { return j < n_jobs ? g->chain[j].text_off : text_n; };
     g->j0 = first_job[g->part];
@@ -536,7 +714,9 @@ int rala_hip::gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_
     std::vector<uint64_t> text_off(jobs.size() + 1, ring), floors(jobs.size() + 1, 0);
     for (size_t j = 0; j < jobs.size(); ++j) {
         text_off[j] = jobs[j].text_off = ring + (jobs[j].text_off - g->a);
-        floors[j] = ring >= g->a ? ring - g->a : 0;             // (where the file's text begins, in the launch's positions)
+        // where the text of the job's member begins, in the launch's positions (one member: where the file's text does)
+        const uint64_t f = g->job_floor[g->j0 + j];
+        floors[j] = f + ring >= g->a ? f + ring - g->a : 0;
     }
     const uint64_t n_seg = (g->n_w + gzip_segment_bytes() - 1) / gzip_segment_bytes();
     if (n_seg >= 0xFFFFFFF0ull) return fail(ctx, RALA_HIP_ETOOLARGE, "text too large for 32-bit segment ids");
@@ -563,8 +743,14 @@ int rala_hip::gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_
     // the out-window, taken at b
     uint32_t stats[4] = {0, 0, 0, 0};
     HIPCHECK(hipMemsetAsync(ctx->d_gzip_compose_stats.p, 0, 16, s));
-    launch_gzip_window_compose(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)(g->j1 - g->j0), own_n, ctx->d_gzip_carry.p, ctx->d_gzip_compose_stats.p,
-                               ctx->d_bgzf_flag.p, s);
+    if (g->members_mode) {
+        // (a chase ends at the floor of the member its first symbol belongs to)
+        launch_gzip_window_compose_members(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, ctx->d_gzip_floor.p, (uint32_t)(g->j1 - g->j0), own_n, ctx->d_gzip_carry.p,
+                                           ctx->d_gzip_compose_stats.p, ctx->d_bgzf_flag.p, s);
+    } else {
+        launch_gzip_window_compose(ctx->d_gzip_sym.p, ctx->d_gzip_off.p, (uint32_t)(g->j1 - g->j0), own_n, ctx->d_gzip_carry.p, ctx->d_gzip_compose_stats.p,
+                                   ctx->d_bgzf_flag.p, s);
+    }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(window_out.data(), ctx->d_gzip_carry.p, ring * 2, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(stats, ctx->d_gzip_compose_stats.p, 16, hipMemcpyDeviceToHost, s));
@@ -572,25 +758,52 @@ int rala_hip::gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_
     g->info.window_markers = (uint64_t)stats[0] | (uint64_t)stats[1] << 32;
     g->info.longest_chase = stats[2];
     g->info.compose_ms = (float)(now_ms() - t1);
+    if (g->members_mode) {
+        g->minfo.floor_stops = stats[3];
+        g->minfo.compose_ms = g->info.compose_ms;
+        for (const GzipMember& m : g->members) {
+            const uint64_t hi = m.text_off + m.text_n;
+            g->minfo.members_begun += m.text_n != 0 && m.text_off >= g->a && m.text_off < g->b;
+            g->minfo.member_ends += m.text_n != 0 && hi > g->a && hi <= g->b;
+        }
+    }
     return RALA_HIP_OK;
 }
 
 // f - g. all: every part's out-window; the window in front of the piece composed and uploaded as the carry, windows and resolve
 // as for a window of a walk: the text [a, a + n_w) to ctx->d_gzip_text + 16 with the byte in front of it ('\n' in front of the
 // file's first) and newlines behind it; *flag: the inflater's.  own[0 .. 1] = CRC register and length of the own text [a, b).
-int rala_hip::gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, uint32_t* flag, uint64_t own[2]) {
+// Option gzip_members: the window is masked in front of the member the piece begins in (gzip_compose_windows_masked), every
+// member that lies inside the own text is proven here, and own[2 .. 6] = {head register, head length, tail register, tail
+// length, the first such member that failed or ~0}: what the piece owes the members that span ranks (gzip_part_owes);
+// own[0 .. 1] stay zero.
+int rala_hip::gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, uint32_t* flag, uint64_t own[7]) {
     hipStream_t s = ctx->stream;
     const uint64_t ring = gzip_ring_symbols(), seg = gzip_segment_bytes();
     *flag = 0;
-    own[0] = own[1] = 0;
+    for (int k = 0; k < 6; ++k) own[k] = 0;
+    own[6] = ~0ull;
     std::vector<uint16_t> windows((size_t)g->parts * ring), carry(ring);
     for (uint32_t p = 0; p < g->parts; ++p) memcpy(windows.data() + (size_t)p * ring, all + (size_t)p * stride + 1, ring * 2);
     bool valid = false;
-    gzip_compose_windows(windows.data(), g->part, carry.data(), &valid);
+    uint8_t before = '\n';
+    if (g->members_mode) {
+        // every part's reach: the text between the first byte of the member its text begins in and its own first byte
+        const size_t n_all = g->chain.size();
+        std::vector<uint64_t> reach(g->parts, 0);
+        for (uint32_t p = 0; p < g->parts; ++p) {
+            const size_t j = g->first_job[p];
+            if (j < n_all) reach[p] = std::min<uint64_t>(g->chain[j].text_off - g->job_floor[j], ring);
+        }
+        int in_front = -1;
+        gzip_compose_windows_masked(windows.data(), reach.data(), g->part, carry.data(), &in_front, &valid);
+        if (g->a && in_front >= 0) before = (uint8_t)in_front;
+    } else {
+        gzip_compose_windows(windows.data(), g->part, carry.data(), &valid);
+        if (g->a && carry[ring - 1] < 0x100) before = (uint8_t)carry[ring - 1];
+    }
     // (a window that is not the text's tail: refused here - and by the rank whose match it was, whose resolve meets no byte)
     if (!valid) *flag = 8;
-    uint8_t before = '\n';
-    if (g->a && carry[ring - 1] < 0x100) before = (uint8_t)carry[ring - 1];
     for (uint32_t i = 0; i < ring; ++i) if (carry[i] >= 0x100) carry[i] = 0x8000;
     const uint64_t own_n = g->b - g->a, n_w = g->n_w, n_seg = (n_w + seg - 1) / seg;
     const uint32_t n_jobs = (uint32_t)(g->j2 - g->j0);
@@ -608,6 +821,28 @@ int rala_hip::gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint6
     HIPCHECK(hipMemcpyAsync(&kernel_flag, ctx->d_bgzf_flag.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     *flag |= kernel_flag;
+    if (g->members_mode) {
+        if (!*flag) { const int rc = piece_prove_members(ctx, g, text, seg_crc, own); if (rc != RALA_HIP_OK) return rc; }
+        g->tm.resolve_ms = (float)(now_ms() - t0);
+        ctx->d_gzip_sym.release();
+        ctx->d_gzip_carry.release();
+        ctx->gzip_tm = g->tm;
+        ctx->gzip_pieces = g->info;
+        ctx->gzip_member_pieces = g->minfo;
+        if (trace_on()) {
+            fprintf(stderr, "[trace] device inflate: part %u of %u of %lu gzip members (%lu header candidates found in %.2f ms, %lu counted here): chunks "
+                    "[%lu, %lu) of %lu, jobs [%lu, %lu) and %lu for the halo, text [%lu, %lu) of %lu; %lu members begin and %lu end in it, %u registers "
+                    "for those that span ranks; %lu own symbols through the window in front (longest chase %u hops, %u stopped at a member's floor), "
+                    "compose %.2f ms; find %.2f ms, decode %.2f ms, resolve %.2f ms, the file shipped in %.1f ms\n", g->part, g->parts,
+                    (unsigned long)g->members.size(), (unsigned long)g->cands.size(), g->member_find_ms, (unsigned long)g->minfo.own_candidates,
+                    (unsigned long)g->c0, (unsigned long)g->c1, (unsigned long)g->n_chunks, (unsigned long)g->j0, (unsigned long)g->j1,
+                    (unsigned long)(g->j2 - g->j1), (unsigned long)g->a, (unsigned long)g->b, (unsigned long)g->tm.text_bytes,
+                    (unsigned long)g->minfo.members_begun, (unsigned long)g->minfo.member_ends, g->minfo.registers_sent,
+                    (unsigned long)g->info.window_markers, g->info.longest_chase, g->minfo.floor_stops, g->info.compose_ms, g->tm.find_ms, g->tm.decode_ms,
+                    g->tm.resolve_ms, g->ship_ms);
+        }
+        return RALA_HIP_OK;
+    }
     // the own text's register: the whole segments' and, where b cuts one, that segment's front by gzip_piece_crc_kernel
     std::vector<uint32_t> reg;
     std::vector<uint64_t> len;
@@ -658,6 +893,29 @@ bool rala_hip::gzip_piece_proven(const GzipPieceRun* g, const uint32_t* reg, con
     uint64_t total = 0;
     for (uint32_t p = 0; p < parts; ++p) total += len[p];
     return total == g->tm.text_bytes && gzip_crc_chain(reg, len, parts) == g->crc;
+}
+
+bool rala_hip::gzip_piece_members(const GzipPieceRun* g) { return g->members_mode; }
+
+// Option gzip_members.  all: what the last exchange gathered, part p's {head register, head length, tail register, tail length,
+// locally failed member} at all[p * stride + at ..]: every member is its trailer's - those inside one rank's text by that rank's
+// word, those that span ranks by the ranks' registers chained in rank order; the same verdict from the same words everywhere.
+bool rala_hip::gzip_piece_members_proven(const GzipPieceRun* g, const uint64_t* all, size_t stride, size_t at) {
+    const uint32_t P = g->parts;
+    if (g->first_job.size() != (size_t)P + 1 || g->members.empty()) return false;
+    std::vector<uint64_t> a(P), b(P), head_len(P), tail_len(P), bad_here(P);
+    std::vector<uint32_t> head_reg(P), tail_reg(P);
+    const size_t n_jobs = g->chain.size();
+    auto off_of = [&](size_t j) { return j < n_jobs ? g->chain[j].text_off : g->tm.text_bytes; };
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint64_t* w = all + (size_t)p * stride + at;
+        a[p] = off_of(g->first_job[p]);
+        b[p] = off_of(g->first_job[p + 1]);
+        head_reg[p] = (uint32_t)w[0]; head_len[p] = w[1]; tail_reg[p] = (uint32_t)w[2]; tail_len[p] = w[3]; bad_here[p] = w[4];
+    }
+    uint64_t bad = 0;
+    return gzip_members_proof(g->members.data(), g->members.size(), a.data(), b.data(), head_reg.data(), head_len.data(), tail_reg.data(), tail_len.data(),
+                              bad_here.data(), P, gzip_crc_chain, &bad);
 }
 
 void rala_hip::gzip_piece_exchange_ms(rala_hip_ctx* ctx, float ms) { ctx->gzip_pieces.exchange_ms = ms; }
@@ -793,6 +1051,36 @@ int rala_hip_gzip_compose_windows(const uint16_t* out_windows, uint32_t parts, u
     bool ok = false;
     gzip_compose_windows(out_windows, part, in_window, &ok);
     *valid = ok ? 1 : 0;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_compose_windows_masked(const uint16_t* out_windows, uint32_t parts, const uint64_t* reach, uint32_t part, uint16_t* in_window,
+                                         int* before, int* valid) {
+    if (!out_windows || !reach || !in_window || !before || !valid || part >= parts) return RALA_HIP_EINVAL;
+    bool ok = false;
+    gzip_compose_windows_masked(out_windows, reach, part, in_window, before, &ok);
+    *valid = ok ? 1 : 0;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_gzip_members_proof(const uint64_t* member_text_off, const uint64_t* member_text_n, const uint32_t* member_crc32, uint64_t n_members,
+                                const uint64_t* part_begin, const uint64_t* part_end, const uint32_t* head_reg, const uint64_t* head_len,
+                                const uint32_t* tail_reg, const uint64_t* tail_len, const uint64_t* local_bad, uint32_t parts, uint64_t* bad_member,
+                                int* valid) {
+    if (!member_text_off || !member_text_n || !member_crc32 || !n_members || !part_begin || !part_end || !head_reg || !head_len || !tail_reg || !tail_len ||
+        !local_bad || !parts || !bad_member || !valid) {
+        return RALA_HIP_EINVAL;
+    }
+    std::vector<GzipMember> members(n_members);
+    for (uint64_t m = 0; m < n_members; ++m) members[m] = GzipMember{member_text_off[m], member_text_n[m], 0, member_crc32[m], 0};
+    *valid = gzip_members_proof(members.data(), n_members, part_begin, part_end, head_reg, head_len, tail_reg, tail_len, local_bad, parts, gzip_crc_chain,
+                                bad_member) ? 1 : 0;
+    return RALA_HIP_OK;
+}
+
+int rala_hip_get_gzip_member_pieces_info(rala_hip_ctx* ctx, rala_hip_gzip_member_pieces_info* out) {
+    if (!ctx || !out) return RALA_HIP_EINVAL;
+    *out = ctx->gzip_member_pieces;
     return RALA_HIP_OK;
 }
 

@@ -680,6 +680,15 @@ void launch_gzip_count_range(const uint8_t* comp, uint64_t end, const uint64_t* 
 // stats (4 words, zeroed by the caller): [0..1] the own symbols that end in the ring (64 bits), [2] the longest chase in hops.
 void launch_gzip_window_compose(const uint16_t* sym, const uint64_t* text_off, uint32_t n_own, uint64_t own_n, uint16_t* out, uint32_t* stats,
                                 uint32_t* flags, hipStream_t s);
+// A piece of a file of SEVERAL members.  The count of member candidates alone: mspans[k], k < n_cands, from cands[k]'s first block
+// as launch_gzip_count gives it beside the chunks (starts: all n_chunks chunks', spans' next counted from chunk 0).
+void launch_gzip_count_members(const uint8_t* comp, uint64_t end, const uint64_t* starts, uint32_t n_chunks, const GzipMemberCand* cands,
+                                uint32_t n_cands, uint64_t deflate_off, uint64_t chunk_bytes, GzipSpan* mspans, hipStream_t s);
+// launch_gzip_window_compose with mfloor[j], j < n_own: where the member of own chunk j begins, in the positions text_off[] counts
+// in (a member that began in front of the ring: 0).  A chase that lands below the floor of the member its first symbol belongs to
+// ends as nothing: 0x8000 in the out-window, flags |= 8, counted in stats[3].
+void launch_gzip_window_compose_members(const uint16_t* sym, const uint64_t* text_off, const uint64_t* mfloor, uint32_t n_own, uint64_t own_n,
+                                        uint16_t* out, uint32_t* stats, uint32_t* flags, hipStream_t s);
 // (host) the CRC register (from zero, no final inversion) of text_n bytes from launch_gzip_resolve's segment registers
 uint32_t gzip_crc_register(const uint32_t* seg_crc, uint64_t text_n);
 // (host) the CRC32 of pieces laid end to end from each piece's register (from zero, no final inversion) and length

@@ -552,7 +552,8 @@ int rala_hip_mg_slice_cuts(const uint32_t* a_id, const uint32_t* b_id, uint64_t 
 //
 // With the options "gzip_on_device" and "gzip_in_pieces" set on every rank's slice context a gzip file of ONE member that is not
 // BGZF is taken by the ranks together (stages.h: gzip_piece_*; include/rala_hip.h): four more exchanges in front of the one that
-// settles the cuts, every one made by every rank whatever happened to it locally.
+// settles the cuts, every one made by every rank whatever happened to it locally.  With "gzip_members" beside them (the same
+// on every rank: compared in the first exchange, RALA_HIP_EINVAL on every rank otherwise) so is a file of SEVERAL members.
 namespace {
 int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular);
 int set_overlaps_from_text(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read,
@@ -579,6 +580,134 @@ int rala_hip_mg_set_overlaps_from_mhap(rala_hip_mg* mg, const char* path, int ch
     return set_overlaps_from_text(mg, path, true, check_lengths, threads, length_error_read, irregular);
 }
 namespace {
+// The FRONT of a collective ingest, shared by the primary file's entry (ingest_paf) and the -s file's
+// (rala_hip_mg_tokenise_sensitive): the rank's part of the file tokenised into T's columns, whatever kind of file it is.
+// A gzip file that is not BGZF, taken by the ranks together (options gzip_on_device and gzip_in_pieces, the same on every rank;
+// with gzip_members a file of several members): four exchanges - who has what file, the chunks' starts, their spans, the
+// out-windows - and between them the steps roll call, find, count, chain, write, out-window, resolve, tokenise (stages.h:
+// gzip_piece_*).  A rank that fails in between makes the next exchange with its code, where every rank learns of it and
+// returns; a refusal is computed from the exchanged words, the same on every rank.  Any other file: overlap_tokenise_part with
+// `take`.  *leave: the caller returns what this returned at once (a verdict every rank shares, *irregular set where it is a
+// refusal); otherwise the caller makes its last exchange with the code returned and F's words, and front_verdict judges them.
+struct IngestFront {
+    PafRange R;
+    uint64_t file_n = 0;
+    uint64_t piece[3] = {0, 0, 1};
+    bool in_pieces = false, gzip_pieces = false;
+    uint64_t own_crc[7] = {0, 0, 0, 0, 0, 0, ~0ull};
+};
+struct CloseRun {
+    rala_hip_ctx* ctx;
+    GzipPieceRun*& run;
+    ~CloseRun() { gzip_piece_close(ctx, run); }
+};
+int ingest_front(rala_hip_mg* mg, int rc, const char* path, bool mhap, bool check_lengths, uint32_t threads, size_t extra_rows, const PafTarget& T,
+                 PartKinds take, GzipPieceRun*& run, IngestFront& F, int* irregular, bool* leave) {
+    rala_hip_ctx* cs = mg->cs;
+    const uint32_t P = mg->world, me = mg->rank;
+    *leave = true;
+    if (rc == RALA_HIP_OK) {
+        struct stat st;
+        if (stat(path, &st) != 0) rc = mg_fail(mg, RALA_HIP_EINVAL, std::string("cannot open ") + path);
+        else if (!S_ISREG(st.st_mode)) rc = mg_fail(mg, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
+        else F.file_n = (uint64_t)st.st_size;
+    }
+    cs->gzip_pieces = rala_hip_gzip_pieces_info();      // (of THIS call: zeros unless the file is taken together below)
+    const bool together = cs->gzip_on_device && cs->gzip_in_pieces;
+    if (together) {
+        const double tx0 = now_ms();
+        double in_steps = 0;
+        auto step = [&](int code, const char* what, double t) { in_steps += now_ms() - t; return from_ctx(mg, cs, code, what); };
+        uint64_t head[7] = {0, 0, 0, 0, 0, 0, cs->gzip_members ? 1u : 0u};
+        std::vector<uint64_t> all, words;
+        double t = now_ms();
+        if (rc == RALA_HIP_OK) rc = step(gzip_piece_open(cs, path, mhap, head, &run), "gzip in pieces", t);
+        rc = agree_with(mg, rc, "gzip in pieces: the file", 0, head, 7, all);
+        if (rc != RALA_HIP_OK) return rc;
+        // (options are the collective's contract: ranks that would walk different protocols from here on all leave instead)
+        for (uint32_t p = 0; p < P; ++p) {
+            if (all[(size_t)p * 8 + 7] != all[7]) {
+                mg->verdict_shared = true;
+                return mg_fail(mg, RALA_HIP_EINVAL, "gzip in pieces: rank " + std::to_string(p) + " disagrees on the option gzip_members");
+            }
+        }
+        F.gzip_pieces = true;
+        for (uint32_t p = 0; p < P; ++p) {
+            F.gzip_pieces = F.gzip_pieces && all[(size_t)p * 8 + 1] == 1;
+            for (int f = 1; f < 6; ++f) F.gzip_pieces = F.gzip_pieces && all[(size_t)p * 8 + 1 + f] == all[1 + f];
+        }
+        if (F.gzip_pieces) {
+            const uint32_t most = (uint32_t)gzip_piece_most_chunks(head[3], P);
+            t = now_ms();
+            rc = step(gzip_piece_find(cs, run, me, P, threads, words), "gzip in pieces: find", t);
+            words.resize((size_t)most + 1, 0);               // (a rank that failed in front of the step gives zeros)
+            rc = agree_with(mg, rc, "gzip in pieces: the chunks' starts", 0, words.data(), most + 1, all);
+            if (rc != RALA_HIP_OK) return rc;
+            const size_t span_words = gzip_piece_span_words(run, all.data(), (size_t)most + 2);
+            t = now_ms();
+            rc = step(gzip_piece_count(cs, run, all.data(), (size_t)most + 2, words), "gzip in pieces: count", t);
+            words.resize(span_words, 0);
+            rc = agree_with(mg, rc, "gzip in pieces: the chunks' spans", 0, words.data(), (uint32_t)span_words, all);
+            if (rc != RALA_HIP_OK) return rc;
+            bool chain = false;
+            t = now_ms();
+            rc = step(gzip_piece_write(cs, run, all.data(), span_words + 1, &chain, words), "gzip in pieces: write", t);
+            // (the chain is the same on every rank: so is this way out)
+            if (rc == RALA_HIP_OK && !chain) { *irregular = 8; return RALA_HIP_OK; }
+            rc = agree_with(mg, rc, "gzip in pieces: the out-windows", 0, words.data(), 8192, all);
+            if (rc != RALA_HIP_OK) return rc;
+            t = now_ms();
+            rc = step(gzip_piece_tokenise(cs, run, all.data(), 8193, check_lengths, threads, extra_rows, T, &F.R, F.own_crc), "gzip in pieces: tokenise", t);
+            F.piece[0] = F.piece[1] = 0; F.piece[2] = 0;
+            gzip_piece_exchange_ms(cs, (float)(now_ms() - tx0 - in_steps));
+        }
+    }
+    *leave = false;
+    if (rc == RALA_HIP_OK && !F.gzip_pieces) {
+        // (a plain file: bytes [n me / P, n (me + 1) / P); a compressed one is text like any other unless the options say otherwise)
+        take.refuse_other = take.refuse_other || together;
+        rc = from_ctx(mg, cs, overlap_tokenise_part(cs, path, me, P, take, check_lengths, threads, extra_rows, T, &F.R, F.piece, &F.in_pieces), "tokenise");
+    }
+    return rc;
+}
+
+// The front's verdict from the words of every rank's last exchange - rank p's at all[p * stride + 1 ..]: the tokeniser's flags at
+// at_flags, begin / end / emptiness of its BGZF piece at at_piece (bit 1 of the last: the file was taken so), the seven words of
+// F.own_crc at at_own - the same on every rank: 0, or the flags that refuse the file (8: a gzip file that is not proven, BGZF
+// pieces that are not one chain from byte 0 to the file's end).
+uint32_t front_verdict(rala_hip_mg* mg, const IngestFront& F, const GzipPieceRun* run, const std::vector<uint64_t>& all, size_t stride, uint32_t at_flags,
+                       uint32_t at_piece, uint32_t at_own) {
+    const uint32_t P = mg->world;
+    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * stride + 1 + f]; };
+    uint32_t flags = 0;
+    for (uint32_t p = 0; p < P; ++p) flags |= (uint32_t)of(p, at_flags);
+    if (F.gzip_pieces && gzip_piece_members(run)) {
+        // every member proven alone from the same words on every rank, before anybody looks at the tokeniser's flags
+        if ((flags & 8) || !gzip_piece_members_proven(run, all.data(), stride, 1 + at_own + 2)) flags = 8;
+        if (flags) mg->cs->gzip_members_last.clear();              // (nothing set: no member list either)
+    } else if (F.gzip_pieces) {
+        // every rank chains the same pairs: the text is the trailer's, or the file is refused on every rank - whatever the
+        // tokeniser made of a text that is not the file's (one context proves the text before it tokenises it)
+        std::vector<uint32_t> reg(P);
+        std::vector<uint64_t> len(P);
+        for (uint32_t p = 0; p < P; ++p) { reg[p] = (uint32_t)of(p, at_own); len[p] = of(p, at_own + 1); }
+        if ((flags & 8) || !gzip_piece_proven(run, reg.data(), len.data(), P)) flags = 8;
+    }
+    // the pieces of a BGZF file must be one chain from byte 0 to the file's end: the same verdict from the same words on every rank
+    bool any_pieces = false;
+    for (uint32_t p = 0; p < P; ++p) any_pieces = any_pieces || (of(p, at_piece + 2) & 2) != 0;
+    if (any_pieces && !flags) {
+        std::vector<ingest::BgzfPiece> pieces(P);
+        bool all_pieces = true;
+        for (uint32_t p = 0; p < P; ++p) {
+            pieces[p].begin = of(p, at_piece); pieces[p].end = of(p, at_piece + 1); pieces[p].empty = (uint32_t)(of(p, at_piece + 2) & 1);
+            all_pieces = all_pieces && (of(p, at_piece + 2) & 2) != 0;
+        }
+        if (!all_pieces || !ingest::bgzf_pieces_chain(pieces.data(), P, F.file_n)) flags = 8;
+    }
+    return flags;
+}
+
 int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, uint32_t threads, int64_t* length_error_read, int* irregular) {
     rala_hip_ctx* cs = mg->cs;
     const uint32_t P = mg->world, me = mg->rank;
@@ -591,76 +720,21 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
     for (int k = 0; k < 7; ++k) T.col[k] = &cs->d_paf_col[k];
     T.strand = &cs->d_paf_strand;
     T.mhap = mhap;
-    PafRange R;
-    uint64_t file_n = 0;
-    uint64_t piece[3] = {0, 0, 1};
-    bool in_pieces = false;
-    if (rc == RALA_HIP_OK) {
-        struct stat st;
-        if (stat(path, &st) != 0) rc = mg_fail(mg, RALA_HIP_EINVAL, std::string("cannot open ") + path);
-        else if (!S_ISREG(st.st_mode)) rc = mg_fail(mg, RALA_HIP_ENOTAFILE, std::string("not a regular file: ") + path);
-        else file_n = (uint64_t)st.st_size;
-    }
     inputs_dropped(cs);
-    cs->gzip_pieces = rala_hip_gzip_pieces_info();      // (of THIS call: zeros unless the file is taken together below)
-    // A single-member gzip file that is not BGZF, taken by the ranks together (options gzip_on_device and gzip_in_pieces, the same
-    // on every rank): four exchanges in front of the one below - who has what file, the chunks' starts, their spans, the
-    // out-windows.  A rank that fails in between makes the next exchange with its code, where every rank learns of it and
-    // returns; a refusal is computed from the exchanged words, the same on every rank.
-    uint64_t own_crc[2] = {0, 0};
-    bool gzip_pieces = false;
-    const bool together = cs->gzip_on_device && cs->gzip_in_pieces;
+    IngestFront F;
     GzipPieceRun* run = nullptr;
-    struct Close {
-        rala_hip_ctx* ctx;
-        GzipPieceRun*& run;
-        ~Close() { gzip_piece_close(ctx, run); }
-    } close_run{cs, run};
-    if (together) {
-        const double tx0 = now_ms();
-        double in_steps = 0;
-        auto step = [&](int code, const char* what, double t) { in_steps += now_ms() - t; return from_ctx(mg, cs, code, what); };
-        uint64_t head[6] = {0, 0, 0, 0, 0, 0};
-        std::vector<uint64_t> all, words;
-        double t = now_ms();
-        if (rc == RALA_HIP_OK) rc = step(gzip_piece_open(cs, path, mhap, head, &run), "gzip in pieces", t);
-        rc = agree_with(mg, rc, "gzip in pieces: the file", 0, head, 6, all);
-        if (rc != RALA_HIP_OK) return rc;
-        gzip_pieces = true;
-        for (uint32_t p = 0; p < P; ++p) {
-            gzip_pieces = gzip_pieces && all[(size_t)p * 7 + 1] == 1;
-            for (int f = 1; f < 6; ++f) gzip_pieces = gzip_pieces && all[(size_t)p * 7 + 1 + f] == all[1 + f];
-        }
-        if (gzip_pieces) {
-            const uint32_t most = (uint32_t)gzip_piece_most_chunks(head[3], P);
-            t = now_ms();
-            rc = step(gzip_piece_find(cs, run, me, P, threads, words), "gzip in pieces: find", t);
-            rc = agree_with(mg, rc, "gzip in pieces: the chunks' starts", 0, words.data(), most, all);
-            if (rc != RALA_HIP_OK) return rc;
-            t = now_ms();
-            rc = step(gzip_piece_count(cs, run, all.data(), (size_t)most + 1, words), "gzip in pieces: count", t);
-            rc = agree_with(mg, rc, "gzip in pieces: the chunks' spans", 0, words.data(), 4 * most, all);
-            if (rc != RALA_HIP_OK) return rc;
-            bool chain = false;
-            t = now_ms();
-            rc = step(gzip_piece_write(cs, run, all.data(), (size_t)4 * most + 1, &chain, words), "gzip in pieces: write", t);
-            // (the chain is the same on every rank: so is this way out)
-            if (rc == RALA_HIP_OK && !chain) { *irregular = 8; return RALA_HIP_OK; }
-            rc = agree_with(mg, rc, "gzip in pieces: the out-windows", 0, words.data(), 8192, all);
-            if (rc != RALA_HIP_OK) return rc;
-            t = now_ms();
-            rc = step(gzip_piece_tokenise(cs, run, all.data(), 8193, check_lengths != 0, threads, 1u << 16, T, &R, own_crc), "gzip in pieces: tokenise", t);
-            piece[0] = piece[1] = 0; piece[2] = 0;
-            gzip_piece_exchange_ms(cs, (float)(now_ms() - tx0 - in_steps));
-        }
-    }
-    if (rc == RALA_HIP_OK && !gzip_pieces) {
-        // (a plain file: bytes [n me / P, n (me + 1) / P); a compressed one is text like any other unless the option says otherwise)
+    CloseRun close_run{cs, run};
+    {
         PartKinds take;
-        take.bgzf_pieces = cs->bgzf_in_pieces;
-        take.refuse_other = cs->bgzf_in_pieces || together;
-        rc = from_ctx(mg, cs, overlap_tokenise_part(cs, path, me, P, take, check_lengths != 0, threads, 1u << 16, T, &R, piece, &in_pieces), "tokenise");
+        take.bgzf_pieces = take.refuse_other = cs->bgzf_in_pieces;
+        bool leave = false;
+        rc = ingest_front(mg, rc, path, mhap, check_lengths != 0, threads, 1u << 16, T, take, run, F, irregular, &leave);
+        if (leave) return rc;
     }
+    const PafRange& R = F.R;
+    const uint64_t* const piece = F.piece;
+    const uint64_t* const own_crc = F.own_crc;
+    const bool in_pieces = F.in_pieces;
     // what the cuts need of this rank's rows
     uint32_t ends[5] = {kNoRow, 0, 0, kNoRow, kNoRow};
     const uint32_t n_mine = (uint32_t)R.n_lines;
@@ -684,34 +758,16 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
     // one host exchange: {rows, first resolved row, end of the first run, query of the first / last resolved row, tokeniser's
     // flags, first length error; begin, end, emptiness of its piece of a BGZF file (bit 1 of the last: the file was taken so)}
     // and, of a gzip file taken together, CRC register and length of the rank's own text
-    const uint64_t mine[12] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad,
-                               piece[0], piece[1], piece[2] | (in_pieces ? 2u : 0u), own_crc[0], own_crc[1]};
+    // (of several members: what it owes the members that span ranks - head and tail register with their lengths - and the first
+    // member inside its own text that is not its trailer's)
+    const uint64_t mine[17] = {n_mine, ends[0] == kNoRow ? n_mine : ends[0], ends[2], ends[3], ends[4], R.flags, R.first_bad,
+                               piece[0], piece[1], piece[2] | (in_pieces ? 2u : 0u), own_crc[0], own_crc[1],
+                               own_crc[2], own_crc[3], own_crc[4], own_crc[5], own_crc[6]};
     std::vector<uint64_t> all;
-    rc = agree_with(mg, rc, "device ingest", 0, mine, 12, all);
+    rc = agree_with(mg, rc, "device ingest", 0, mine, 17, all);
     if (rc != RALA_HIP_OK) return rc;
-    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 13 + 1 + f]; };
-    uint32_t flags = 0;
-    for (uint32_t p = 0; p < P; ++p) flags |= (uint32_t)of(p, 5);
-    if (gzip_pieces) {
-        // every rank chains the same pairs: the text is the trailer's, or the file is refused on every rank - whatever the
-        // tokeniser made of a text that is not the file's (one context proves the text before it tokenises it)
-        std::vector<uint32_t> reg(P);
-        std::vector<uint64_t> len(P);
-        for (uint32_t p = 0; p < P; ++p) { reg[p] = (uint32_t)of(p, 10); len[p] = of(p, 11); }
-        if ((flags & 8) || !gzip_piece_proven(run, reg.data(), len.data(), P)) flags = 8;
-    }
-    // the pieces of a BGZF file must be one chain from byte 0 to the file's end: the same verdict from the same words on every rank
-    bool any_pieces = false;
-    for (uint32_t p = 0; p < P; ++p) any_pieces = any_pieces || (of(p, 9) & 2) != 0;
-    if (any_pieces && !flags) {
-        std::vector<ingest::BgzfPiece> pieces(P);
-        bool all_pieces = true;
-        for (uint32_t p = 0; p < P; ++p) {
-            pieces[p].begin = of(p, 7); pieces[p].end = of(p, 8); pieces[p].empty = (uint32_t)(of(p, 9) & 1);
-            all_pieces = all_pieces && (of(p, 9) & 2) != 0;
-        }
-        if (!all_pieces || !ingest::bgzf_pieces_chain(pieces.data(), P, file_n)) flags = 8;
-    }
+    auto of = [&](uint32_t p, uint32_t f) { return all[(size_t)p * 18 + 1 + f]; };
+    const uint32_t flags = front_verdict(mg, F, run, all, 18, 5, 7, 10);
     if (flags) { *irregular = (int)flags; return RALA_HIP_OK; }
     for (uint32_t p = 0; p < P; ++p) {
         if (of(p, 6) != ~0ull) { *length_error_read = (int64_t)(of(p, 6) & 0xFFFFFFFFull); return RALA_HIP_OK; }   // (file order: the lowest rank's)
@@ -769,7 +825,60 @@ int ingest_paf(rala_hip_mg* mg, const char* path, bool mhap, int check_lengths, 
     dev.length = cs->d_paf_col[6].p + off; dev.strand = cs->d_paf_strand.p + off;
     return rala_hip_mg_set_overlaps(mg, &dev, final_rows[me], first_pos[me], RALA_HIP_MEM_DEVICE);
 }
+
+// The -s file of a sharded run (collective): the front above into the buffers rala_hip_tokenise_sensitive uses, never into the
+// primary overlaps' columns - no length check, no cuts (any contiguous shares will do), a rank's share the lines whose first byte
+// lies in its part.  One exchange behind the front: {rows, tokeniser's flags, the BGZF piece, the gzip piece's words}.
+int tokenise_sensitive(rala_hip_mg* mg, const char* path, bool mhap, uint32_t threads, rala_hip_overlaps* out, uint64_t* n, int* irregular) {
+    rala_hip_ctx* cs = mg->cs;
+    const uint32_t P = mg->world;
+    int rc = RALA_HIP_OK;
+    if (hipSetDevice(mg->device) != hipSuccess) rc = mg_fail(mg, RALA_HIP_EDEVICE, "hipSetDevice");
+    PafTarget T;
+    for (int k = 0; k < 7; ++k) T.col[k] = &cs->d_sens_col[k];
+    T.strand = &cs->d_sens_strand;
+    T.mhap = mhap;
+    IngestFront F;
+    GzipPieceRun* run = nullptr;
+    CloseRun close_run{cs, run};             // (compressed bytes, symbols and text are released on every way out)
+    PartKinds take;
+    take.bgzf_pieces = take.refuse_other = true;
+    take.gzip_whole = P == 1;
+    bool leave = false;
+    rc = ingest_front(mg, rc, path, mhap, false, threads, 0, T, take, run, F, irregular, &leave);
+    if (leave) return rc;
+    const uint64_t mine[12] = {F.R.n_lines, F.R.flags, F.piece[0], F.piece[1], F.piece[2] | (F.in_pieces ? 2u : 0u), F.own_crc[0], F.own_crc[1],
+                               F.own_crc[2], F.own_crc[3], F.own_crc[4], F.own_crc[5], F.own_crc[6]};
+    std::vector<uint64_t> all;
+    rc = agree_with(mg, rc, "device ingest of the sensitive overlaps", 0, mine, 12, all);
+    if (rc != RALA_HIP_OK) return rc;
+    const uint32_t flags = front_verdict(mg, F, run, all, 13, 1, 2, 5);
+    if (flags) { *irregular = (int)flags; return RALA_HIP_OK; }
+    uint64_t total = 0;
+    for (uint32_t p = 0; p < P; ++p) total += all[(size_t)p * 13 + 1];
+    if (total >= 0xFFFFFFF0ull) {
+        mg->verdict_shared = true;           // (from the exchanged counts: the same answer on every rank)
+        return mg_fail(mg, RALA_HIP_ETOOLARGE, "file positions must fit 32 bits");
+    }
+    out->a_id = cs->d_sens_col[0].p; out->b_id = cs->d_sens_col[1].p; out->a_begin = cs->d_sens_col[2].p; out->a_end = cs->d_sens_col[3].p;
+    out->b_begin = cs->d_sens_col[4].p; out->b_end = cs->d_sens_col[5].p; out->length = cs->d_sens_col[6].p; out->strand = cs->d_sens_strand.p;
+    *n = F.R.n_lines;
+    return RALA_HIP_OK;
+}
 }  // namespace
+
+int rala_hip_mg_tokenise_sensitive(rala_hip_mg* mg, const char* path, int format, uint32_t threads, rala_hip_overlaps* out, uint64_t* n, int* irregular) {
+    if (!mg || !path || !out || !n || !irregular || (format != 0 && format != 1)) return RALA_HIP_EINVAL;
+    *irregular = 0;
+    *n = 0;
+    if (!mg->comm) return mg_fail(mg, RALA_HIP_EINVAL, "the rank has not joined its group (rala_hip_mg_join)");
+    if (!mg->have_reads) return mg_fail(mg, RALA_HIP_EINVAL, "set the reads first");
+    mg->verdict_shared = false;
+    const int rc = tokenise_sensitive(mg, path, format == 1, threads, out, n, irregular);
+    // (a failure the others do not know of: they must not wait for this rank in the next collective)
+    if (rc != RALA_HIP_OK && !mg->verdict_shared) mg->comm->abort();
+    return rc;
+}
 
 namespace {
 

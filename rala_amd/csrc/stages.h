@@ -71,26 +71,37 @@ int overlap_tokenise_part(rala_hip_ctx* ctx, const char* path, uint32_t part, ui
 // gzip_on_device; ingest_gzip.hip), as steps with a host exchange between each two of them (sharded.hip makes those: every rank
 // makes every exchange, whatever a step returned).  `all` is what agree_with gathered: part p's words at all[p * stride + 1 ..].
 //   open      the file opened, its header and trailer read (no device): head = {1 if it is such a file, file size, where the
-//             deflate bytes begin, chunks, the trailer's CRC32, its ISIZE} - the ranks compare them before anything is shipped;
-//   find      the file shipped, block starts found in the part's own chunks (ingest_formats.h: gzip_part_chunk)  -> `most` words
-//   count     the own chunks counted, landing on the starts any rank found                                        -> 4 * most words
+//             deflate bytes begin, chunks, the (last) trailer's CRC32, its ISIZE, the option gzip_members} (7 words) - the ranks compare them before anything is shipped;
+//   find      the file shipped, block starts found in the part's own chunks (ingest_formats.h: gzip_part_chunk), with gzip_members the
+//             member headers of the whole file                     -> `most` + 1 words: the own chunks' starts, the headers found (or 0)
+//   count     the own chunks counted, landing on the starts any rank found, with gzip_members the own header candidates too
+//                                                                   -> gzip_piece_span_words: 4 per chunk and candidate of the most any part owns
 //   write     the chain (the same on every rank from the same words; *valid = false: refused, the steps end here), the own jobs
 //             and the halo's written, the out-window composed (gzip_window_compose_kernel)                       -> 8192 words
 //   tokenise  the window in front of the piece composed from all out-windows and uploaded as the carry, windows and resolve as
 //             they are, the lines that begin in the own text tokenised; own = {CRC register, length} of the own text
 //   proven    the registers of all parts chained: the trailer's CRC32 and the text's size
 //   close     the compressed bytes, symbols and text released, on every way out
+// With the option gzip_members beside them a file of SEVERAL members is taken the same way (head[6] = the option, compared by the
+// ranks): find also finds the member headers of the whole file (the same list on every rank; the last of its most + 1 words is
+// their number), count also counts the candidates whose deflate bytes begin in the own chunks (gzip_piece_span_words: the words
+// every part gives), write walks gzip_chain_members and composes the out-window with member floors
+// (gzip_window_compose_members_kernel), tokenise masks the window in front of the member the piece begins in and proves the
+// members inside the own text, own[2 .. 6] = what it owes the members that span ranks, members_proven: all of them, on every rank.
 struct GzipPieceRun;
-int gzip_piece_open(rala_hip_ctx* ctx, const char* path, bool mhap, uint64_t head[6], GzipPieceRun** run);
+int gzip_piece_open(rala_hip_ctx* ctx, const char* path, bool mhap, uint64_t head[7], GzipPieceRun** run);
 uint64_t gzip_piece_most_chunks(uint64_t n_chunks, uint32_t parts);
 int gzip_piece_find(rala_hip_ctx* ctx, GzipPieceRun* g, uint32_t part, uint32_t parts, uint32_t threads, std::vector<uint64_t>& starts_out);
 int gzip_piece_count(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, std::vector<uint64_t>& spans_out);
 int gzip_piece_write(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, bool* valid, std::vector<uint64_t>& window_out);
-int gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, uint32_t* flag, uint64_t own[2]);
+int gzip_piece_resolve(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, uint32_t* flag, uint64_t own[7]);
 void gzip_piece_text(const GzipPieceRun* g, uint64_t* own_n, uint64_t* n_w, uint64_t* file_n, float* ship_ms, uint32_t* n_readers);
 int gzip_piece_tokenise(rala_hip_ctx* ctx, GzipPieceRun* g, const uint64_t* all, size_t stride, bool check_lengths, uint32_t threads,
-                        size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t own[2]);
+                        size_t extra_rows, const PafTarget& T, PafRange* out, uint64_t own[7]);
 bool gzip_piece_proven(const GzipPieceRun* g, const uint32_t* reg, const uint64_t* len, uint32_t parts);
+size_t gzip_piece_span_words(GzipPieceRun* g, const uint64_t* all, size_t stride);
+bool gzip_piece_members(const GzipPieceRun* g);
+bool gzip_piece_members_proven(const GzipPieceRun* g, const uint64_t* all, size_t stride, size_t at);
 void gzip_piece_exchange_ms(rala_hip_ctx* ctx, float ms);
 void gzip_piece_close(rala_hip_ctx* ctx, GzipPieceRun* g);
 

@@ -33,7 +33,8 @@ SYMBOLS = (
     "rala_hip_mg_unique_id", "rala_hip_mg_local_group_create", "rala_hip_mg_local_group_destroy", "rala_hip_mg_create",
     "rala_hip_mg_create_contexts", "rala_hip_mg_join", "rala_hip_set_name_table", "rala_hip_set_overlaps_from_paf", "rala_hip_set_overlaps_from_mhap",
     "rala_hip_get_ingest_timings", "rala_hip_get_inflate_timings", "rala_hip_get_gzip_timings", "rala_hip_gzip_head", "rala_hip_gzip_chain", "rala_hip_gzip_chain_members", "rala_hip_gzip_find_members", "rala_hip_get_gzip_members",
-    "rala_hip_gzip_pieces", "rala_hip_gzip_compose_windows", "rala_hip_get_gzip_pieces_info", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
+    "rala_hip_gzip_pieces", "rala_hip_gzip_compose_windows", "rala_hip_get_gzip_pieces_info", "rala_hip_gzip_compose_windows_masked", "rala_hip_gzip_members_proof",
+    "rala_hip_get_gzip_member_pieces_info", "rala_hip_mg_tokenise_sensitive", "rala_hip_bgzf_index", "rala_hip_get_overlap_columns", "rala_hip_tokenise_sensitive_paf",
     "rala_hip_bgzf_index_range", "rala_hip_bgzf_pieces_chain", "rala_hip_tokenise_sensitive", "rala_hip_mg_set_overlaps_from_mhap",
     "rala_hip_mg_set_overlaps_from_paf", "rala_hip_mg_get_slice",
     "rala_hip_index_sequences", "rala_hip_get_sequence_index", "rala_hip_get_sequence_timings",
@@ -106,6 +107,15 @@ class GzipPiecesInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GzipMemberPiecesInfo(ctypes.Structure):
+    """rala_hip_gzip_member_pieces_info"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("own_candidates", "members_begun", "member_ends")] + [
+        ("registers_sent", ctypes.c_uint32), ("floor_stops", ctypes.c_uint32), ("compose_ms", ctypes.c_float), ("pad", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
 
 
 GZIP_WINDOW = 32768
@@ -269,6 +279,9 @@ def lib(build=True):
         L.rala_hip_gzip_pieces.argtypes = [vp, u64, u64, u64, u64, u32, vp]
         L.rala_hip_gzip_compose_windows.argtypes = [vp, u32, u32, vp, ctypes.POINTER(i32)]
         L.rala_hip_get_gzip_pieces_info.argtypes = [vp, ctypes.POINTER(GzipPiecesInfo)]
+        L.rala_hip_gzip_compose_windows_masked.argtypes = [vp, u32, vp, u32, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.rala_hip_gzip_members_proof.argtypes = [vp, vp, vp, u64] + [vp] * 7 + [u32, ctypes.POINTER(u64), ctypes.POINTER(i32)]
+        L.rala_hip_get_gzip_member_pieces_info.argtypes = [vp, ctypes.POINTER(GzipMemberPiecesInfo)]
         L.rala_hip_layout_split.argtypes = [u32, vp, u32, u32, vp, vp]
         L.rala_hip_mg_layout_batch.argtypes = [vp, u32] + [vp] * 8 + [u32, ctypes.c_double, ctypes.c_double]
         L.rala_hip_mg_layout_batch_threads.argtypes = [vp, u32, u32] + [vp] * 6 + [u32, ctypes.c_double, ctypes.c_double]
@@ -540,6 +553,11 @@ class Context:
     def gzip_pieces_info(self):
         t = GzipPiecesInfo()
         self._check(self.L.rala_hip_get_gzip_pieces_info(self.h, ctypes.byref(t)))
+        return t.as_dict()
+
+    def gzip_member_pieces_info(self):
+        t = GzipMemberPiecesInfo()
+        self._check(self.L.rala_hip_get_gzip_member_pieces_info(self.h, ctypes.byref(t)))
         return t.as_dict()
 
     def gzip_members(self):
@@ -1049,6 +1067,40 @@ def gzip_compose_windows(out_windows, part):
     if rc != 0:
         raise RalaHipError(rc, "rala_hip_gzip_compose_windows")
     return got, valid.value
+
+
+def gzip_compose_windows_masked(out_windows, reach, part):
+    """rala_hip_gzip_compose_windows_masked (no device): (the window in front of `part` masked in front of the member the part begins
+    in, the byte in front of the part from the unmasked window or -1, valid).  out_windows: parts x 32768 uint16; reach: per part,
+    the text bytes between the first byte of the member its text begins in and its own first byte."""
+    w = np.ascontiguousarray(out_windows, dtype=np.uint16).reshape(-1, GZIP_WINDOW)
+    r = np.ascontiguousarray(reach, dtype=np.uint64)
+    assert len(r) == len(w)
+    got = np.zeros(GZIP_WINDOW, dtype=np.uint16)
+    before, valid = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib().rala_hip_gzip_compose_windows_masked(w.ctypes.data, len(w), r.ctypes.data, part, got.ctypes.data, ctypes.byref(before), ctypes.byref(valid))
+    if rc != 0:
+        raise RalaHipError(rc, "rala_hip_gzip_compose_windows_masked")
+    return got, before.value, bool(valid.value)
+
+
+def gzip_members_proof(members, parts, head, tail, local_bad):
+    """rala_hip_gzip_members_proof (no device): (valid, first member that fails).  members: [(text_off, text_n, crc32)]; parts:
+    [(begin, end)] of the text; head, tail: [(register, length)] per part; local_bad: per part, a member index or None."""
+    m_off, m_n = (np.array([m[k] for m in members], dtype=np.uint64) for k in (0, 1))
+    m_crc = np.array([m[2] for m in members], dtype=np.uint32)
+    a, b = (np.array([p[k] for p in parts], dtype=np.uint64) for k in (0, 1))
+    h_reg, t_reg = (np.array([x[0] for x in regs], dtype=np.uint32) for regs in (head, tail))
+    h_len, t_len = (np.array([x[1] for x in regs], dtype=np.uint64) for regs in (head, tail))
+    bad_here = np.array([0xFFFFFFFFFFFFFFFF if x is None else x for x in local_bad], dtype=np.uint64)
+    assert len(a) == len(h_reg) == len(t_reg) == len(bad_here)
+    bad, valid = ctypes.c_uint64(0), ctypes.c_int32(0)
+    rc = lib().rala_hip_gzip_members_proof(m_off.ctypes.data, m_n.ctypes.data, m_crc.ctypes.data, len(members), a.ctypes.data, b.ctypes.data, h_reg.ctypes.data,
+                                           h_len.ctypes.data, t_reg.ctypes.data, t_len.ctypes.data, bad_here.ctypes.data, len(a), ctypes.byref(bad),
+                                           ctypes.byref(valid))
+    if rc != 0:
+        raise RalaHipError(rc, "rala_hip_gzip_members_proof")
+    return bool(valid.value), int(bad.value)
 
 
 def gzip_chain_members(chunks, cands, file_n, last_crc, last_isize):

@@ -379,9 +379,12 @@ void Graph::initialize() {
     // bgzf_in_pieces; a file whose pieces do not join, or any other gzip file, is irregular there and the host reader decides)
     // ... and, where io::device_gzip_wanted() says so as well (RALA_DEVICE_GZIP=1), a .gz file of one gzip member that is not
     // BGZF together (options gzip_on_device and gzip_in_pieces on every rank: the chunks' starts and spans and one window of
-    // 32 768 symbols per rank travel between them).  A file of several members (RALA_DEVICE_GZIP=2) stays the host reader's.
+    // 32 768 symbols per rank travel between them).  A file of several members (RALA_DEVICE_GZIP=2) stays the host reader's
+    // unless io::device_compressed_members_wanted() (RALA_DEVICE_COMPRESSED=2): then the option gzip_members joins the two on
+    // every rank and the ranks take any chain of such members together.
     const int gz_kind = gz && !ranks_.empty() && io::device_compressed_wanted() ? io::sniff_compression(overlaps_path_) : 0;
-    const bool ranks_gzip = gz_kind == 2 && io::device_gzip_wanted() && !io::device_gzip_members_wanted();
+    const bool ranks_members = gz_kind == 2 && io::device_gzip_members_wanted() && io::device_compressed_members_wanted();
+    const bool ranks_gzip = gz_kind == 2 && io::device_gzip_wanted() && (!io::device_gzip_members_wanted() || ranks_members);
     const bool ranks_compressed = !ranks_.empty() && io::device_compressed_wanted() && (gz ? gz_kind == 1 || ranks_gzip : mhap_text);
     const bool device_ingest = (io::has_suffix(overlaps_path_, ".paf") || ((mhap_text || gz) && ranks_.empty()) || ranks_compressed) &&
                                !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
@@ -443,6 +446,8 @@ void Graph::initialize() {
                     r_opt = rala_hip_set_option(rala_hip_mg_context(mg), "gzip_on_device", 1);
                     const int r_pieces = rala_hip_set_option(rala_hip_mg_context(mg), "gzip_in_pieces", 1);
                     if (r_opt == RALA_HIP_OK) r_opt = r_pieces;
+                    const int r_members = ranks_members ? rala_hip_set_option(rala_hip_mg_context(mg), "gzip_members", 1) : RALA_HIP_OK;
+                    if (r_opt == RALA_HIP_OK) r_opt = r_members;
                 }
                 int r = rala_hip_mg_set_reads(mg, read_len_.data(), read_len_.size());
                 if (r == RALA_HIP_OK) r = r_opt;
@@ -563,8 +568,12 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
         const bool s_gz = io::has_suffix(sensitive_overlaps_path, ".gz");
         const bool s_mhap = io::has_suffix(sensitive_overlaps_path, ".mhap") || io::has_suffix(sensitive_overlaps_path, ".mhap.gz");
         const int s_kind = s_gz && io::device_compressed_wanted() ? io::sniff_compression(sensitive_overlaps_path) : 0;
+        // With io::device_compressed_members_wanted() (RALA_DEVICE_COMPRESSED=2) the -s file of a sharded run goes through ONE
+        // collective instead (rala_hip_mg_tokenise_sensitive: the pieces joined in there), and with it a gzip file that is not
+        // BGZF over the ranks together where io::device_gzip_wanted() - several members where RALA_DEVICE_GZIP=2.
+        const bool s_collective = !ranks_.empty() && io::device_compressed_members_wanted();
         const bool s_compressed = io::device_compressed_wanted() &&
-                                  (s_gz ? s_kind == 1 || (s_kind == 2 && P == 1 && io::device_gzip_wanted()) : s_mhap);
+                                  (s_gz ? s_kind == 1 || (s_kind == 2 && (P == 1 || s_collective) && io::device_gzip_wanted()) : s_mhap);
         const bool device_ingest = (io::has_suffix(sensitive_overlaps_path, ".paf") || s_compressed) &&
                                    (name_table_.n_buckets() != 0 || device_names_) &&       // (a table is installed, or can be)
                                    !(getenv("RALA_DEVICE_INGEST") && atoi(getenv("RALA_DEVICE_INGEST")) == 0);
@@ -586,7 +595,24 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
                     rc[k] = device_names_ ? rala_hip_copy_name_table(c, ctx_)
                                           : rala_hip_set_name_table(c, name_table_.buckets(), name_table_.n_buckets(), name_table_.arena().data(),
                                                                     name_table_.arena().size());
-                    if (rc[k] == RALA_HIP_OK && s_compressed) {
+                    if (s_collective) {
+                        // (the options that decide which exchanges the call makes hang on nothing this rank alone can see; a rank
+                        // that failed above still makes the call, with nothing to read, so that nobody waits for it)
+                        int r_opt = RALA_HIP_OK;
+                        if (s_kind == 2) {
+                            for (const char* key : {"gzip_on_device", "gzip_in_pieces"}) {
+                                const int r1 = rala_hip_set_option(c, key, 1);
+                                if (r_opt == RALA_HIP_OK) r_opt = r1;
+                            }
+                            const int r2 = rala_hip_set_option(c, "gzip_members", io::device_gzip_members_wanted() ? 1 : 0);
+                            if (r_opt == RALA_HIP_OK) r_opt = r2;
+                        }
+                        if (rc[k] == RALA_HIP_OK) rc[k] = r_opt;
+                        const char* const path = rc[k] == RALA_HIP_OK ? sensitive_overlaps_path.c_str() : "";
+                        const int r3 = rala_hip_mg_tokenise_sensitive(ranks_[k], path, s_mhap ? 1 : 0, std::max(1u, num_threads_ / P), &device_shares_[k],
+                                                                      &device_share_n_[k], &irregular[k]);
+                        if (rc[k] == RALA_HIP_OK) rc[k] = r3;
+                    } else if (rc[k] == RALA_HIP_OK && s_compressed) {
                         if (s_kind == 2) {
                             rc[k] = rala_hip_set_option(c, "gzip_on_device", 1);
                             if (rc[k] == RALA_HIP_OK && io::device_gzip_members_wanted()) rc[k] = rala_hip_set_option(c, "gzip_members", 1);
@@ -605,7 +631,7 @@ void Graph::construct(const std::string& sensitive_overlaps_path) {
             for (auto& t : th) t.join();
             sens_on_device_ = true;
             for (uint32_t k = 0; k < P; ++k) sens_on_device_ = sens_on_device_ && rc[k] == RALA_HIP_OK && !irregular[k];
-            if (sens_on_device_ && s_kind == 1) {
+            if (sens_on_device_ && s_kind == 1 && !s_collective) {
                 // (no collective in there: whether the contexts' pieces are the whole file is known only now)
                 std::vector<uint64_t> begin(P), end(P);
                 std::vector<int> empty(P);

@@ -137,6 +137,11 @@ struct PafOnDevice {
     std::vector<uint64_t> member_off, member_n;     // rala_hip_get_gzip_members of the call
     std::vector<rala_hip_gzip_pieces_info> pieces;   // rala_hip_get_gzip_pieces_info of every rank (hp_text_device_ranks)
     std::vector<uint32_t> member_crc;
+    // rala_hip_get_gzip_members and rala_hip_get_gzip_member_pieces_info of every rank's slice context (hp_text_device_ranks)
+    std::vector<std::vector<uint64_t>> rank_member_off, rank_member_n;
+    std::vector<std::vector<uint32_t>> rank_member_crc;
+    std::vector<rala_hip_gzip_member_pieces_info> member_pieces;
+    std::vector<int> before_rc;     // what every rank's call on the file ingested first returned (hp_text_device_ranks)
     int before_irregular = 0;       // what the file ingested first on the same context gave (hp_text_device_after)
     int64_t before_bad = -1;
 };
@@ -330,6 +335,9 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
     std::vector<std::vector<uint8_t>> strand(world);
     std::vector<uint64_t> share(3 * (size_t)world, 0);
     out->pieces.assign(world, rala_hip_gzip_pieces_info());
+    out->member_pieces.assign(world, rala_hip_gzip_member_pieces_info());
+    out->before_rc.assign(world, RALA_HIP_OK);
+    out->rank_member_off.resize(world); out->rank_member_n.resize(world); out->rank_member_crc.resize(world);
     if (out->rc == RALA_HIP_OK) {
         std::vector<std::thread> th;
         for (uint32_t k = 0; k < world; ++k) {
@@ -338,7 +346,21 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
                 int r = rala_hip_mg_join(mg, RALA_HIP_COMM_LOCAL, group);
                 if (r == RALA_HIP_OK) r = rala_hip_mg_set_reads(mg, read_len, n_reads);
                 rala_hip_ctx* cs = rala_hip_mg_context(mg);
-                for (uint32_t o = 0; o < n_options && r == RALA_HIP_OK; ++o) r = rala_hip_set_option(cs, keys[o], values[o]);
+                // (a key "name@k" is rank k's alone and holds for the file ingested `before` only: behind that call rank k takes the
+                // group's value of "name", which must be among the keys - ranks that disagree on an option the roll call compares)
+                auto own_key = [&](const char* key, std::string* name) {
+                    const char* at = strchr(key, '@');
+                    if (!at) return false;
+                    *name = std::string(key, (size_t)(at - key));
+                    return (uint32_t)atoi(at + 1) == k;
+                };
+                bool disagrees = false;
+                for (uint32_t o = 0; o < n_options && r == RALA_HIP_OK; ++o) if (!strchr(keys[o], '@')) r = rala_hip_set_option(cs, keys[o], values[o]);
+                for (uint32_t o = 0; o < n_options && r == RALA_HIP_OK; ++o) {
+                    std::string name;
+                    if (strchr(keys[o], '@')) disagrees = true;
+                    if (own_key(keys[o], &name)) r = rala_hip_set_option(cs, name.c_str(), values[o]);
+                }
                 if (r == RALA_HIP_OK && !mhap) r = rala_hip_set_name_table(cs, table.buckets(), table.n_buckets(), table.arena().data(), table.arena().size());
                 uint64_t first = 0, n = 0;
                 std::vector<uint32_t> got[7];
@@ -353,10 +375,13 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
                 };
                 if (sensitive) {
                     rala_hip_overlaps dev = {};
-                    if (r == RALA_HIP_OK && before) {
-                        r = rala_hip_tokenise_sensitive(cs, before, mhap ? 1 : 0, k, world, threads, &dev, &n, &share[3 * k], &before_irregular[k]);
-                    }
-                    if (r == RALA_HIP_OK) r = rala_hip_tokenise_sensitive(cs, path, mhap ? 1 : 0, k, world, threads, &dev, &n, &share[3 * k], &irregular[k]);
+                    // (sensitive == 2: through the one collective, rala_hip_mg_tokenise_sensitive - nothing to join behind it)
+                    auto take = [&](const char* file, int* irr) {
+                        return sensitive == 2 ? rala_hip_mg_tokenise_sensitive(mg, file, mhap ? 1 : 0, threads, &dev, &n, irr)
+                                              : rala_hip_tokenise_sensitive(cs, file, mhap ? 1 : 0, k, world, threads, &dev, &n, &share[3 * k], irr);
+                    };
+                    if (r == RALA_HIP_OK && before) r = take(before, &before_irregular[k]);
+                    if (r == RALA_HIP_OK) r = take(path, &irregular[k]);
                     // (read back through the context: the columns are plain device memory, adopted as its overlaps)
                     if (r == RALA_HIP_OK && !irregular[k]) r = rala_hip_set_overlaps(cs, &dev, n, RALA_HIP_MEM_DEVICE);
                     if (r == RALA_HIP_OK && !irregular[k]) r = read_back(n);
@@ -367,6 +392,16 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
                     };
                     if (r == RALA_HIP_OK && before) {
                         r = ingest(before, &before_bad[k], &before_irregular[k]);
+                        out->before_rc[k] = r;
+                        if (disagrees) {
+                            // (what every rank's call returned is the result - hp_paf_device_before_rc; the group must still be usable)
+                            r = RALA_HIP_OK;
+                            for (uint32_t o = 0; o < n_options && r == RALA_HIP_OK; ++o) {
+                                std::string name;
+                                if (!own_key(keys[o], &name)) continue;
+                                for (uint32_t q = 0; q < n_options; ++q) if (name == keys[q]) r = rala_hip_set_option(cs, keys[q], values[q]);
+                            }
+                        }
                         // (nothing was set by a refusal)
                         if (r == RALA_HIP_OK && before_irregular[k] && rala_hip_mg_get_slice(mg, &first, &n) == RALA_HIP_OK) r = RALA_HIP_EDEVICE;
                         first = n = 0;
@@ -381,6 +416,13 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
                 }
                 slices[2 * k] = first; slices[2 * k + 1] = n;
                 (void)rala_hip_get_gzip_pieces_info(cs, &out->pieces[k]);
+                (void)rala_hip_get_gzip_member_pieces_info(cs, &out->member_pieces[k]);
+                uint64_t n_members = 0;
+                if (rala_hip_get_gzip_members(cs, &n_members, 0, nullptr, nullptr, nullptr) == RALA_HIP_OK && n_members) {
+                    out->rank_member_off[k].resize(n_members); out->rank_member_n[k].resize(n_members); out->rank_member_crc[k].resize(n_members);
+                    (void)rala_hip_get_gzip_members(cs, &n_members, n_members, out->rank_member_off[k].data(), out->rank_member_n[k].data(),
+                                                    out->rank_member_crc[k].data());
+                }
                 for (int c = 0; c < 7; ++c) col[c][k] = std::move(got[c]);
                 strand[k] = std::move(got_strand);
                 rc[k] = r;
@@ -395,11 +437,11 @@ void* hp_text_device_ranks(const char* path, const char* before, const char* nam
         if (bad[k] >= 0 && out->bad < 0) out->bad = bad[k];
         if (before_bad[k] >= 0 && out->before_bad < 0) out->before_bad = before_bad[k];
         // (every rank the same verdict: one that differs shows as a value no rank gave)
-        if (!sensitive && (irregular[k] != irregular[0] || before_irregular[k] != before_irregular[0])) out->irregular |= 1 << 20;
+        if (sensitive != 1 && (irregular[k] != irregular[0] || before_irregular[k] != before_irregular[0])) out->irregular |= 1 << 20;
         for (int c = 0; c < 7; ++c) out->col[c].insert(out->col[c].end(), col[c][k].begin(), col[c][k].end());
         out->strand.insert(out->strand.end(), strand[k].begin(), strand[k].end());
     }
-    if (sensitive && out->rc == RALA_HIP_OK && !out->irregular && rala::io::sniff_compression(path) == 1) {
+    if (sensitive == 1 && out->rc == RALA_HIP_OK && !out->irregular && rala::io::sniff_compression(path) == 1) {
         std::vector<uint64_t> begin(world), end(world);
         std::vector<int> empty(world);
         for (uint32_t k = 0; k < world; ++k) { begin[k] = share[3 * k]; end[k] = share[3 * k + 1]; empty[k] = (int)share[3 * k + 2]; }
@@ -447,6 +489,30 @@ int hp_paf_device_pieces_info(void* h, uint32_t k, int64_t* info) {
     info[4] = (int64_t)p.window_markers; info[5] = (int64_t)p.longest_chase;
     info[6] = (int64_t)(p.compose_ms * 1000.0f); info[7] = (int64_t)(p.exchange_ms * 1000.0f);
     return 1;
+}
+// rank k's view of the members of a gzip file the ranks took together (hp_text_device_ranks; rala_hip_get_gzip_members on its slice
+// context): their number; with cap >= it, each one's text offset, text size and CRC32
+uint64_t hp_paf_device_rank_members(void* h, uint32_t k, uint64_t cap, uint64_t* text_off, uint64_t* text_n, uint32_t* crc32) {
+    const auto* o = (const PafOnDevice*)h;
+    if (k >= o->rank_member_off.size()) return 0;
+    const uint64_t n = o->rank_member_off[k].size();
+    for (uint64_t m = 0; m < n && cap >= n; ++m) { text_off[m] = o->rank_member_off[k][m]; text_n[m] = o->rank_member_n[k][m]; crc32[m] = o->rank_member_crc[k][m]; }
+    return n;
+}
+// ... and what its piece saw of them (rala_hip_get_gzip_member_pieces_info): info[0 .. 5] = own candidates, members begun, member
+// ends, registers sent, floor stops, compose us; 0: no such rank
+int hp_paf_device_member_pieces_info(void* h, uint32_t k, int64_t* info) {
+    const auto* o = (const PafOnDevice*)h;
+    if (k >= o->member_pieces.size()) return 0;
+    const rala_hip_gzip_member_pieces_info& p = o->member_pieces[k];
+    info[0] = (int64_t)p.own_candidates; info[1] = (int64_t)p.members_begun; info[2] = (int64_t)p.member_ends; info[3] = (int64_t)p.registers_sent;
+    info[4] = (int64_t)p.floor_stops; info[5] = (int64_t)(p.compose_ms * 1000.0f);
+    return 1;
+}
+// what rank k's call on the file ingested first returned (hp_text_device_ranks with `before`; a rala_hip code, 0: no such rank or OK)
+int hp_paf_device_before_rc(void* h, uint32_t k) {
+    const auto* o = (const PafOnDevice*)h;
+    return k < o->before_rc.size() ? o->before_rc[k] : 0;
 }
 void hp_paf_device_copy(void* h, uint32_t* a_id, uint32_t* b_id, uint32_t* a_begin, uint32_t* a_end, uint32_t* b_begin, uint32_t* b_end,
                         uint32_t* length, uint8_t* strand) {

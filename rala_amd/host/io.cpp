@@ -92,6 +92,11 @@ bool device_compressed_wanted() {
     return e ? atoi(e) != 0 : false;
 }
 
+bool device_compressed_members_wanted() {
+    const char* e = getenv("RALA_DEVICE_COMPRESSED");
+    return e ? atoi(e) == 2 : false;
+}
+
 int sniff_compression(const std::string& path) {
     unsigned char h[18] = {0};
     FILE* f = fopen(path.c_str(), "rb");

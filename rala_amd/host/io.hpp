@@ -46,6 +46,10 @@ bool device_gzip_members_wanted();
  * .mhap or .mhap.gz given with -s (rala_hip_tokenise_sensitive)?  RALA_DEVICE_COMPRESSED=1 says so; without it: no - unmeasured,
  * see README.md, "Compressed overlap files" */
 bool device_compressed_wanted();
+/*! @brief ... and, beside all of that, does a gzip file of several members that is not BGZF go over the ranks of a run on several
+ * GPUs together where device_gzip_members_wanted() (rala_hip options "gzip_on_device", "gzip_in_pieces" and "gzip_members" on every
+ * rank)?  RALA_DEVICE_COMPRESSED=2 says so; =1 leaves such a file to the host reader as before - unmeasured */
+bool device_compressed_members_wanted();
 /*! @brief does Graph::postprocess lay out all components of a round in one call (rala_hip_layout_batch) instead of one
  * rala_hip_layout per component?  RALA_LAYOUT_BATCH=1 says so; without it: no - the same weights either way; many components
  * gain a lot, one giant component loses 1 %, see README.md, "Layout of all components in one call" */
